@@ -20,6 +20,13 @@ A "step" is one integration step of the batch: one evaluation of the vector-fiel
 consecutive steps of a real trajectory that starts at the prior (the W warm-up steps come first and
 contain the bootstrap evaluation).  A 250-timestep sample costs 250 network evaluations (249 steps + 1
 bootstrap), hence   molecules/s @250 = global_molecules / (250 * seconds_per_step).
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, then ONE compact JSON line.  ``--full``
+adds everything else the line used to carry, each after the timed region: the event-instrumented per-kernel pass and the roofline of the
+dominant kernel, the secondary legs (size distribution, C2, C5, latency sweeps, opt-in precisions), the end-to-end FlowMol.sample() timing,
+the CPU baseline, and on N > 1 GPUs the multi-GPU parity check before the timed region and the size-distribution leg after it.
+``--dump-outputs DIR`` writes what the last timed step computed (final state and endpoint prediction; on N > 1 GPUs the gathered batch)
+as DIR/<name>.npy in float32; the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -689,6 +696,30 @@ def bind_rank_to_gpu_socket(dev_index):
     return info
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6          # --dump-outputs writes at most this much; larger outputs: the same seeded subset of rows every run
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write every array as <out_dir>/<name>.npy in float32 (integer tokens are exact in float32).  When the arrays together exceed
+    DUMP_BUDGET_BYTES, every array keeps the same fraction of its rows, chosen by a fixed seed and kept in order, so two runs of the same
+    arguments write the same rows."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().to('cpu', torch.float32).contiguous() for k, v in arrays.items()}
+    total = sum(t.numel() * t.element_size() for t in host.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    shapes = {}
+    for k, t in host.items():
+        if frac < 1.0 and t.shape[0] > 1:
+            keep = max(1, int(t.shape[0] * frac))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+            t = t[rows]
+        np.save(out_dir / f'{k}.npy', t.numpy())
+        shapes[k] = list(t.shape)
+    return {'dir': str(out_dir), 'dtype': 'float32', 'arrays': shapes, 'row_sample': None if frac >= 1.0 else f'seeded subset of {frac:.4f} of the rows (seed {seed})'}
+
+
 def dry_run(args):
     """`bench.py --gpus N --dry-run`: the N-rank plan without touching a GPU -- molecules and cost per rank, payload bytes of the one
     all-gather, the device each rank would take and the launch line."""
@@ -709,7 +740,7 @@ def dry_run(args):
            'launch': f'python -m torch.distributed.run --nnodes=1 --nproc-per-node {world} --master-addr 127.0.0.1 --master-port P bench.py --gpus {world} --steps {args.steps} --warmup {args.warmup}',
            'backend': 'nccl (RCCL over xGMI); one process per GPU; no collective during integration, ONE all_gather_into_tensor at the end',
            }
-    if world > 1:          # what the run will check before it times anything (multi_gpu_parity)
+    if world > 1:          # what a --full run will check before it times anything (multi_gpu_parity)
         from flowmol_amd import shard
         pn = parity_job_sizes(world)
         pparts = shard.partition_lpt(pn, world)
@@ -717,7 +748,7 @@ def dry_run(args):
         out['multi_gpu_parity_plan'] = {
             'world_size': world, 'molecules': int(pn.numel()), 'n_timesteps': PARITY_T, 'seed': PARITY_SEED, 'sizes': pn.tolist(),
             'molecules_per_rank': [int(len(p_)) for p_ in pparts], 'payload_bytes_per_rank': pay, 'all_gather_slot_bytes': slot_p, 'all_gather_bytes': slot_p * world,
-            'checks': "sample_distributed(noise='replicated' and 'philox') on the N ranks == sample() of the same seed on rank 0: token_diffs == 0, x_rel < 1e-4, every rank holds the same "
+            'checks': "with --full: sample_distributed(noise='replicated' and 'philox') on the N ranks == sample() of the same seed on rank 0: token_diffs == 0, x_rel < 1e-4, every rank holds the same "
                       'gathered batch; emitted as `multi_gpu_parity` {token_diffs, x_rel, philox_token_diffs, world_size, distinct_pci_devices, rccl_version, all_gather_bytes, ok} in the JSON '
                       'line; a failing check exits non-zero before the timed region',
             'exercised_by': 'tests/test_gpu_parity.py::test_bench_multi_gpu_line_carries_parity_block (8 gloo ranks on one GPU; nccl with 2 and all devices when the box has them)'}
@@ -750,7 +781,14 @@ def main():
     ap.add_argument('--cpu-mols', type=int, default=16)
     ap.add_argument('--cpu-steps', type=int, default=8)
     ap.add_argument('--cpu-ref-batch', type=int, default=128, help="CPU baseline at the reference protocol's batch size (test.py:30); 0 = only the --cpu-mols sample")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure: per-kernel times and roofline, secondary legs, end-to-end API timing, '
+                         'CPU baseline, multi-GPU parity (the --no-* options above select among these)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     wl = WORKLOADS[args.workload]
     args.preset = args.preset or wl['preset']
     args.mols_per_gpu = args.mols_per_gpu or wl['mols']
@@ -797,7 +835,7 @@ def main():
     cost = (all_sizes * (all_sizes - 1)).double()
     shard_cost = torch.tensor([float(cost[p_].sum()) for p_ in parts])
     parity = None
-    if world > 1:
+    if world > 1 and args.full:
         parity = multi_gpu_parity(cfg, sd, eng, world, rank, dev, dist.get_backend())
         if not parity['ok']:
             if rank == 0:
@@ -829,11 +867,11 @@ def main():
     for w in range(n_win):
         leg.advance(win_steps[w])
         win_ev[w + 1].record()
-    gather_ms = None
+    gather_ms = gathered = None
     if world > 1:   # inside the timed region: the job is not done until every rank holds the results
         torch.cuda.synchronize(dev)
         tg = time.perf_counter()
-        gather_all()
+        gathered = gather_all()
         torch.cuda.synchronize(dev)
         gather_ms = (time.perf_counter() - tg) * 1e3
     torch.cuda.synchronize(dev)
@@ -865,19 +903,32 @@ def main():
     evals = T if cfg.self_conditioning else T - 1      # network evaluations per sample: T-1 steps (+ the bootstrap evaluation of self-conditioned models)
     mols_per_s = B * world / (evals * ms_per_step / 1e3)
 
-    # ---- per-kernel timing (HIP events on the launch stream) for the roofline of the dominant kernel: a separate
-    #      event-instrumented pass of 2 more steps AFTER the timed region
+    # ---- what the last timed step computed, before anything advances the trajectory further: the state and the endpoint prediction of this
+    #      rank's batch (one GPU), or the batch every rank holds after the all-gather (N GPUs; written by rank 0)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if gathered is not None:
+            arrays = dict(gathered)
+        else:
+            st, pred = leg.state, leg.run.last_dst()
+            arrays = {'x': st['x_t'], 'a': st['a_t'], 'c': st['c_t'], 'e': st['e_t']}
+            if pred is not None:
+                arrays.update({f'pred_{k}': v for k, v in pred.items()})
+        dumped = dump_outputs(args.dump_outputs, arrays)
+
     finite = bool(torch.isfinite(leg.state['x_t']).all().item())
     try:            # which build of the kernels produced this line: digest of csrc/ + header + flags (flowmol_amd/build.py), as in profiles/current_pmc.json
         from flowmol_amd import build as fm_build
         lib_digest = fm_build.STAMP.read_text().strip()[:16]
     except Exception:
         lib_digest = None
-    kern, ev_overhead = leg.kernel_times(2)
+    ex = executed_macs(cfg, U, torch.cuda.get_device_properties(dev).multi_processor_count)
+    # ---- --full: per-kernel timing (HIP events on the launch stream) for the roofline of the dominant kernel: a separate
+    #      event-instrumented pass of 2 more steps AFTER the timed region
+    kern, ev_overhead = leg.kernel_times(2) if args.full else ({}, None)
     launches_per_step = sum(v['launches_per_step'] for v in kern.values())
     # counters of the dominant kernel from the committed rocprofv3 PMC passes (same workload AND same library digest only); never measured by this run
-    pmc = load_pmc(args.workload, N, E, args.size_dist is None and args.precision == 'f32' and world == 1)
-    ex = executed_macs(cfg, U, torch.cuda.get_device_properties(dev).multi_processor_count)
+    pmc = load_pmc(args.workload, N, E, args.size_dist is None and args.precision == 'f32' and world == 1) if args.full else None
     roofline = None
     if 'edge_message' in kern and args.precision in ('bf16x3', 'bf16x6', 'f16x3'):
         # opt-in mode: the scalar and gate GEMMs issue 3 bf16 products per term on padded K (7 / 10 / 10 k32 blocks); the vector path stays f32
@@ -924,36 +975,40 @@ def main():
                    'process_group': {'size': world, 'backend': (dist.get_backend() if world > 1 else None), 'rccl_version': rccl, 'ranks': rank_info}},
         'network_eval_ms': ms_per_step, 'ms_per_step_windows': windows, 'per_rank_ms_per_step': per_rank_ms, 'final_gather_ms': gather_ms,
         'multi_gpu_parity': parity,
-        'launches_per_step': launches_per_step,
         'whole_path': None if args.precision != 'f32' else {'algorithmic_tflops_per_gpu': alg_tf, 'executed_tflops_per_gpu': exe_tf,
                        'executed_frac': exe_tf / FP32_PEAK_TFLOPS,
                        'algorithmic_over_executed': alg_tf / exe_tf,
                        'note': 'algorithmic = the reference-executed FLOP count of a network evaluation (BASELINE.md section 2) per second; executed = MFMA FLOPs '
                                'the kernels issue (per-source terms hoisted to per-node GEMMs, few-input embeddings tabulated); only executed_frac is a '
                                'fraction of the f32 peak -- the algorithmic rate may exceed the peak because fewer FLOPs are executed'},
-        'kernels': kern,
-        'kernels_note': 'per-kernel averages come from a separate HIP-event-instrumented pass of 2 steps after the timed region; '
-                        f'avg_us = event pair minus the pair overhead measured in the same pass on an empty kernel ({ev_overhead:.1f} us)',
     }
+    if args.full:
+        out['launches_per_step'] = launches_per_step
+        out['kernels'] = kern
+        out['kernels_note'] = ('per-kernel averages come from a separate HIP-event-instrumented pass of 2 steps after the timed region; '
+                               f'avg_us = event pair minus the pair overhead measured in the same pass on an empty kernel ({ev_overhead:.1f} us)')
     if roofline:
         out['roofline'] = roofline
+    if dumped:
+        out['outputs'] = dumped
     out['config']['canonical_arithmetic'] = eng.tuning.get('canonical', 0) >= 0
-    if rank == 0 and world == 1 and args.workload == 'c3' and args.precision == 'f32' and args.size_dist is None and not args.no_secondary:
+    out['config']['full'] = bool(args.full)
+    if args.full and rank == 0 and world == 1 and args.workload == 'c3' and args.precision == 'f32' and args.size_dist is None and not args.no_secondary:
         del leg
         out['secondary'] = secondary_legs({args.preset: (cfg, eng)}, dev, lib_digest, args.secondary_steps)
         # BASELINE.json's metric reads "(GEOM-drugs size dist)": that figure next to `value` (which north_star asks on fixed-size graphs), at the top level
         g = out['secondary']['geom_size_dist']
         out['value_geom_size_dist'], out['ms_per_step_geom_size_dist'] = g['value'], g['ms_per_step']
         out['config']['workload_size_dist'] = g['workload'] + f"; {g['steps']} timed steps after {g['warmup']} warm-up steps"
-    elif world > 1 and args.workload == 'c3' and args.precision == 'f32' and args.size_dist is None and not args.no_secondary:
+    elif args.full and world > 1 and args.workload == 'c3' and args.precision == 'f32' and args.size_dist is None and not args.no_secondary:
         del leg        # every rank takes part (barriers); LPT-balanced GEOM sizes, max over ranks
         sdl = size_dist_leg(eng, cfg, world, rank, dev, B, T, args.secondary_steps)
         out['value_geom_size_dist'], out['ms_per_step_geom_size_dist'] = sdl['value_geom_size_dist'], sdl['ms_per_step_geom_size_dist']
         out['config']['workload_size_dist'] = sdl['workload_size_dist']
         out['config']['size_dist_shard_cost_max_over_mean'] = sdl['size_dist_shard_cost_max_over_mean']
-    if rank == 0 and world == 1 and not args.no_api_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_api_e2e:
         out['api_end_to_end'] = api_end_to_end(args, all_sizes, T, dev, wl['traj'])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(cfg, sd, all_sizes, args.cpu_mols, args.cpu_steps, T, evals, ref_batch=args.cpu_ref_batch)
     if rank == 0:
         print(json.dumps(out))

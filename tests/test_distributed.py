@@ -316,7 +316,7 @@ def _bench_parity_worker(rank, world, port, sizes, q):
 
 
 def test_bench_multi_gpu_parity_block_on_two_gloo_ranks(emu_lib_path):
-    """The block `bench.py --gpus N` (N > 1) runs before its timed region and emits as `multi_gpu_parity`, here on two gloo ranks
+    """The block `bench.py --gpus N --full` (N > 1) runs before its timed region and emits as `multi_gpu_parity`, here on two gloo ranks
     over the emulated kernels: sample_distributed in the replicated and the Philox noise mode equals the single-process sample on rank 0 --
     0 differing tokens -- every rank holds the same gathered batch and receives the same verdict."""
     sizes = [4, 6, 3, 5, 2]

@@ -578,8 +578,8 @@ def test_eight_rank_process_group_on_one_gpu_equals_single_process_sample():
     _report('eight_ranks_one_gpu', rep)
 
 
-def _run_bench_ranks(world, backend, extra=()):
-    """`python bench.py --gpus <world> ...` exactly as the driver starts a multi-GPU bench (bench.py launches its ranks itself when no
+def _run_bench_ranks(world, backend, extra=(), full=True):
+    """`python bench.py --gpus <world> ...` as a multi-GPU bench is started, with --full unless full=False (bench.py launches its ranks itself when no
     launcher environment is set); returns the parsed JSON line."""
     import subprocess
     import sys
@@ -590,7 +590,8 @@ def _run_bench_ranks(world, backend, extra=()):
         env['FM_BENCH_BACKEND'] = 'gloo'
     else:
         env.pop('FM_BENCH_BACKEND', None)
-    cmd = [sys.executable, str(root / 'bench.py'), '--gpus', str(world), '--steps', '4', '--warmup', '2', '--mols-per-gpu', '32', '--no-cpu-baseline', '--no-api-e2e', *extra]
+    cmd = [sys.executable, str(root / 'bench.py'), '--gpus', str(world), '--steps', '4', '--warmup', '2', '--mols-per-gpu', '32', *(['--full'] if full else []),
+           '--no-cpu-baseline', '--no-api-e2e', *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500, cwd='/tmp')
     assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -615,7 +616,7 @@ def _check_multi_gpu_line(d, world, backend):
 
 
 def test_bench_multi_gpu_line_carries_parity_block():
-    """the only thing the driver ever runs on the 8-GPU node is `bench.py --gpus N`, so that run proves itself.  Here the whole
+    """`bench.py --gpus N --full` proves itself before it times anything.  Here the whole
     command -- self-launch of 8 ranks, process group, the parity block BEFORE the timed region (sample_distributed in the replicated and the
     Philox noise mode on the ranks vs the single-process sample of the same seed on rank 0: 0 differing tokens, coordinates within 1e-4), the
     timed steps with their four sub-windows, the one all-gather -- runs with 8 ranks sharing this box's one MI355X (FM_BENCH_BACKEND=gloo: RCCL
@@ -636,6 +637,81 @@ def test_bench_multi_gpu_line_over_rccl_between_devices(which):
     p = _check_multi_gpu_line(_run_bench_ranks(world, 'nccl'), world, 'nccl')
     assert p['distinct_pci_devices'] == world and p['rccl_version']
     _report(f'bench_multi_gpu_parity[{world} nccl ranks]', p)
+
+
+def _replay_bench_leg(mols, n_steps, rank=0, n_atoms=47, T=250, device='cuda:0', lib=None):
+    """bench.py's leg rebuilt from its seeds with the engine alone (not through bench.py): flowmol3, synthetic weights (seed 0), `mols` molecules of
+    `n_atoms` atoms, prior positions from a generator seeded 1 + rank, torch noise from one seeded 2 + rank, `n_steps` integration steps from the
+    prior.  Returns the state and the endpoint prediction after the last step as float32 arrays, named as --dump-outputs names them."""
+    from flowmol_amd.engine import Engine, IntegrationRun, StepNoise, make_step_plan
+    cfg = presets.flowmol3()
+    eng = Engine(cfg, weights.synth_state_dict(cfg, 0), device=device, lib=lib)
+    eng.bind(torch.full((mols,), n_atoms, dtype=torch.int64))
+    plan = make_step_plan(T, cfg.stochasticity, cfg.high_confidence_threshold, cfg.cat_temperature)
+    gen, g0 = torch.Generator(device=device), torch.Generator(device=device)
+    gen.manual_seed(2 + rank)
+    g0.manual_seed(1 + rank)
+    x0 = torch.randn(eng.N, 3, device=device, generator=g0)
+    eng.remove_com(x0)
+    state = eng.prior_state(x0)
+    run = IntegrationRun(eng, state, plan, lambda i, last: StepNoise.draw(eng.N, eng.U, cfg.n_atom_types, cfg.n_charges, cfg.n_bond_types, last, device,
+                                                                          generator=gen))
+    run.run(0, n_steps)
+    eng.synchronize()
+    out = {k: state[f'{k}_t'] for k in 'xace'} | {f'pred_{k}': v for k, v in run.last_dst().items()}
+    out = {k: v.to('cpu', torch.float32).numpy() for k, v in out.items()}
+    eng.close()
+    return out
+
+
+def test_bench_plain_line_and_dumped_outputs_repeat(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) prints one compact line with the headline fields, times exactly --steps steps and carries
+    none of the --full figures; --dump-outputs writes the last timed step's state and endpoint prediction -- equal to the same trajectory
+    rebuilt from the seeds and advanced warm-up + timed steps -- and a second run of the same arguments writes the same arrays bit for bit."""
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parent.parent
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        cmd = [sys.executable, str(root / 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--mols-per-gpu', '16', '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tmp_path)
+        assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+        out = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(out) == 1, r.stdout[-2000:]
+        assert len(out[0]) < 4096, len(out[0])
+        lines.append(json.loads(out[0]))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob('*.npy'))})
+    line = lines[0]
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in line, k
+    assert line['steps'] == 5 and line['warmup'] == 2 and sum(line['ms_per_step_windows']['steps_per_window']) == 5
+    assert line['ms_per_step'] > 0 and line['value'] > 0 and line['unit'] == 'molecules/s' and line['higher_is_better'] and line['config']['finite']
+    for k in ('kernels', 'roofline', 'secondary', 'api_end_to_end', 'cpu_baseline'):
+        assert k not in line, k
+    N, U = 16 * 47, 16 * 47 * 46 // 2
+    assert set(dumps[0]) == {'x', 'a', 'c', 'e', 'pred_x', 'pred_a', 'pred_c', 'pred_e'} and line['outputs']['row_sample'] is None
+    assert dumps[0]['x'].shape == (N, 3) and dumps[0]['a'].shape == (N,) and dumps[0]['e'].shape == (U,) and dumps[0]['pred_e'].shape[0] == U
+    for k, v in dumps[0].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert np.array_equal(v, dumps[1][k]), k
+    want = _replay_bench_leg(16, 2 + 5)
+    for k, v in want.items():
+        assert np.array_equal(dumps[0][k], v), k
+
+
+def test_bench_plain_multi_rank_line_and_dumped_batch(tmp_path):
+    """A plain `bench.py --gpus 2` (two gloo ranks sharing the one GPU, no --full): no parity block, both ranks timed, and --dump-outputs
+    (written by rank 0) holds the gathered batch -- rank 0's molecules, then rank 1's, each equal to its rank's trajectory rebuilt from the seeds."""
+    out = tmp_path / 'out'
+    d = _run_bench_ranks(2, 'gloo', extra=('--dump-outputs', str(out)), full=False)
+    assert d['n_gpus'] == 2 and d['multi_gpu_parity'] is None and not d['config']['full'] and 'value_geom_size_dist' not in d
+    assert len(d['per_rank_ms_per_step']) == 2 and d['final_gather_ms'] is not None and d['config']['process_group']['backend'] == 'gloo'
+    got = {p_.stem: np.load(p_) for p_ in sorted(out.glob('*.npy'))}
+    assert set(got) == set('xace') and d['outputs']['row_sample'] is None
+    ranks = [_replay_bench_leg(32, 2 + 4, rank=r) for r in range(2)]
+    for k in 'xace':
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], np.concatenate([r_[k] for r_ in ranks])), k
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs at least two GPUs (RCCL between distinct devices)')

@@ -508,3 +508,30 @@ def test_bench_dry_run_plan_and_cost_sample():
     first = float((c5[:16] * (c5[:16] - 1)).double().mean() / (c5 * (c5 - 1)).double().mean())
     assert abs(ratio - 1) < 0.06 < abs(first - 1)                  # the first 16 molecules of c5 cost 23 % more than the workload's mean
     assert torch.equal(bench._cost_sample(torch.full((64,), 47), 16), torch.full((16,), 47))
+
+
+def test_bench_dump_outputs_float32_within_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes every array as DIR/<name>.npy in float32 (tokens exactly); above the byte budget every array keeps
+    the same seeded, ordered subset of its rows, so two runs of the same arguments write the same files."""
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location('bench_mod3', Path(__file__).resolve().parent.parent / 'bench.py')
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.randn(1000, 3, generator=torch.Generator().manual_seed(0))
+    e = torch.arange(5000, dtype=torch.int32)
+    info = bench.dump_outputs(tmp_path / 'whole', {'x': x, 'e': e})
+    assert info['row_sample'] is None and info['arrays'] == {'x': [1000, 3], 'e': [5000]}
+    got = np.load(tmp_path / 'whole' / 'e.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, np.arange(5000, dtype=np.float32))
+    assert np.array_equal(np.load(tmp_path / 'whole' / 'x.npy'), x.numpy())
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 8000)          # 32,000 bytes of arrays: a quarter of each array's rows
+    runs = []
+    for i in range(2):
+        bench.dump_outputs(tmp_path / f'cut{i}', {'x': x, 'e': e})
+        runs.append({k: np.load(tmp_path / f'cut{i}' / f'{k}.npy') for k in 'xe'})
+    assert sum(v.nbytes for v in runs[0].values()) <= 8000
+    assert runs[0]['x'].shape == (250, 3) and runs[0]['e'].shape == (1250,)
+    assert np.all(np.diff(runs[0]['e']) > 0)                      # rows kept in their order
+    for k in 'xe':
+        assert np.array_equal(runs[0][k], runs[1][k])

@@ -50,6 +50,8 @@ if bench is not None and bench['config'].get('library_digest') in digests:
     (P / f'{ptag}_bench.json').write_text(json.dumps(bench) + '\n')          # the un-profiled bench line of the same call
 else:
     bench = passes['stats']                                                     # sizes / algorithmic bytes: the profiled run's own line (its timings carry the profiler)
+# a plain bench line carries no roofline (bench.py --full does); the profiled passes always run with --full
+roofline = (bench if 'roofline' in bench else passes['stats'])['roofline']
 
 
 def instances(txt, prefix):
@@ -83,16 +85,16 @@ traffic = {
     'kernel': k_main, 'workload': bench['config']['workload'],
     'per_instance': {name: {'dispatches': d, 'FETCH_SIZE_KiB': instances(fetch, k).get(name, (0, {}))[1].get('FETCH_SIZE'), 'WRITE_SIZE_KiB': instances(write, k).get(name, (0, {}))[1].get('WRITE_SIZE'),
                             'mfma_busy_frac': c['SQ_VALU_MFMA_BUSY_CYCLES'] / (c['GRBM_GUI_ACTIVE'] / 8 * 1024)} for name, (d, c) in instances(sq, k).items()},
-    'source': f'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of `python bench.py ... --no-cpu-baseline --no-api-e2e`, '
+    'source': f'rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) of `python bench.py ... --full --no-cpu-baseline --no-api-e2e`, '
               f'per-dispatch averages: profiles/{ptag}_pmc_fetch.txt, profiles/{ptag}_pmc_write_tcc.txt',
     'FETCH_SIZE_KiB': f, 'WRITE_SIZE_KiB': w,
     'correction': 'MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE reports 1/2 of the bytes of wide coalesced reads -> doubled; WRITE_SIZE as reported',
     'hbm_bytes_per_launch': int((2 * f + w) * 1024),
-    'algorithmic_bytes_per_launch': bench['roofline']['algorithmic_bytes_per_launch'],
+    'algorithmic_bytes_per_launch': roofline['algorithmic_bytes_per_launch'],
 }
 (P / f'{ptag}_traffic.json').write_text(json.dumps(traffic, indent=1) + '\n')
 busy, gui = counter(sq, k_main, 'SQ_VALU_MFMA_BUSY_CYCLES'), counter(sq, k_main, 'GRBM_GUI_ACTIVE')
-print(json.dumps({'value': bench['value'], 'ms_per_step': bench['ms_per_step'], 'roofline_frac': bench['roofline']['frac'], 'executed_frac': bench['roofline']['executed_frac'],
+print(json.dumps({'value': bench['value'], 'ms_per_step': bench['ms_per_step'], 'roofline_frac': roofline['frac'], 'executed_frac': roofline['executed_frac'],
                   'mfma_busy_frac': busy / (gui / 8 * 1024), 'hbm_bytes_per_launch': traffic['hbm_bytes_per_launch'],
                   'algorithmic_bytes_per_launch': traffic['algorithmic_bytes_per_launch']}, indent=1))
 if '--current' in sys.argv:
