@@ -25,16 +25,22 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', '-shared', f'--offload-arch={ARCH}', '-ff
 
 
 UNITY = 'fm_all_units.cpp'          # dev-only single-unit build (tools/build_variant.sh); never part of the parallel build
+UNITS = ('fm_engine.cpp', 'fm_tu_msg32.cpp', 'fm_tu_msg16.cpp', 'fm_tu_node.cpp')
+EXPORTS = SRC / 'exports.map'      # linker version script: only the fm_* functions of the C ABI are exported
 
 
 def units():
     """The translation units of the library: compiled separately and in parallel (one hipcc per unit), then linked.  Every unit carries its own
-    gfx950 code object; the engine reaches the other units' kernels through plain host launcher functions (csrc/fm_host.h)."""
-    return sorted(p for p in SRC.glob('*.cpp') if p.name != UNITY)
+    gfx950 code object; the engine reaches the other units' kernels through plain host launcher functions (csrc/fm_host.h).  A .cpp file in csrc/
+    that is not listed here (or a listed one that is missing) is an error, not a silent change of the product."""
+    found = sorted(p.name for p in SRC.glob('*.cpp') if p.name != UNITY)
+    if found != sorted(UNITS):
+        raise RuntimeError(f'flowmol_amd/csrc/*.cpp {found} != build.UNITS {sorted(UNITS)}: list the translation units in flowmol_amd/build.py')
+    return [SRC / u for u in UNITS]
 
 
 def _sources():
-    return sorted(list(SRC.glob('*.cpp')) + list(SRC.glob('*.h')) + [PKG.parent / 'include' / 'flowmol_hip.h'])
+    return sorted(list(SRC.glob('*.cpp')) + list(SRC.glob('*.h')) + [EXPORTS, PKG.parent / 'include' / 'flowmol_hip.h'])
 
 
 def _digest() -> str:
@@ -69,7 +75,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
             return job[1]
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
             objs = list(ex.map(compile_one, jobs))
-        link = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', *[str(o) for o in objs], '-o', str(OUT)]
+        link = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', f'-Wl,--version-script={EXPORTS}', *[str(o) for o in objs], '-o', str(OUT)]
         if verbose:
             print(' '.join(link), flush=True)
         subprocess.run(link, check=True)

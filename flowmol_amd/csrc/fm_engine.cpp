@@ -184,76 +184,92 @@ void fill_mlp(FmMlpArgs& a, const MlpW& w, int rows) {
     a.ldx = ld_for(w.K1p > w.O ? w.K1p : w.O); a.ldh = ld_for(w.H);
     if (a.slabQ0 && a.ldh < 164) a.ldh = 164;      // SC_EDGE with the fused pair slab: the hidden tile later holds the K = 160 rows [rbf | ef]
 }
-template <int MODE>
-void launch_mlp(Launch& L, const char* name, FmMlpArgs a, const MlpW& w, int rows, bool small_tiles = false) {
+// ---------------------------------------------------------------------------------------- instance lists of this unit's families (fm_host.h)
+using MlpFn = decltype(&fm_k_mlp2<FM_MLP_TABLE>);
+using MlpPairFn = decltype(&fm_k_mlp2_pair<FM_MLP_SC_NODE, FM_MLP_SC_EDGE>);
+using Mlp4Fn = decltype(&fm_k_mlp4<FM_MLP4_SC_NODE>);
+using Mlp4PairFn = decltype(&fm_k_mlp4_pair<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>);
+using ProjFn = decltype(&fm_k_node_proj<32>);
+using EdgeUpdFn = decltype(&fm_k_edge_update<32, false>);
+using EdgeUpdSpFn = decltype(&fm_k_edge_update_sp<32>);
+// MLP tiles are opted into the widest input row any model has (K1 = 256 + 16 + 16 + 32); 32-row tiles into the 64-row size
+inline size_t lds_mlp_max(int tm) { return lds_mlp(ld_for(pad8(256 + 16 + 16 + 32)), 260, tm == 16 ? 16 : FM_TM); }
+template <int MODE, int TM = FM_TM> Inst<MlpFn> mlp_inst() { return {{MODE, TM}, fm_k_mlp2<MODE, TM>, lds_mlp_max(TM)}; }
+template <int A, int B, int TM = FM_TM> Inst<MlpPairFn> mlp_pair_inst() { return {{A, B, TM}, fm_k_mlp2_pair<A, B, TM>, lds_mlp_max(TM)}; }
+template <int MODE> Inst<Mlp4Fn> mlp4_inst() { return {{MODE}, fm_k_mlp4<MODE>, (size_t)FM_MLP4_LDS_BYTES}; }
+template <int MODE4, int B> Inst<Mlp4PairFn> mlp4_pair_inst() { return {{MODE4, B}, fm_k_mlp4_pair<MODE4, B>, lds_mlp_max(16)}; }
+template <int V, int TM = FM_TM> Inst<ProjFn> proj_inst() { return {{V, TM}, fm_k_node_proj<V, TM>, lds_proj(V, TM)}; }
+template <int TM, bool NARROW, bool HEAD = false> Inst<EdgeUpdFn> eupd_inst() { return {{TM, NARROW, HEAD}, fm_k_edge_update<TM, NARROW, HEAD>, lds_edge_upd(TM)}; }
+template <int TM, int FMT> Inst<EdgeUpdSpFn> eupd_sp_inst() { return {{TM, FMT}, fm_k_edge_update_sp<TM, FMT>, lds_edge_upd_sp(TM)}; }
+
+const InstList<MlpFn> mlp_instances{"mode, tile_rows", {
+    mlp_inst<FM_MLP_TABLE>(), mlp_inst<FM_MLP_SC_NODE>(), mlp_inst<FM_MLP_NODE_HEAD>(), mlp_inst<FM_MLP_EDGE_HEAD>(), mlp_inst<FM_MLP_SC_EDGE>(),
+    mlp_inst<FM_MLP_SC_EDGE, 32>(), mlp_inst<FM_MLP_EDGE_HEAD, 32>(),
+    mlp_inst<FM_MLP_SC_NODE, 16>(), mlp_inst<FM_MLP_NODE_HEAD, 16>(), mlp_inst<FM_MLP_EDGE_HEAD, 16>(), mlp_inst<FM_MLP_SC_EDGE, 16>(),
+    mlp_inst<FM_MLP_TABLE, 16>()}};       // compiled and opted in, never selected: the token / dense embeddings run 64-row tiles
+const InstList<MlpPairFn> mlp_pair_instances{"mode_a, mode_b, tile_rows", {
+    mlp_pair_inst<FM_MLP_SC_NODE, FM_MLP_SC_EDGE>(), mlp_pair_inst<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD>(),
+    mlp_pair_inst<FM_MLP_SC_NODE, FM_MLP_SC_EDGE, 16>(), mlp_pair_inst<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, 16>()}};
+const InstList<Mlp4Fn> mlp4_instances{"mode", {mlp4_inst<FM_MLP4_SC_NODE>(), mlp4_inst<FM_MLP4_NODE_HEAD>(), mlp4_inst<FM_MLP4_PROJ0>()}};
+const InstList<Mlp4PairFn> mlp4_pair_instances{"mode_a, mode_b", {mlp4_pair_inst<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>(), mlp4_pair_inst<FM_MLP4_NODE_HEAD, FM_MLP_EDGE_HEAD>()}};
+const InstList<ProjFn> node_proj_instances{"V, tile_rows", {proj_inst<32>(), proj_inst<16>(), proj_inst<32, 16>(), proj_inst<16, 16>()}};
+const InstList<EdgeUpdFn> edge_update_instances{"tile_rows, narrow, head", {eupd_inst<32, false>(), eupd_inst<64, false>(), eupd_inst<32, true>(), eupd_inst<32, false, true>()}};
+const InstList<EdgeUpdSpFn> edge_update_sp_instances{"tile_rows, half_planes", {eupd_sp_inst<32, 0>(), eupd_sp_inst<32, 1>()}};
+
+// fm_k_mlp2<mode, tm> over `rows` rows
+void launch_mlp(Launch& L, int mode, const char* name, FmMlpArgs a, const MlpW& w, int rows, int tm = FM_TM) {
     fill_mlp(a, w, rows);
-    if (small_tiles) L(name, fm_k_mlp2<MODE, 16>, dim3((rows + 15) / 16), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh, 16), a);
-    else if (MODE == FM_MLP_SC_EDGE && a.slabQ0)
-        // with the pair slab the kernel is matrix-pipe work followed by 3 KB of row stores per pair: 32-row tiles (38 KB of LDS) put four
-        // independent workgroups on a CU instead of two, so that one's stores overlap the others' GEMMs
-        L(name, fm_k_mlp2<FM_MLP_SC_EDGE, 32>, dim3((rows + 31) / 32), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh, 32), a);
-    else if (MODE == FM_MLP_EDGE_HEAD && (rows + 31) / 32 >= 16 * L.c->n_cus)
-        // large batches: the pair head is a gather of two 512-byte rows per pair in front of 17 k MAC -- latency / HBM work; 32-row tiles (34 KB of LDS)
-        // put four workgroups on a CU instead of two
-        L(name, fm_k_mlp2<FM_MLP_EDGE_HEAD, 32>, dim3((rows + 31) / 32), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh, 32), a);
-    else L(name, fm_k_mlp2<MODE>, dim3((rows + FM_TM - 1) / FM_TM), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh), a);
-}
-template <int MODE_A, int MODE_B>
-void launch_mlp_pair(Launch& L, const char* name, FmMlpArgs a, const MlpW& wa, int rows_a, FmMlpArgs b, const MlpW& wb, int rows_b, bool small_tiles = false) {
-    fill_mlp(a, wa, rows_a); fill_mlp(b, wb, rows_b);
-    const int tm = small_tiles ? 16 : FM_TM;
-    const int ta = (rows_a + tm - 1) / tm, tb = (rows_b + tm - 1) / tm;
-    const size_t lds = std::max(lds_mlp(a.ldx, a.ldh, tm), lds_mlp(b.ldx, b.ldh, tm));
-    if (small_tiles) L(name, fm_k_mlp2_pair<MODE_A, MODE_B, 16>, dim3(ta + tb), dim3(FM_THREADS), lds, a, b, ta);
-    else L(name, fm_k_mlp2_pair<MODE_A, MODE_B>, dim3(ta + tb), dim3(FM_THREADS), lds, a, b, ta);
+    launch_inst(L, mlp_instances, {mode, tm}, name, dim3((rows + tm - 1) / tm), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh, tm), a);
 }
 
-// Pair-slab convolutions of a bound batch (fm_ctx::n_pq of them at most): the hoist is on for batches with at least four rounds of 32-row pair tiles
-// (measured neutral below: the table costs a kernel phase, the saving is matrix-pipe time small batches are not bound by) or when fm_config.pair_slab
-// forces it.  ONE predicate for the workspace layout (the Q tables, U KB each, exist only when it holds) and for every evaluation.
-inline int pq_convs(const fm_ctx* c, long long U) {
-    if (c->n_pq == 0 || U <= 0 || ld_for(c->sc_edge.H) > 164) return 0;      // the slab GEMM reads [rbf | ef] rows at the pitch 164 of a 128-wide hidden tile
-    return (c->pq_forced || c->canonical || (U + 31) / 32 >= 16LL * c->n_cus) ? c->n_pq : 0;      // canonical: a rule that does not read the batch size
+// The node-side MLP (N rows) and the pair-side MLP (U rows) of one stage -- the self-conditioning layer or the output heads -- with the same inputs.
+// While the batch is small they share one launch (two launches less per step where launches are what a step costs).  The shared launch allocates the
+// LARGER tile's LDS (node tiles: 147 KB -> one workgroup per CU) for every workgroup, so once the pair tiles alone fill the chip they run as a launch of
+// their own at two workgroups per CU (profiles/r02n: 1.16 -> 0.94 ms and 0.83 -> 0.68 ms per step at 1024 molecules).  BatchPlan::pair_mlps decides;
+// the node side runs 4-row tiles when mlp4 holds and the stage has quad-row weights (a4.W1q), the pair side 32-row tiles when pair32 holds and its
+// tiles are not small.  pair = nullptr: the node side only.
+void launch_mlp_stage(Launch& L, const BatchPlan& p, bool mlp4, int mode4, int mode_n, int mode_p, const char* both, const char* node, const char* pair,
+                      const FmMlp4Args& a4, FmMlpArgs a, const MlpW& wn, FmMlpArgs e, const MlpW& wp, bool pair32) {
+    const int N = p.N, U = p.U;
+    const bool quad = mlp4 && a4.W1q, small = p.small_node && p.small_pair;
+    const dim3 blk(FM_THREADS);
+    if (pair && p.pair_mlps && quad && small) {
+        fill_mlp(e, wp, U);
+        const int ta = (N + 3) / 4, tb = (U + 15) / 16;
+        launch_inst(L, mlp4_pair_instances, {mode4, mode_p}, both, dim3(ta + tb), blk, std::max((size_t)FM_MLP4_LDS_BYTES, lds_mlp(e.ldx, e.ldh, 16)), a4, e, ta);
+    } else if (pair && p.pair_mlps) {
+        fill_mlp(a, wn, N); fill_mlp(e, wp, U);
+        const int tm = small ? 16 : FM_TM, ta = (N + tm - 1) / tm, tb = (U + tm - 1) / tm;
+        launch_inst(L, mlp_pair_instances, {mode_n, mode_p, tm}, both, dim3(ta + tb), blk, std::max(lds_mlp(a.ldx, a.ldh, tm), lds_mlp(e.ldx, e.ldh, tm)), a, e, ta);
+    } else {
+        if (quad) launch_inst(L, mlp4_instances, {mode4}, node, dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, a4);
+        else launch_mlp(L, mode_n, node, a, wn, N, p.small_node ? 16 : FM_TM);
+        if (pair) launch_mlp(L, mode_p, pair, e, wp, U, p.small_pair ? 16 : pair32 ? 32 : FM_TM);
+    }
 }
 
 // ---------------------------------------------------------------------------------------- one network evaluation
 // node_proj instances (small kernels of this unit): V = 16 | 32 vector channels, 64- or 16-row tiles
 void launch_node_proj(Launch& L, const char* name, int V, bool small, int N, const FmProjArgs& pa) {
-    const dim3 blk(FM_THREADS);
-    if (V == 32) { if (small) L(name, fm_k_node_proj<32, 16>, dim3((N + 15) / 16), blk, lds_proj(32, 16), pa); else L(name, fm_k_node_proj<32>, dim3((N + FM_TM - 1) / FM_TM), blk, lds_proj(32), pa); }
-    else { if (small) L(name, fm_k_node_proj<16, 16>, dim3((N + 15) / 16), blk, lds_proj(16, 16), pa); else L(name, fm_k_node_proj<16>, dim3((N + FM_TM - 1) / FM_TM), blk, lds_proj(16), pa); }
+    const int tm = small ? 16 : FM_TM;
+    launch_inst(L, node_proj_instances, {V, tm}, name, dim3((N + tm - 1) / tm), dim3(FM_THREADS), lds_proj(V, tm), pa);
 }
 
-// One network evaluation of the bound batch.  The kernel instances are selected from the context's run-time parameters (vector channels V, edge / node tile heights
-// TE / TN chosen at fm_batch_bind, destination-feature vectors HX); the heavy families live in translation units of their own (fm_host.h).
+// One network evaluation of the bound batch.  The kernel instances are selected from the model (vector channels V, destination-feature vectors HX), the batch
+// plan (tile heights, fusions, MLP tiles: plan_batch) and this call (prev given, dense inputs, taps); the heavy families live in translation units of their own (fm_host.h).
 int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* prev, int remove_com, const fm_dst* out,
              bool taps_on, const fm_dense_state* dense = nullptr, const float* temb = nullptr) {
     Launch L{c, st};
-    const int V = c->V, TE = c->tm_edge, TN = c->tm_node, HX = c->HX;
+    const BatchPlan& p = c->plan;
+    const int V = c->V, TE = p.tm_edge, TN = p.tm_node, HX = c->HX;
     const FmBatch& b = c->b;
     const int N = b.N, E = b.E, U = b.U;
     const fm_config& cf = c->cfg;
     const int nc1 = c->nc + 1;
-    auto tap = [&](const std::string& n, const void* p, size_t bytes) { if (taps_on) L.tap(n, p, bytes); };
+    auto tap = [&](const std::string& n, const void* src, size_t bytes) { if (taps_on) L.tap(n, src, bytes); };
 
-    // Node- and pair-side MLPs with the same inputs share one launch while the batch is small (two launches less per step where launches
-    // are what a step costs).  The shared launch allocates the LARGER tile's LDS (node tiles: 147 KB -> one workgroup per CU) for every
-    // workgroup, so once the pair tiles alone fill the chip they run as a launch of their own at two workgroups per CU
-    // (profiles/r02n: 1.16 -> 0.94 ms and 0.83 -> 0.68 ms per step at 1024 molecules).  fm_config.pair_mlps = 1 | -1 forces either (0 = this rule).
-    const int mlp_tiles = (N + FM_TM - 1) / FM_TM + (U + FM_TM - 1) / FM_TM;
-    const bool pair_mlps = c->fuse_node && (c->pair_mlps_forced >= 0 ? c->pair_mlps_forced != 0 : mlp_tiles <= c->n_cus);
-    // 16-row MLP tiles while even those do not fill the chip (4 per CU fit in LDS): a tile's two dependent GEMMs are matrix-pipe time on one CU,
-    // so a quarter of the rows is a quarter of the latency (fm_config.mlp_small_tiles = 1 | -1 forces either, 0 = this rule)
-    const bool small_node = c->small_mlp_forced >= 0 ? c->small_mlp_forced != 0 : (N + 15) / 16 <= 4 * c->n_cus;      // decided per side: the node side
-    const bool small_pair = c->small_mlp_forced >= 0 ? c->small_mlp_forced != 0 : (U + 15) / 16 <= 4 * c->n_cus;      // stays small ~25x longer than the pair side
-    const bool small_mlp = small_node && small_pair;                                                                   // shared launches
-    // node-side MLPs on 4-row tiles (fm_k_mlp4) while such tiles fit one per CU: a 16-row tile's two 256-wide layers are ~7 us of matrix time on one CU
-    // whatever the batch, four rows on v_mfma_f32_4x4x1 are the layers' weight stream; fm_config.mlp_small_tiles = 2 forces it (1 / -1: never)
-    const bool mlp4 = c->node_head_W1q && !dense && (c->mlp4_forced >= 0 ? c->mlp4_forced != 0 : (N + 3) / 4 <= c->n_cus);      // the regular tiles' bits (fm_rows4_linear): the choice may follow the batch size in canonical mode
-    const int tiles4 = (N + 3) / 4;
-    // pair-slab convolutions of this evaluation (first pass only; FmMlpArgs::slabQ0): self-conditioned evaluations with at least four rounds of
-    // 32-row pair tiles (measured neutral on small batches: the table costs a kernel phase, the saving is matrix-pipe time they are not bound by)
-    const int n_pq = (HX == 0 && prev && !dense) ? pq_convs(c, U) : 0;
+    const bool mlp4 = p.mlp4 && !dense;
+    const int n_pq = (prev && !dense) ? p.n_pq : 0;      // pair-slab convolutions of this evaluation (first pass only; FmMlpArgs::slabQ0)
     FmMlpArgs ma{};
     ma.na = c->na; ma.nc = c->nc; ma.ne = c->ne;
     ma.rbf_mu_step = c->rbf_mu_step; ma.rbf_inv_sigma = c->rbf_inv_sigma;
@@ -267,11 +283,11 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
           (const float*)dense->a_t, c->na, (const float*)dense->c_t, c->nc, temb, cf.time_embedding_dim);
         FmMlpArgs a{};
         a.in = c->Ps; a.in_ld = kp; a.out = c->s; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
-        launch_mlp<FM_MLP_TABLE>(L, "embed_nodes", a, c->node_embed, N);
+        launch_mlp(L, FM_MLP_TABLE, "embed_nodes", a, c->node_embed, N);
         FmMlpArgs e{};
         e.in = dense->e_t; e.in_ld = c->ne; e.in_w = c->ne; e.out = c->ef; e.out_ld = 128; e.ln_g = c->edge_ln_g; e.ln_b = c->edge_ln_b; e.ln_n = c->F;
         e.p_e0 = b.p_e0; e.p_e1 = b.p_e1;
-        launch_mlp<FM_MLP_TABLE>(L, "embed_pairs", e, c->edge_embed, U);
+        launch_mlp(L, FM_MLP_TABLE, "embed_pairs", e, c->edge_embed, U);
         tap("embed.s", c->s, (size_t)N * 256 * 4);
         tap("embed.ef", c->ef, (size_t)E * 128 * 4);
     } else if (prev) {
@@ -292,17 +308,9 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
         a4.N = N; a4.W1q = c->sc_node_W1q; a4.b1 = c->sc_node.b1; a4.W2q = c->sc_node_W2q; a4.b2 = c->sc_node.b2;
         a4.s_tab = a.s_tab; a4.tok_a = a.tok_a; a4.tok_c = a.tok_c; a4.n_c1 = nc1; a4.prev_a = a.prev_a; a4.prev_c = a.prev_c; a4.prev_x = a.prev_x; a4.x_t = a.x_t;
         a4.na = c->na; a4.nc = c->nc; a4.rbf_mu_step = c->rbf_mu_step; a4.rbf_inv_sigma = c->rbf_inv_sigma; a4.out = c->s;
-        // one row per unordered pair, written to both directed edges; node and pair tiles share one launch
-        if (pair_mlps && mlp4 && small_mlp && c->sc_node_W1q) {
-            fill_mlp(e, c->sc_edge, U);
-            const int tb = (U + 15) / 16;
-            L("sc", fm_k_mlp4_pair<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>, dim3(tiles4 + tb), dim3(FM_THREADS), std::max((size_t)FM_MLP4_LDS_BYTES, lds_mlp(e.ldx, e.ldh, 16)), a4, e, tiles4);
-        } else if (pair_mlps) launch_mlp_pair<FM_MLP_SC_NODE, FM_MLP_SC_EDGE>(L, "sc", a, c->sc_node, N, e, c->sc_edge, U, small_mlp);
-        else {
-            if (mlp4 && c->sc_node_W1q) L("sc_node", fm_k_mlp4<FM_MLP4_SC_NODE>, dim3(tiles4), dim3(FM_THREADS), (size_t)FM_MLP4_LDS_BYTES, a4);
-            else launch_mlp<FM_MLP_SC_NODE>(L, "sc_node", a, c->sc_node, N, small_node);
-            launch_mlp<FM_MLP_SC_EDGE>(L, "sc_edge", e, c->sc_edge, U, small_pair);
-        }
+        // one row per unordered pair, written to both directed edges; with the pair slab the edge kernel is matrix-pipe work followed by 3 KB of row
+        // stores per pair: 32-row tiles (38 KB of LDS) put four independent workgroups on a CU instead of two, so that one's stores overlap the others' GEMMs
+        launch_mlp_stage(L, p, mlp4, FM_MLP4_SC_NODE, FM_MLP_SC_NODE, FM_MLP_SC_EDGE, "sc", "sc_node", "sc_edge", a4, a, c->sc_node, e, c->sc_edge, n_pq > 0);
         tap("sc.s", c->s, (size_t)N * 256 * 4);
         tap("sc.ef", c->ef, (size_t)E * 128 * 4);
     } else {
@@ -316,9 +324,8 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
 
     const dim3 blk(FM_THREADS);
     const dim3 gn((N + FM_TM - 1) / FM_TM), ge((E + FM_TM - 1) / FM_TM);     // 64-row kernels
-    const dim3 gnt((N + TN - 1) / TN), get(c->n_tiles_msg);                 // GVP kernels (edge tiles: molecule-aligned, FmBatch::tile_desc)
-    // fm_config.fuse_node = -1 keeps round 1's launch sequence: node_proj / pos_update / node_proj_asd as kernels of their own (0 / 1 = fused)
-    const bool fuse = c->fuse_node != 0 && HX == 0;      // destination-feature models keep the unfused node sequence (their projection GVP reuses the tile)
+    const dim3 gnt((N + TN - 1) / TN), get(p.n_tiles_msg);                 // GVP kernels (edge tiles: molecule-aligned, FmBatch::tile_desc)
+    const bool fuse = p.fuse_node;
     const int n_pass = cf.n_convs * (cf.n_recycles > 1 ? cf.n_recycles : 1);       // vector_field.py:307: the whole stack again, same weights
     bool head_done = false;      // the edge head ran as the epilogue of the last EdgeUpdate
     for (int it = 0; it < n_pass; ++it) {
@@ -331,9 +338,9 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
             if (it == 0 && mlp4 && cw.Wps4) {
                 FmMlp4Args p4{};
                 p4.N = N; p4.in = c->s; p4.Wps4 = cw.Wps4; p4.Ps = c->Ps; p4.PV = c->PV; p4.pv_w = c->PVW; p4.v_init = c->v; p4.V = V; p4.x_src = x_t; p4.x_dst = c->xw;
-                L("node_proj", fm_k_mlp4<FM_MLP4_PROJ0>, dim3(tiles4), blk, (size_t)FM_MLP4_LDS_BYTES, p4);
+                launch_inst(L, mlp4_instances, {FM_MLP4_PROJ0}, "node_proj", dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, p4);
             }
-            else launch_node_proj(L, "node_proj", V, small_node, N, pa);
+            else launch_node_proj(L, "node_proj", V, p.small_node, N, pa);
         }
         FmMsgArgs m{};
         m.b = b; m.x = c->xw; m.ef = c->ef; m.Ps = c->Ps; m.PV = c->PV; m.w0 = cw.w0;
@@ -350,8 +357,8 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
         const bool dbg = taps_on && it == 0 && c->taps.count("conv0.msg.s") && c->taps.count("conv0.msg.v");
         m.dbg_s = dbg ? (float*)c->taps["conv0.msg.s"] : nullptr; m.dbg_v = dbg ? (float*)c->taps["conv0.msg.v"] : nullptr;
         dim3 gmsg = get;
-        if (c->xcd_swizzle) { m.xcd_chunk = ((int)get.x + 7) / 8; gmsg = dim3(8 * m.xcd_chunk); }
-        const bool pq = HX == 0 && cf.precision == FM_PREC_F32 && it < n_pq;
+        if (p.xcd_swizzle) { m.xcd_chunk = ((int)get.x + 7) / 8; gmsg = dim3(8 * m.xcd_chunk); }
+        const bool pq = it < n_pq;
         if (pq) { m.Q = c->Q[it]; m.g0.Ws = cw.Ws_sh; }          // GVP0's scalar GEMM: K = KU0 (hidden-vector norms); the rest arrives through Q
         fm_launch_edge_message(L, V, TE, HX, cf.precision, pq, gmsg, m);
         const int u = cf.update_after[i];
@@ -372,18 +379,14 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
             }
         }
         nu.s_real = c->S;
-        {   // instance of the node kernel: split precision (fused sequence only), 4 rg nodes per workgroup (small batches), narrow, or the regular one
-            const bool spn = HX == 0 && TN <= 32 && prec_two_plane(cf.precision) && fuse;
-            const int rg = (!spn && HX == 0 && (TN == 16 || TN == 32) && c->node_rg && fuse && c->S == 256 && cf.precision == FM_PREC_F32) ? c->node_rg : 0;
-            if (spn) {
+        {   // instance of the node kernel: split precision, 4 rg nodes per workgroup (one tile per CU), narrow, or the regular one
+            if (p.node_sp) {
                 if (it + 1 < n_pass) nu.Wps_sp = c->conv[(i + 1) % cf.n_convs].Wps_sp;
                 if (u >= 0) nu.Wasd_sp = c->upd[u].Wasd_sp;
-                fm_launch_node_update(L, V, TN, true, cf.precision == FM_PREC_F16X3 ? 3 : 1, 0, gnt, lds_gvp_sp(V, TN) - (size_t)TN * 9 * 4, nu);
-            } else if (rg) {        // one tile per CU
-                fm_launch_node_update(L, V, TN, false, 0, rg, dim3((N + 4 * rg - 1) / (4 * rg)), lds_gvp(V, TN, false), nu);
-            } else {
-                fm_launch_node_update(L, V, TN, c->S != 256, 0, 0, gnt, lds_gvp(V, TN, false), nu);
             }
+            const int rg = p.node_rg;
+            const size_t lds = p.node_sp ? lds_gvp_sp(V, TN) - (size_t)TN * 9 * 4 : lds_gvp(V, TN, false);
+            fm_launch_node_update(L, V, TN, p.node_sp || c->S != 256, p.node_sp, rg, rg ? dim3((N + 4 * rg - 1) / (4 * rg)) : gnt, lds, nu);
         }
         if (tagg) { tap(ci + ".agg.s", c->tap_s, (size_t)N * 256 * 4); tap(ci + ".agg.v", c->tap_v, (size_t)N * 3 * V * 4); }
         tap(ci + ".s", c->s, (size_t)N * 256 * 4);
@@ -396,25 +399,24 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
                 fm_launch_pos_update(L, V, TN, gnt, pp);
                 FmProjArgs pa2{};
                 pa2.N = N; pa2.s = c->s; pa2.v = c->v; pa2.Wasd = uw.Wasd; pa2.Asd = c->Asd;
-                launch_node_proj(L, "node_proj_asd", V, small_node, N, pa2);
+                launch_node_proj(L, "node_proj_asd", V, p.small_node, N, pa2);
             }
             FmEdgeUpdArgs eu{};
             eu.b = b; eu.x = c->xw; eu.Asd = c->Asd; eu.ef = c->ef; eu.W1 = uw.W1; eu.b1 = uw.b1; eu.W2 = uw.W2; eu.b2 = uw.b2;
             eu.ln_g = uw.ln_g; eu.ln_b = uw.ln_b; eu.rbf_mu_step = c->rbf_mu_step; eu.rbf_inv_sigma = c->rbf_inv_sigma;
             eu.f_real = c->F;
             if (prec_two_plane(cf.precision)) {
-                FmEdgeUpdSpW sw{uw.W1_sp, uw.W2_sp};
-                if (cf.precision == FM_PREC_F16X3) L("edge_update", fm_k_edge_update_sp<32, 1>, dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
-                else L("edge_update", fm_k_edge_update_sp<32>, dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
-            } else if (it == n_pass - 1 && c->fuse_head && c->F == 128 && c->tm_eupd == 32 && (long long)c->nmax * (c->nmax - 1) * 512 < 0x7ffffe00LL      // the tile's pair rows are
-                       && !(taps_on && c->taps.count("upd" + std::to_string(i) + ".ef"))) {      // gathered with 31-bit offsets inside ONE molecule's edge rows (n < 2048 atoms); larger: separate head
+                const FmEdgeUpdSpW sw{uw.W1_sp, uw.W2_sp};
+                launch_inst(L, edge_update_sp_instances, {32, cf.precision == FM_PREC_F16X3}, "edge_update", dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
+            } else if (it == n_pass - 1 && p.fuse_head && !(taps_on && c->taps.count("upd" + std::to_string(i) + ".ef"))) {
                 // the evaluation's last EdgeUpdate: its rows feed the edge head and nothing else -- tiles of 16 pairs, the head as the epilogue, no ef store
                 eu.hW1 = c->edge_head.W1; eu.hb1 = c->edge_head.b1; eu.hW2 = c->edge_head.W2; eu.hb2 = c->edge_head.b2; eu.out_e = out->e; eu.ne = c->ne;
-                L("edge_update_head", fm_k_edge_update<32, false, true>, dim3((U + 15) / 16), blk, lds_edge_upd(32), eu);
+                launch_inst(L, edge_update_instances, {32, false, true}, "edge_update_head", dim3((U + 15) / 16), blk, lds_edge_upd(32), eu);
                 head_done = true;
-            } else if (c->F != 128) L("edge_update", fm_k_edge_update<32, true>, dim3((E + 31) / 32), blk, lds_edge_upd(32), eu);
-            else if (c->tm_eupd == 32) L("edge_update", fm_k_edge_update<32, false>, dim3((E + 31) / 32), blk, lds_edge_upd(32), eu);
-            else L("edge_update", fm_k_edge_update<64, false>, dim3((E + 63) / 64), blk, lds_edge_upd(64), eu);
+            } else {
+                const int tm = p.tm_eupd;
+                launch_inst(L, edge_update_instances, {tm, c->F != 128, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
+            }
             const std::string ui = "upd" + std::to_string(i);
             tap(ui + ".x", c->xw, (size_t)N * 3 * 4);
             if (!head_done) tap(ui + ".ef", c->ef, (size_t)E * 128 * 4);
@@ -428,29 +430,15 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
         FmMlp4Args a4{};
         a4.N = N; a4.W1q = c->node_head_W1q; a4.b1 = c->node_head.b1; a4.W2q = c->node_head_W2q; a4.b2 = c->node_head.b2;
         a4.na = c->na; a4.nc = c->nc; a4.in = c->s; a4.out = out->a; a4.out2 = out->c;
-        if (head_done) {          // only the node head is left
-            if (mlp4) L("node_head", fm_k_mlp4<FM_MLP4_NODE_HEAD>, dim3(tiles4), dim3(FM_THREADS), (size_t)FM_MLP4_LDS_BYTES, a4);
-            else launch_mlp<FM_MLP_NODE_HEAD>(L, "node_head", a, c->node_head, N, small_node);
-        } else if (pair_mlps && mlp4 && small_mlp) {
-            fill_mlp(e, c->edge_head, U);
-            const int tb = (U + 15) / 16;
-            L("heads", fm_k_mlp4_pair<FM_MLP4_NODE_HEAD, FM_MLP_EDGE_HEAD>, dim3(tiles4 + tb), dim3(FM_THREADS), std::max((size_t)FM_MLP4_LDS_BYTES, lds_mlp(e.ldx, e.ldh, 16)), a4, e, tiles4);
-        } else if (pair_mlps) launch_mlp_pair<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD>(L, "heads", a, c->node_head, N, e, c->edge_head, U, small_mlp);
-        else {
-            if (mlp4) L("node_head", fm_k_mlp4<FM_MLP4_NODE_HEAD>, dim3(tiles4), dim3(FM_THREADS), (size_t)FM_MLP4_LDS_BYTES, a4);
-            else launch_mlp<FM_MLP_NODE_HEAD>(L, "node_head", a, c->node_head, N, small_node);
-            launch_mlp<FM_MLP_EDGE_HEAD>(L, "edge_head", e, c->edge_head, U, small_pair);
-        }
+        // head_done: only the node head is left
+        launch_mlp_stage(L, p, mlp4, FM_MLP4_NODE_HEAD, FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, "heads", "node_head", head_done ? nullptr : "edge_head", a4, a, c->node_head,
+                         e, c->edge_head, p.edge_head32);
     }
     if (remove_com != 2) {       // 2: the caller's fused CTMC kernel centres the raw positions (c->xw) and writes out->x itself
         L.copy(out->x, c->xw, (size_t)N * 3 * 4);
         if (remove_com) L("remove_com", fm_k_remove_com, dim3(b.B), dim3(64), 0, out->x, (const int*)b.mol_node_off);
     }
     return L.rc;
-}
-
-int evaluate_dispatch(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* prev, int remove_com, const fm_dst* out, bool taps_on) {
-    return evaluate(c, st, state, prev, remove_com, out, taps_on);
 }
 
 // The (atom type, charge) embedding table(s) of `n_tables` consecutive time points (temb: n_tables x time_embedding_dim) into the
@@ -466,7 +454,7 @@ int embed_table(fm_ctx* c, hipStream_t st, const float* temb, int n_tables = 1) 
     a.out = c->s_tab_base; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
     fill_mlp(a, c->node_embed, c->tab_rows);
     a.tab_tiles = (c->tab_rows + FM_TM - 1) / FM_TM; a.tab_stride = a.tab_tiles * FM_TM * 256;
-    L("embed_table", fm_k_mlp2<FM_MLP_TABLE>, dim3(a.tab_tiles * n_tables), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh), a);
+    launch_inst(L, mlp_instances, {FM_MLP_TABLE, FM_TM}, "embed_table", dim3(a.tab_tiles * n_tables), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh), a);
     return L.rc;
 }
 
@@ -479,14 +467,14 @@ int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* 
     c->s_tab = c->s_tab_base + (size_t)table_slot * c->tab_slot_floats;
     const bool sc = c->cfg.self_conditioning != 0;
     if (sc && !prev && bootstrap) {
-        rc = evaluate_dispatch(c, st, state, nullptr, 0, &c->boot, false);
+        rc = evaluate(c, st, state, nullptr, 0, &c->boot, false);
         if (rc) return rc;
         if (c->taps.count("boot.x")) { Launch L{c, st}; L.tap("boot.x", c->boot.x, (size_t)c->b.N * 12); L.tap("boot.a", c->boot.a, (size_t)c->b.N * c->na * 4);
             L.tap("boot.c", c->boot.c, (size_t)c->b.N * c->nc * 4); L.tap("boot.e", c->boot.e, (size_t)c->b.U * c->ne * 4); if (L.rc) return L.rc; }
         prev = &c->boot;
     }
     if (!sc) prev = nullptr;
-    return evaluate_dispatch(c, st, state, prev, remove_com, out, true);
+    return evaluate(c, st, state, prev, remove_com, out, true);
 }
 
 __global__ void fm_k_noop() {}
@@ -539,10 +527,7 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
     if (frame) { f.sink_x = frame->x; f.sink_x1 = frame->x1; }
     if (sc->noise_mode == FM_NOISE_PHILOX) { f.philox = 1; f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->mol_gid; }
     else if (!nz->q_a || !nz->u1_a || !nz->q_e) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
-    // a few molecules: 1024-thread workgroups (one per molecule and modality is all the parallelism there is) -- and batches whose LARGEST molecule has more
-    // than 4096 pairs (n >= 92): its pair rows are one workgroup's serial loop, 35 rounds of 256 threads at 134 atoms (GEOM size distribution: 135 us of a
-    // 67.8-ms step against 39 us at 1024 x 47 atoms); else 256.  Same arithmetic either way (integer counts, per-row decisions).
-    if ((b.B * 4 <= c->n_cus && c->nmax > 23) || c->nmax >= 92) L("ctmc", fm_k_ctmc_fused<1024>, dim3(b.B, 4), dim3(1024), 0, f);
+    if (c->plan.ctmc_threads == 1024) L("ctmc", fm_k_ctmc_fused<1024>, dim3(b.B, 4), dim3(1024), 0, f);
     else L("ctmc", fm_k_ctmc_fused<256>, dim3(b.B, 4), dim3(256), 0, f);
     return L.rc;
 }
@@ -618,7 +603,7 @@ int fm_create(const fm_config* cfg, const fm_tensor_desc* tensors, int n_tensors
         pack_linear(B, c->node_embed.W2, W2, S, S, 256, 256, ident);
         pad_vec(B, c->node_embed.b2, b2, S, 256);
         pad_vec(B, c->node_ln_g, g, S, 256); pad_vec(B, c->node_ln_b, be, S, 256);
-        c->tab_rows = (na + 1) * (nc + 1); c->tab_kp = pad8(kin);
+        c->tab_rows = (na + 1) * (nc + 1);
     }
     const float *ee_W1, *ee_b1, *ee_W2, *ee_b2, *ee_g, *ee_b;
     {
@@ -827,28 +812,10 @@ int fm_create(const fm_config* cfg, const fm_tensor_desc* tensors, int n_tensors
     e = hipMemcpy(c->arena, B.A.h.data(), c->arena_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(c->arena); delete c; return fail(nullptr, FM_ERR_HIP, "fm_create: weight upload failed: %s", hipGetErrorString(e)); }
     for (const Fix& f : B.fix) *f.slot = c->arena + f.off * sizeof(float);
-    // ---- dynamic LDS opt-in (up to 160 KiB per workgroup on gfx950)
-    // launch-tuning overrides (fm_config, ABI 5; 0 = automatic everywhere)
-    c->tm_edge_forced = cfg->tile_edge; c->tm_node_forced = cfg->tile_node;
-    c->tm_eupd = cfg->tile_edge_update == 64 ? 64 : 32;
-    c->xcd_swizzle = cfg->xcd_swizzle >= 0; c->fuse_node = cfg->fuse_node >= 0; c->fuse_head = cfg->fuse_node == 0 || cfg->fuse_node == 1;
-    c->pair_mlps_forced = cfg->pair_mlps == 0 ? -1 : (cfg->pair_mlps > 0);
-    c->small_mlp_forced = cfg->mlp_small_tiles == 0 ? -1 : (cfg->mlp_small_tiles > 0);
-    c->mlp4_forced = cfg->mlp_small_tiles == 0 ? -1 : (cfg->mlp_small_tiles == 2);
-    // pair-slab hoist: the convolutions that run before any molecule update see pair-symmetric edge features and distances
-    c->n_pq = 0;
-    c->pq_forced = cfg->pair_slab > 0;
-    c->canonical = cfg->canonical >= 0;
-    if (cfg->pair_slab >= 0 && HX == 0 && cfg->precision == FM_PREC_F32 && cfg->self_conditioning)
-        for (int i = 0; i < cfg->n_convs && i < 2; ++i) {
-            bool clean = true;
-            for (int j = 0; j < i; ++j) clean &= cfg->update_after[j] < 0;
-            if (!clean) break;
-            c->n_pq = i + 1;
-        }
+    // launch-tuning overrides (fm_config, ABI 5; 0 = automatic everywhere): read per batch by plan_batch
     auto tile_ok = [](int t) { return t == 0 || t == 16 || t == 32 || t == 64; };
     auto rg_tile = [](int t) { return t == 4 || t == 8 || t == 12 || t == 20; };
-    if (!tile_ok(c->tm_edge_forced) || !(tile_ok(c->tm_node_forced) || rg_tile(c->tm_node_forced))) {
+    if (!tile_ok(cfg->tile_edge) || !(tile_ok(cfg->tile_node) || rg_tile(cfg->tile_node))) {
         (void)hipFree(c->arena); delete c;
         return fail(nullptr, FM_ERR_INVALID, "fm_create: fm_config.tile_edge must be 0 (automatic), 16, 32 or 64; tile_node additionally 4, 8, 12 or 20");
     }
@@ -857,21 +824,10 @@ int fm_create(const fm_config* cfg, const fm_tensor_desc* tensors, int n_tensors
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             c->n_cus = prop.multiProcessorCount;
     }
-    fm_set_lds_msg_v32(); fm_set_lds_msg_v16(); fm_set_lds_node();      // the heavy families' instances, in their own translation units
-    set_lds(fm_k_node_proj<32>, lds_proj(32)); set_lds(fm_k_node_proj<16>, lds_proj(16));
-    set_lds(fm_k_node_proj<32, 16>, lds_proj(32, 16)); set_lds(fm_k_node_proj<16, 16>, lds_proj(16, 16));
-    set_lds(fm_k_edge_update_sp<32>, lds_edge_upd_sp(32)); set_lds(fm_k_edge_update_sp<32, 1>, lds_edge_upd_sp(32));
-    set_lds(fm_k_edge_update<32, false>, lds_edge_upd(32)); set_lds(fm_k_edge_update<64, false>, lds_edge_upd(64)); set_lds(fm_k_edge_update<32, true>, lds_edge_upd(32)); set_lds(fm_k_edge_update<32, false, true>, lds_edge_upd(32));
-    const size_t mlp_max = lds_mlp(ld_for(pad8(256 + 16 + 16 + 32)), 260);
-    set_lds(fm_k_mlp2<FM_MLP_TABLE>, mlp_max); set_lds(fm_k_mlp2<FM_MLP_SC_NODE>, mlp_max); set_lds(fm_k_mlp2<FM_MLP_NODE_HEAD>, mlp_max);
-    set_lds(fm_k_mlp2<FM_MLP_EDGE_HEAD>, mlp_max); set_lds(fm_k_mlp2<FM_MLP_SC_EDGE>, mlp_max); set_lds(fm_k_mlp2<FM_MLP_SC_EDGE, 32>, mlp_max); set_lds(fm_k_mlp2<FM_MLP_EDGE_HEAD, 32>, mlp_max);
-    set_lds(fm_k_mlp2_pair<FM_MLP_SC_NODE, FM_MLP_SC_EDGE>, mlp_max); set_lds(fm_k_mlp2_pair<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD>, mlp_max);
-    const size_t mlp_small = lds_mlp(ld_for(pad8(256 + 16 + 16 + 32)), 260, 16);
-    set_lds(fm_k_mlp4<FM_MLP4_SC_NODE>, FM_MLP4_LDS_BYTES); set_lds(fm_k_mlp4<FM_MLP4_NODE_HEAD>, FM_MLP4_LDS_BYTES); set_lds(fm_k_mlp4<FM_MLP4_PROJ0>, FM_MLP4_LDS_BYTES);
-    set_lds(fm_k_mlp4_pair<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>, mlp_small); set_lds(fm_k_mlp4_pair<FM_MLP4_NODE_HEAD, FM_MLP_EDGE_HEAD>, mlp_small);
-    set_lds(fm_k_mlp2<FM_MLP_SC_NODE, 16>, mlp_small); set_lds(fm_k_mlp2<FM_MLP_NODE_HEAD, 16>, mlp_small); set_lds(fm_k_mlp2<FM_MLP_TABLE, 16>, mlp_small);
-    set_lds(fm_k_mlp2<FM_MLP_EDGE_HEAD, 16>, mlp_small); set_lds(fm_k_mlp2<FM_MLP_SC_EDGE, 16>, mlp_small);
-    set_lds(fm_k_mlp2_pair<FM_MLP_SC_NODE, FM_MLP_SC_EDGE, 16>, mlp_small); set_lds(fm_k_mlp2_pair<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, 16>, mlp_small);
+    // ---- dynamic LDS opt-in (up to 160 KiB per workgroup on gfx950): every instance list of the library
+    fm_opt_in_msg_v32(); fm_opt_in_msg_v16(); fm_opt_in_node();      // the heavy families, in their own translation units
+    opt_in(mlp_instances); opt_in(mlp_pair_instances); opt_in(mlp4_instances); opt_in(mlp4_pair_instances);
+    opt_in(node_proj_instances); opt_in(edge_update_instances); opt_in(edge_update_sp_instances);
     *out = c;
     return FM_OK;
 }
@@ -887,15 +843,10 @@ int fm_destroy(fm_ctx* c) {
     return FM_OK;
 }
 
-// ---------------------------------------------------------------------------------------- workspace
-struct WsLayout {
-    int B, N, E, U, P, nmax, tab_rows, tab_kp, tm_edge, tm_node, node_rg, n_tiles_msg;
-    size_t off_mol_tile, off_tile_desc, off_mol_node, off_mol_edge, off_mol_pair, off_node_mol, off_first_edge, off_esrc, off_edst, off_epair, off_pe0, off_pe1,
-        off_pair_mol, off_s, off_v, off_xw, off_ef, off_Ps, off_Asd, off_PV, off_part_s, off_part_v, off_Psd, off_PVd, off_stab, off_bx, off_ba,
-        off_bc, off_be, off_tap_s, off_tap_v, off_gid, off_sa1, off_sc1, off_se1, off_Q0, off_Q1, total;
-};
-
-static int ws_layout(fm_ctx* c, const int32_t* n_atoms, int B, WsLayout& w) {
+// ---------------------------------------------------------------------------------------- batch plan
+// Every launch choice that depends on the batch, made here only, from the model, its fm_config overrides (0 = automatic), the CU count and the molecule
+// sizes: the workspace is laid out for the plan, fm_batch_bind keeps it in the context, evaluate / ctmc_impl read it.
+static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     if (B <= 0) return fail(c, FM_ERR_INVALID, "batch of %d molecules", B);
     long long N = 0, E = 0;
     int nmax = 0;
@@ -907,74 +858,131 @@ static int ws_layout(fm_ctx* c, const int32_t* n_atoms, int B, WsLayout& w) {
     if (E > 0x7fffffffLL / 4) return fail(c, FM_ERR_INVALID, "batch too large for int32 edge indexing (%lld edges)", E);
     // per-node tables (Ps, Asd: 1 KiB rows) are gathered through buffer descriptors with 31-bit byte offsets
     if (N > 0x7fffffffLL / 1024) return fail(c, FM_ERR_INVALID, "batch too large: %lld nodes (limit %lld per bind; split the batch)", N, 0x7fffffffLL / 1024);
-    const int V = c->V;
-    w.B = B; w.N = (int)N; w.E = (int)E; w.U = (int)(E / 2);
-    // tile sizes of this batch.  The edge-message kernel is bound by a CU's matrix pipe, so a launch takes (tiles per CU, rounded up) rounds of one tile time plus the
+    const fm_config& cf = c->cfg;
+    const int n_cus = c->n_cus;
+    const bool f32 = cf.precision == FM_PREC_F32, two_plane = prec_two_plane(cf.precision);
+    p = BatchPlan{};
+    p.B = B; p.N = (int)N; p.E = (int)E; p.U = (int)(E / 2); p.nmax = nmax;
+    const int U = p.U;
+    p.P = nmax > 1 ? (nmax - 2) / FM_CHUNK_E + 2 : 1;      // chunks of FM_CHUNK_E rows a destination's n - 1 in-edges can touch
+    // Edge-message tiles.  The kernel is bound by a CU's matrix pipe, so a launch takes (tiles per CU, rounded up) rounds of one tile time plus the
     // first tile's latency: measured on the MI355X (flowmol3 model, 1 .. 64 molecules x 47 atoms, profiles/r06t_*, r06u_*) 11 + 18 r16 us with 16-row tiles and
     // 13.5 + 31 r32 us with 32-row tiles, r = ceil(tiles / CUs) -- 32-row tiles do 16 rows in 15.5 instead of 18 us, 16-row tiles quantise in half the step.  The
     // cheaper of the two by that model (one molecule: 16 rows; 4, 5, 8, 9 molecules: 16; everything from 14 molecules on: 32).  Both give the same bits (canonical
-    // arithmetic), so the choice is free to follow the batch size.
+    // arithmetic), so the choice is free to follow the batch size.  fm_config.tile_edge (16 | 32 | 64) forces a height.
     {
         long long t16 = 0, t32 = 0;
         for (int i = 0; i < B; ++i) { const long long e = (long long)n_atoms[i] * (n_atoms[i] - 1); t16 += (e + 15) / 16; t32 += (e + 31) / 32; }
-        const long long r16 = (t16 + c->n_cus - 1) / c->n_cus, r32 = (t32 + c->n_cus - 1) / c->n_cus;
-        w.tm_edge = c->tm_edge_forced ? c->tm_edge_forced : (36 * r16 + 22 < 62 * r32 + 27 ? 16 : 32);
+        const long long r16 = (t16 + n_cus - 1) / n_cus, r32 = (t32 + n_cus - 1) / n_cus;
+        p.tm_edge = cf.tile_edge ? cf.tile_edge : (36 * r16 + 22 < 62 * r32 + 27 ? 16 : 32);
     }
-    if ((c->HX || !c->cfg.has_mask) && (w.tm_edge > 32)) w.tm_edge = 32;
+    if ((c->HX || !cf.has_mask) && (p.tm_edge > 32)) p.tm_edge = 32;
+    long long nt = 0;
+    for (int i = 0; i < B; ++i) nt += ((long long)n_atoms[i] * (n_atoms[i] - 1) + p.tm_edge - 1) / p.tm_edge;      // every molecule starts a tile
+    p.n_tiles_msg = (int)nt;
+    p.xcd_swizzle = cf.xcd_swizzle >= 0;      // fm_config.xcd_swizzle = -1 disables
+    // fm_config.fuse_node = -1 keeps round 1's launch sequence: node_proj / pos_update / node_proj_asd as kernels of their own (0 / 1 = fused);
+    // destination-feature models keep the unfused node sequence (their projection GVP reuses the tile)
+    p.fuse_node = cf.fuse_node >= 0 && c->HX == 0;
     // node tiles: 32 rows once the chip is full, 16 while 32-row tiles would leave CUs idle -- and, for full-width f32 models on the fused node
     // sequence, tiles of 4 / 8 / 12 nodes in the 16-row frame or 20 nodes in the 32-row frame (RG instances of fm_k_node_update) whenever such
     // tiles fit ONE per CU: the node kernel is a serial chain per tile whose scalar GEMMs scale with the tile height, so the smallest tile that
-    // still gives every tile a CU of its own is the fastest (beyond one tile per CU the small tiles lose: each streams the full weights)
-    const bool rg_ok = c->S == 256 && c->HX == 0 && c->cfg.precision == FM_PREC_F32 && c->fuse_node;
-    int tn = c->tm_node_forced;
+    // still gives every tile a CU of its own is the fastest (beyond one tile per CU the small tiles lose: each streams the full weights).
+    // fm_config.tile_node (16 | 32 | 64, or 4 / 8 / 12 / 20 nodes) forces a size.
+    const bool rg_ok = c->S == 256 && c->HX == 0 && f32 && cf.fuse_node >= 0;
+    int tn = cf.tile_node;
     if (!tn) {
-        tn = (N + 31) / 32 <= c->n_cus ? 16 : 32;
+        tn = (N + 31) / 32 <= n_cus ? 16 : 32;
         if (rg_ok) {      // the 4 RG-node instances keep the regular tiles' summation order (fm_wave_gemm4): the choice may follow the batch size in canonical mode
             static const int cand[] = {4, 8, 12, 16, 20};
-            for (int r : cand) if ((N + r - 1) / r <= c->n_cus) { tn = r; break; }
+            for (int r : cand) if ((N + r - 1) / r <= n_cus) { tn = r; break; }
         }
     }
-    w.node_rg = 0;
     if (tn == 4 || tn == 8 || tn == 12 || tn == 20) {
-        if (rg_ok) { w.node_rg = tn / 4; tn = tn == 20 ? 32 : 16; }
-        else tn = tn == 20 ? 32 : 16;          // models the instances do not exist for take the frame's regular tile
+        if (rg_ok) p.node_rg = tn / 4;
+        tn = tn == 20 ? 32 : 16;          // models the instances do not exist for take the frame's regular tile
     }
-    w.tm_node = tn;
-    if ((c->HX || !c->cfg.has_mask) && (w.tm_node > 32)) w.tm_node = 32;
-    w.P = nmax > 1 ? (nmax - 2) / FM_CHUNK_E + 2 : 1; w.nmax = nmax;      // chunks of FM_CHUNK_E rows a destination's n - 1 in-edges can touch
-    long long nt = 0;
-    for (int i = 0; i < B; ++i) nt += ((long long)n_atoms[i] * (n_atoms[i] - 1) + w.tm_edge - 1) / w.tm_edge;      // every molecule starts a tile
-    w.n_tiles_msg = (int)nt;
-    w.tab_rows = c->tab_rows; w.tab_kp = c->tab_kp;
+    p.tm_node = tn;
+    if ((c->HX || !cf.has_mask) && (p.tm_node > 32)) p.tm_node = 32;
+    // split-precision node kernel: the fused sequence of the two-plane modes, 16- / 32-row tiles
+    p.node_sp = (p.fuse_node && p.tm_node <= 32 && two_plane) ? (cf.precision == FM_PREC_F16X3 ? 3 : 1) : 0;
+    // EdgeUpdate: fm_config.tile_edge_update = 64 selects 64-row tiles for full-width f32 models (the narrow and split-precision instances are 32 rows)
+    p.tm_eupd = cf.tile_edge_update == 64 && c->F == 128 && !two_plane ? 64 : 32;
+    // the edge head as the epilogue of the last EdgeUpdate (fm_config.fuse_node = 2 | -1: separate): the tile's pair rows are gathered with 31-bit offsets
+    // inside ONE molecule's edge rows (n < 2048 atoms); larger: separate head
+    p.fuse_head = (cf.fuse_node == 0 || cf.fuse_node == 1) && c->F == 128 && p.tm_eupd == 32 && !two_plane
+                  && (long long)nmax * (nmax - 1) * 512 < 0x7ffffe00LL;
+    // Pair-slab convolutions: the convolutions that run before any molecule update see pair-symmetric edge features and distances (self-conditioned f32
+    // models; fm_config.pair_slab = -1: none).  The hoist is on for batches with at least four rounds of 32-row pair tiles (measured neutral below: the
+    // table costs a kernel phase, the saving is matrix-pipe time small batches are not bound by), when fm_config.pair_slab = 1 forces it, or in canonical
+    // mode.  fm_config.canonical >= 0 (default): the ONE launch choice that selects another f32 summation order -- the pair slab (slab + K = 40 chain
+    // instead of one K = 200 chain) -- is FIXED: computed in every evaluation that can use it, so that a molecule's result does not depend on the size or
+    // composition of its batch (see FM_CHUNK_E in fm_kernels.h for the aggregation order).  Tile heights -- incl. the 4 RG-node instances and the 4-row node
+    // MLPs, whose GEMMs keep the regular tiles' order since round 6 (fm_wave_gemm4) -- follow the batch size in both modes.  -1: the pair slab follows the
+    // batch size too (round 5's rule).  The Q tables (U KB each) exist in the workspace only when the batch uses them.
+    if (cf.pair_slab >= 0 && c->HX == 0 && f32 && cf.self_conditioning && U > 0 && ld_for(c->sc_edge.H) <= 164      // the slab GEMM reads [rbf | ef]
+        && (cf.pair_slab > 0 || cf.canonical >= 0 || (U + 31) / 32 >= 16LL * n_cus))                                  // rows at the pitch 164 of a 128-wide hidden tile
+        p.n_pq = cf.n_convs > 1 && cf.update_after[0] < 0 ? 2 : 1;      // the first two convolutions, unless a molecule update runs after the first
+    // Node- and pair-side MLPs with the same inputs share one launch while the batch is small (launch_mlp_stage); fm_config.pair_mlps = 1 | -1 forces either
+    const int mlp_tiles = (p.N + FM_TM - 1) / FM_TM + (U + FM_TM - 1) / FM_TM;
+    p.pair_mlps = cf.fuse_node >= 0 && (cf.pair_mlps ? cf.pair_mlps > 0 : mlp_tiles <= n_cus);
+    // 16-row MLP tiles while even those do not fill the chip (4 per CU fit in LDS): a tile's two dependent GEMMs are matrix-pipe time on one CU,
+    // so a quarter of the rows is a quarter of the latency (fm_config.mlp_small_tiles = 1 | -1 forces either, 0 = this rule)
+    p.small_node = cf.mlp_small_tiles ? cf.mlp_small_tiles > 0 : (p.N + 15) / 16 <= 4 * n_cus;      // decided per side: the node side
+    p.small_pair = cf.mlp_small_tiles ? cf.mlp_small_tiles > 0 : (U + 15) / 16 <= 4 * n_cus;        // stays small ~25x longer than the pair side
+    // node-side MLPs on 4-row tiles (fm_k_mlp4) while such tiles fit one per CU: a 16-row tile's two 256-wide layers are ~7 us of matrix time on one CU
+    // whatever the batch, four rows on v_mfma_f32_4x4x1 are the layers' weight stream; fm_config.mlp_small_tiles = 2 forces it (1 / -1: never).  The regular
+    // tiles' bits (fm_rows4_linear): the choice may follow the batch size in canonical mode
+    p.mlp4 = c->node_head_W1q && (cf.mlp_small_tiles ? cf.mlp_small_tiles == 2 : (p.N + 3) / 4 <= n_cus);
+    // large batches: a separate edge head is a gather of two 512-byte rows per pair in front of 17 k MAC -- latency / HBM work; 32-row tiles (34 KB of LDS)
+    // put four workgroups on a CU instead of two
+    p.edge_head32 = (U + 31) / 32 >= 16 * n_cus;
+    // CTMC: a few molecules: 1024-thread workgroups (one per molecule and modality is all the parallelism there is) -- and batches whose LARGEST molecule has
+    // more than 4096 pairs (n >= 92): its pair rows are one workgroup's serial loop, 35 rounds of 256 threads at 134 atoms (GEOM size distribution: 135 us of a
+    // 67.8-ms step against 39 us at 1024 x 47 atoms); else 256.  Same arithmetic either way (integer counts, per-row decisions).
+    p.ctmc_threads = (B * 4 <= n_cus && nmax > 23) || nmax >= 92 ? 1024 : 256;
+    return FM_OK;
+}
+
+// ---------------------------------------------------------------------------------------- workspace
+struct WsLayout {
+    size_t off_mol_tile, off_tile_desc, off_mol_node, off_mol_edge, off_mol_pair, off_node_mol, off_first_edge, off_esrc, off_edst, off_epair, off_pe0, off_pe1,
+        off_pair_mol, off_s, off_v, off_xw, off_ef, off_Ps, off_Asd, off_PV, off_part_s, off_part_v, off_Psd, off_PVd, off_stab, off_bx, off_ba,
+        off_bc, off_be, off_tap_s, off_tap_v, off_gid, off_sa1, off_sc1, off_se1, off_Q0, off_Q1, total;
+};
+
+static WsLayout ws_layout(const fm_ctx* c, const BatchPlan& p) {
+    const size_t B = p.B, N = p.N, E = p.E, U = p.U, V = c->V;
+    WsLayout w;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    w.off_mol_tile = take((size_t)(B + 1) * 4); w.off_tile_desc = take((size_t)w.n_tiles_msg * 16);
-    w.off_mol_node = take((size_t)(B + 1) * 4); w.off_mol_edge = take((size_t)(B + 1) * 4); w.off_mol_pair = take((size_t)(B + 1) * 4);
-    w.off_node_mol = take((size_t)N * 4); w.off_first_edge = take((size_t)N * 4);
-    w.off_esrc = take((size_t)E * 4); w.off_edst = take((size_t)E * 4); w.off_epair = take((size_t)E * 4);
-    w.off_pe0 = take((size_t)w.U * 4); w.off_pe1 = take((size_t)w.U * 4); w.off_pair_mol = take((size_t)w.U * 4);
-    w.off_s = take((size_t)N * 256 * 4); w.off_v = take((size_t)N * 3 * V * 4); w.off_xw = take((size_t)N * 3 * 4);
-    w.off_ef = take((size_t)E * 128 * 4);
-    w.off_Ps = take((size_t)N * 256 * 4); w.off_Asd = take((size_t)N * 256 * 4); w.off_PV = take((size_t)N * 3 * c->PVW * 4);
-    w.off_Psd = take(c->HX ? (size_t)N * 256 * 4 : 0); w.off_PVd = take(c->HX ? (size_t)N * 3 * c->PVW * 4 : 0);
-    w.off_part_s = take((size_t)N * w.P * 256 * 4); w.off_part_v = take((size_t)N * w.P * 3 * V * 4);
-    w.off_stab = take((size_t)align_up(w.tab_rows, FM_TM) * 256 * 4 * FM_TAB_SLOTS);
-    w.off_bx = take((size_t)N * 3 * 4); w.off_ba = take((size_t)N * c->na * 4); w.off_bc = take((size_t)N * c->nc * 4); w.off_be = take((size_t)w.U * c->ne * 4);
-    w.off_tap_s = take((size_t)N * 256 * 4); w.off_tap_v = take((size_t)N * 3 * V * 4);
-    w.off_gid = take((size_t)B * 4);
-    w.off_sa1 = take((size_t)N * 4); w.off_sc1 = take((size_t)N * 4); w.off_se1 = take((size_t)w.U * 4);
-    const int npq = pq_convs(c, w.U);      // the pair-slab tables are as large as `ef` each: only batches that use them pay for them (8192 x 47 atoms: 13.3 GB without, 31.5 GB with)
-    w.off_Q0 = take(npq > 0 ? (size_t)w.U * 256 * 4 : 0); w.off_Q1 = take(npq > 1 ? (size_t)w.U * 256 * 4 : 0);
+    w.off_mol_tile = take((B + 1) * 4); w.off_tile_desc = take((size_t)p.n_tiles_msg * 16);
+    w.off_mol_node = take((B + 1) * 4); w.off_mol_edge = take((B + 1) * 4); w.off_mol_pair = take((B + 1) * 4);
+    w.off_node_mol = take(N * 4); w.off_first_edge = take(N * 4);
+    w.off_esrc = take(E * 4); w.off_edst = take(E * 4); w.off_epair = take(E * 4);
+    w.off_pe0 = take(U * 4); w.off_pe1 = take(U * 4); w.off_pair_mol = take(U * 4);
+    w.off_s = take(N * 256 * 4); w.off_v = take(N * 3 * V * 4); w.off_xw = take(N * 3 * 4);
+    w.off_ef = take(E * 128 * 4);
+    w.off_Ps = take(N * 256 * 4); w.off_Asd = take(N * 256 * 4); w.off_PV = take(N * 3 * c->PVW * 4);
+    w.off_Psd = take(c->HX ? N * 256 * 4 : 0); w.off_PVd = take(c->HX ? N * 3 * c->PVW * 4 : 0);
+    w.off_part_s = take(N * p.P * 256 * 4); w.off_part_v = take(N * p.P * 3 * V * 4);
+    w.off_stab = take(align_up(c->tab_rows, FM_TM) * 256 * 4 * FM_TAB_SLOTS);
+    w.off_bx = take(N * 3 * 4); w.off_ba = take(N * c->na * 4); w.off_bc = take(N * c->nc * 4); w.off_be = take(U * c->ne * 4);
+    w.off_tap_s = take(N * 256 * 4); w.off_tap_v = take(N * 3 * V * 4);
+    w.off_gid = take(B * 4);
+    w.off_sa1 = take(N * 4); w.off_sc1 = take(N * 4); w.off_se1 = take(U * 4);
+    // the pair-slab tables are as large as `ef` each: only batches that use them pay for them (8192 x 47 atoms: 13.3 GB without, 31.5 GB with)
+    w.off_Q0 = take(p.n_pq > 0 ? U * 256 * 4 : 0); w.off_Q1 = take(p.n_pq > 1 ? U * 256 * 4 : 0);
     w.total = o;
-    return FM_OK;
+    return w;
 }
 
 int fm_workspace_bytes(fm_ctx* c, const int32_t* n_atoms, int B, size_t* bytes) {
     if (!c || !n_atoms || !bytes) return fail(c, FM_ERR_INVALID, "fm_workspace_bytes: null argument");
-    WsLayout w;
-    int rc = ws_layout(c, n_atoms, B, w);
+    BatchPlan p;
+    const int rc = plan_batch(c, n_atoms, B, p);
     if (rc) return rc;
-    *bytes = w.total;
+    *bytes = ws_layout(c, p).total;
     return FM_OK;
 }
 
@@ -1005,9 +1013,10 @@ static int stage_release(fm_ctx* c, hipStream_t st) {
 
 int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* workspace, size_t bytes) {
     if (!c || !n_atoms || !workspace) return fail(c, FM_ERR_INVALID, "fm_batch_bind: null argument");
-    WsLayout w;
-    int rc = ws_layout(c, n_atoms, B, w);
+    BatchPlan p;
+    int rc = plan_batch(c, n_atoms, B, p);
     if (rc) return rc;
+    const WsLayout w = ws_layout(c, p);
     if (bytes < w.total) return fail(c, FM_ERR_INVALID, "fm_batch_bind: workspace of %zu bytes < required %zu", bytes, w.total);
     if ((uintptr_t)workspace % 256) return fail(c, FM_ERR_INVALID, "fm_batch_bind: workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -1019,7 +1028,7 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
     for (int i = 0; i < B; ++i) {
         const int n = n_atoms[i];
         no[i + 1] = no[i] + n; eo[i + 1] = eo[i] + n * (n - 1); po[i + 1] = po[i] + n * (n - 1) / 2; ids[i] = i;
-        to[i + 1] = to[i] + (n * (n - 1) + w.tm_edge - 1) / w.tm_edge;
+        to[i + 1] = to[i] + (n * (n - 1) + p.tm_edge - 1) / p.tm_edge;
     }
     {   // a copy that fails after earlier ones were enqueued must not leave the staging buffer unguarded: the event is recorded either way
         hipError_t e_ = hipMemcpyAsync(base + w.off_mol_node, no, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st);
@@ -1032,8 +1041,8 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
         if (rc) return rc;
     }
     FmBatch& b = c->b;
-    b.B = B; b.N = w.N; b.E = w.E; b.U = w.U; b.P = w.P;
-    b.n_tiles = w.n_tiles_msg; b.tile_rows = w.tm_edge;
+    b.B = B; b.N = p.N; b.E = p.E; b.U = p.U; b.P = p.P;
+    b.n_tiles = p.n_tiles_msg; b.tile_rows = p.tm_edge;
     b.mol_tile_off = (const int*)(base + w.off_mol_tile); b.tile_desc = (int4*)(base + w.off_tile_desc);
     b.mol_node_off = (const int*)(base + w.off_mol_node); b.mol_edge_off = (const int*)(base + w.off_mol_edge); b.mol_pair_off = (const int*)(base + w.off_mol_pair);
     b.node_mol = (int*)(base + w.off_node_mol); b.node_first_edge = (int*)(base + w.off_first_edge);
@@ -1044,18 +1053,17 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
     c->part_s = (float*)(base + w.off_part_s); c->part_v = (float*)(base + w.off_part_v);
     c->Psd = (float*)(base + w.off_Psd); c->PVd = (float*)(base + w.off_PVd);
     c->s_tab = c->s_tab_base = (float*)(base + w.off_stab);
-    c->tab_slot_floats = (size_t)align_up(w.tab_rows, FM_TM) * 256;
+    c->tab_slot_floats = (size_t)align_up(c->tab_rows, FM_TM) * 256;
     c->boot.x = (float*)(base + w.off_bx); c->boot.a = (float*)(base + w.off_ba); c->boot.c = (float*)(base + w.off_bc); c->boot.e = (float*)(base + w.off_be);
     c->tap_s = (float*)(base + w.off_tap_s); c->tap_v = (float*)(base + w.off_tap_v);
     c->mol_gid = (int*)(base + w.off_gid);
     c->sa1 = (int32_t*)(base + w.off_sa1); c->sc1 = (int32_t*)(base + w.off_sc1); c->se1 = (int32_t*)(base + w.off_se1);
     c->Q[0] = (float*)(base + w.off_Q0); c->Q[1] = (float*)(base + w.off_Q1);
-    c->n_tiles_e = (w.E + FM_TM - 1) / FM_TM; c->n_tiles_n = (w.N + FM_TM - 1) / FM_TM; c->n_tiles_u = (w.U + FM_TM - 1) / FM_TM;
     Launch L{c, st};
-    const int work = w.E > w.N ? w.E : w.N;
+    const int work = p.E > p.N ? p.E : p.N;
     L("batch_setup", fm_k_batch_setup, dim3((work + 255) / 256), dim3(256), 0, b);
     if (L.rc) return L.rc;
-    c->bound = true; c->nmax = w.nmax; c->tm_edge = w.tm_edge; c->tm_node = w.tm_node; c->node_rg = w.node_rg; c->n_tiles_msg = w.n_tiles_msg;
+    c->bound = true; c->plan = p;
     return FM_OK;
 }
 
@@ -1223,7 +1231,7 @@ int fm_stability(fm_ctx* c, void* stream, const fm_state* state, const uint32_t*
     FmStabArgs a{};
     a.b = c->b; a.a = state->a_t; a.c = state->c_t; a.e = state->e_t; a.table = table; a.n_types = n_types; a.n_charges = c->nc;
     a.fake_tok = fake_atom_token; a.ne = c->ne; a.arom = explicit_aromaticity; a.out = out;
-    L("stability", fm_k_stability, dim3(c->b.B), dim3(64), (size_t)c->nmax * 8, a);
+    L("stability", fm_k_stability, dim3(c->b.B), dim3(64), (size_t)c->plan.nmax * 8, a);
     return L.rc;
 }
 

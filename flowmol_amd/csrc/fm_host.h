@@ -1,11 +1,13 @@
-// Host-side declarations shared by the translation units of libflowmol_hip.so (round 6: the kernel instances are compiled in several units in parallel --
-// fm_engine.cpp: C ABI, weight packing, workspace, the launch sequence and the small kernels; fm_tu_msg32.cpp / fm_tu_msg16.cpp: the edge-message instances;
-// fm_tu_node.cpp: the node-kernel instances -- instead of one 78-second unit; flowmol_amd/build.py).  The engine reaches the heavy kernels through the
-// plain launcher functions declared at the end of this file, so that no unit instantiates another unit's kernels.
+// Host-side declarations shared by the translation units of libflowmol_hip.so, compiled in parallel (flowmol_amd/build.py) -- fm_engine.cpp: C ABI, weight
+// packing, the batch plan, workspace, the launch sequence and the small kernels; fm_tu_msg32.cpp / fm_tu_msg16.cpp: the edge-message instances; fm_tu_node.cpp:
+// the node-kernel instances.  The engine reaches the heavy kernels through the launcher functions declared at the end of this file (no unit instantiates
+// another unit's kernels).  Every launch choice that depends on the batch is made once, by plan_batch (fm_engine.cpp), into the BatchPlan that the workspace
+// layout and the launches read; every kernel family names its instances once, in an instance list that its launcher and the LDS opt-in both read.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -48,6 +50,28 @@ struct UpdW {
     const void* Wasd4 = nullptr;       // quad-row packed (4-node tiles)
 };
 
+// The launch choices of one bound batch (plan_batch, fm_engine.cpp): made from the model, its fm_config overrides, the CU count and the molecule
+// sizes.  What varies per call (prev given, dense inputs, taps, the last pass) is decided by the evaluation itself.
+struct BatchPlan {
+    int B = 0, N = 0, E = 0, U = 0, nmax = 0;      // molecules, atoms, directed edges, pairs; atoms of the largest molecule
+    int P = 1;                // partial-sum chunks per destination node (FmBatch::P)
+    int tm_edge = 32;         // edge-message tile rows (16 | 32 | 64)
+    int n_tiles_msg = 0;      // molecule-aligned edge-message tiles (FmBatch::n_tiles)
+    bool xcd_swizzle = true;  // edge-message tile -> workgroup mapping: contiguous tile range per XCD
+    int tm_node = 32;         // node-kernel tile rows (16 | 32 | 64)
+    int node_rg = 0;          // node kernel on tiles of 4 * node_rg nodes (RG instances; 1, 2, 3 in the 16-row frame, 5 in the 32-row frame), 0 = off
+    int node_sp = 0;          // split-precision node kernel: 1 (bf16 planes) | 3 (half planes), 0 = f32
+    bool fuse_node = true;    // node_update also runs the next conv's projections, EdgeUpdate's node terms and NodePositionUpdate
+    int tm_eupd = 32;         // EdgeUpdate tile rows (32 | 64)
+    bool fuse_head = true;    // the evaluation's last EdgeUpdate may run the edge output head on its pairs (fm_k_edge_update<32, false, true>)
+    int n_pq = 0;             // pair-slab convolutions of a self-conditioned evaluation (0..2; the workspace holds their Q tables)
+    bool pair_mlps = false;   // node- and pair-side MLPs of a stage share one launch
+    bool small_node = false, small_pair = false;      // 16-row MLP / node_proj tiles on the node / pair side
+    bool mlp4 = false;        // node-side MLPs on 4-row tiles (fm_k_mlp4)
+    bool edge_head32 = false; // a separate edge head runs 32-row tiles
+    int ctmc_threads = 256;   // workgroup size of fm_k_ctmc_fused (256 | 1024)
+};
+
 }  // namespace fmh
 using namespace fmh;
 
@@ -56,29 +80,9 @@ struct fm_ctx {
     std::string err;
     int V = 32, S = 256, F = 128, na = 0, nc = 0, ne = 0;
     int HX = 0, SD = 0, PVW = 48;     // use_dst_feats: destination vectors / scalars per message; width of the hoisted hidden-vector rows
-    // Rows per workgroup tile of the GVP kernels, chosen per bound batch (ws_layout): 32 once the chip is full, 16 while
-    // the 32-row tiling would leave CUs idle (fewer tiles than CUs) - half the work per tile, i.e. lower step latency
-    // for small batches.  fm_config.tile_edge / tile_node (16|32|64) force a size; tile_edge_update (32|64) for EdgeUpdate.
-    int tm_edge = 32, tm_node = 32, tm_eupd = 32;
-    int tm_edge_forced = 0, tm_node_forced = 0;
-    int n_cus = 256;
-    int pair_mlps_forced = -1;      // fm_config.pair_mlps
-    int small_mlp_forced = -1;      // fm_config.mlp_small_tiles
-    int mlp4_forced = -1;           // fm_config.mlp_small_tiles = 2: the node-side MLPs on 4-row tiles (fm_k_mlp4) whatever the batch; 1 / -1: never
+    int n_cus = 256;          // compute units of the device (fm_create); read by plan_batch only
     const void *sc_node_W1q = nullptr, *sc_node_W2q = nullptr, *node_head_W1q = nullptr, *node_head_W2q = nullptr;      // quad-row packed copies for fm_k_mlp4
-    int fuse_head = 1;        // the evaluation's last EdgeUpdate also runs the edge output head on its pairs (fm_k_edge_update<32, false, true>; fm_config.fuse_node = 2 | -1: separate)
-    int fuse_node = 1;        // node_update also runs the next conv's projections, EdgeUpdate's node terms and NodePositionUpdate (fm_config.fuse_node = -1: separate launches)
-    int n_pq = 0;             // leading convolutions (0..2) whose [rbf | ef] slab is computed per unordered pair (self-conditioned models; fm_config.pair_slab = -1: 0)
-    int node_rg = 0;          // this batch runs the node kernel on tiles of 4 * node_rg nodes (RG instances; 1, 2, 3 in the 16-row frame, 5 in the 32-row
-                              // frame): chosen per bound batch, fm_config.tile_node = 4 / 8 / 12 / 20 forces it
-    int pq_forced = 0;        // fm_config.pair_slab = 1: also for batches whose pair tiles do not fill the chip
-    // fm_config.canonical >= 0 (default): the ONE launch choice that selects another f32 summation order -- the pair slab (slab + K = 40 chain instead of one K = 200
-    // chain) -- is FIXED: computed in every evaluation that can use it, so that a molecule's result does not depend on the size or composition of its batch (see
-    // FM_CHUNK_E in fm_kernels.h for the aggregation order).  Tile heights -- incl. the 4 RG-node instances and the 4-row node MLPs, whose GEMMs keep the regular
-    // tiles' order since round 6 (fm_wave_gemm4) -- follow the batch size in both modes.  -1: the pair slab follows the batch size too (round 5's rule).
-    bool canonical = true;
     float* Q[2] = {nullptr, nullptr};      // (U,256) each, in the workspace
-    int xcd_swizzle = 1;      // edge-message tile -> workgroup mapping: contiguous tile range per XCD (fm_config.xcd_swizzle = -1 disables)
     float rbf_mu_step = 0.f, rbf_inv_sigma = 0.f;
     // ---- weights (one device arena)
     char* arena = nullptr; size_t arena_bytes = 0;
@@ -88,13 +92,11 @@ struct fm_ctx {
     const float *ef_tab = nullptr, *T1 = nullptr;          // (ne+1,128) each
     std::vector<ConvW> conv;
     std::vector<UpdW> upd;
-    int tab_rows = 0, tab_kp = 0;
+    int tab_rows = 0;
     // ---- batch binding
     bool bound = false;
-    int nmax = 0;             // atoms of the largest molecule of the bound batch
+    BatchPlan plan{};         // the bound batch's launch choices (plan_batch)
     FmBatch b{};
-    int n_tiles_e = 0, n_tiles_n = 0, n_tiles_u = 0;
-    int n_tiles_msg = 0;      // molecule-aligned edge-message tiles of the bound batch (FmBatch::n_tiles)
     float *s = nullptr, *v = nullptr, *xw = nullptr, *ef = nullptr, *Ps = nullptr, *Asd = nullptr, *PV = nullptr;
     float *part_s = nullptr, *part_v = nullptr, *s_tab = nullptr, *Psd = nullptr, *PVd = nullptr;
     float* s_tab_base = nullptr; size_t tab_slot_floats = 0;      // FM_TAB_SLOTS embedding tables (one per step of a chunk); s_tab = the current step's
@@ -132,8 +134,6 @@ inline int pad8(int k) { return (k + 7) / 8 * 8; }
 inline int pad16(int k) { return (k + 15) / 16 * 16; }
 inline int ld_for(int k) { int ld = (k + 3) / 4 * 4; while (((ld / 4) & 1) == 0) ld += 4; return ld; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-template <class F> void set_lds(F f, size_t bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
 
 inline int pvw_of(int V, int HX) { return (pad8(V + 1 + HX + 4) + 8 + 15) / 16 * 16; }     // FmGvpTile::PVW
 inline size_t lds_gvp_sp(int V, int TM, int npl = 2) {       // split-precision edge message: npl bf16 planes instead of the f32 scalar tile, gates inside Vh
@@ -189,17 +189,44 @@ struct Launch {
     }
 };
 
+// ---------------------------------------------------------------------------------------- kernel instance lists
+// A kernel family that needs more than the default dynamic LDS lists its compiled instances ONCE: {key the launcher selects it by, kernel, LDS bytes
+// it is opted into}.  fm_create walks every list (opt_in); launchers launch only through a list (launch_inst), so an instance that is not listed cannot be
+// launched, and a launch that asks for more LDS than its entry was opted into fails with FM_ERR_INVALID before it reaches HIP.
+using InstKey = std::array<int, 5>;
+template <class Fn> struct Inst { InstKey key; Fn fn; size_t lds; };
+template <class Fn> struct InstList { const char* key_names; std::vector<Inst<Fn>> v; };      // key_names ("V, tile_node, ..."): for error messages
+
+template <class Fn> void opt_in(const InstList<Fn>& list) {
+    for (const Inst<Fn>& i : list.v) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(i.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)i.lds);
+}
+
+template <class Fn, class... Args>
+void launch_inst(Launch& L, const InstList<Fn>& list, const InstKey& key, const char* name, dim3 grid, dim3 block, size_t lds, Args... args) {
+    if (L.rc != FM_OK) return;
+    for (const Inst<Fn>& i : list.v)
+        if (i.key == key) {
+            if (lds > i.lds) L.rc = fail(L.c, FM_ERR_INVALID, "launch of %s asks for %zu bytes of LDS, its instance is opted into %zu", name, lds, i.lds);
+            else L(name, i.fn, grid, block, lds, args...);
+            return;
+        }
+    char k[96]; int n = 0;
+    for (int f = 0, nf = 1 + (int)std::count(list.key_names, list.key_names + strlen(list.key_names), ','); f < nf; ++f)
+        n += snprintf(k + n, sizeof k - n, f ? ", %d" : "%d", key[f]);
+    L.rc = fail(L.c, FM_ERR_INVALID, "no %s instance for (%s) = (%s)", name, list.key_names, k);
+}
+
 // ---------------------------------------------------------------------------------------- launchers of the heavy kernel families (one translation unit each)
-// Every launcher selects the instance from run-time parameters and reports an unsupported combination through L.rc; fm_set_lds_* opt the unit's instances
-// into their dynamic LDS sizes (called once by fm_create).
+// Every launcher selects the instance from run-time parameters and reports an unsupported combination through L.rc; fm_opt_in_* walk the unit's instance
+// lists (called once by fm_create).
 void fm_launch_edge_message(Launch& L, int V, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m);      // fm_tu_msg32.cpp / fm_tu_msg16.cpp
 void fm_launch_edge_message_v32(Launch& L, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m);
 void fm_launch_edge_message_v16(Launch& L, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m);
-void fm_set_lds_msg_v32(); void fm_set_lds_msg_v16();
+void fm_opt_in_msg_v32(); void fm_opt_in_msg_v16();
 // node kernels (fm_tu_node.cpp): narrow = LayerNorm statistics over a real width < 256; sp = 0 | 1 (bf16x3) | 3 (f16x3); rg = 0 | 1 | 2 | 3 | 5 (4 rg nodes per tile)
 void fm_launch_node_update(Launch& L, int V, int TN, bool narrow, int sp, int rg, dim3 grid, size_t lds, const FmNodeUpdArgs& nu);
 void fm_launch_pos_update(Launch& L, int V, int TN, dim3 grid, const FmPosArgs& pp);
 void fm_launch_dst_proj(Launch& L, int V, int TN, int HX, dim3 grid, const FmDstProjArgs& dp);
-void fm_set_lds_node();
+void fm_opt_in_node();
 
 }  // namespace fmh

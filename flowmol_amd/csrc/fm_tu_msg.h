@@ -6,38 +6,28 @@
 
 namespace fmh {
 
+using MsgFn = decltype(&fm_k_edge_message<32, 32, 512, 0, 0>);
+inline size_t lds_msg(int V, int TE, int HX, int SP) { return SP ? lds_gvp_sp(V, TE, SP == 2 ? 3 : 2) : lds_gvp(V, TE, true, HX); }
+template <int V, int TE, int HX, int SP, int PQ = 0> Inst<MsgFn> msg_inst() { return {{TE, HX, SP, PQ}, fm_k_edge_message<V, TE, 512, HX, SP, PQ>, lds_msg(V, TE, HX, SP)}; }
+
 template <int V>
-void fm_launch_edge_message_v(Launch& L, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m) {
+const InstList<MsgFn>& msg_instances() {
     constexpr int HXV = V / 4;
-    const dim3 blk(512);
-#define FM_MSG_TE(TE_)                                                                                                                                          \
-    if (TE == TE_) {                                                                                                                                            \
-        if (HX == 0) {                                                                                                                                          \
-            if (precision == FM_PREC_BF16X3) { L("edge_message", fm_k_edge_message<V, TE_, 512, 0, 1>, grid, blk, lds_gvp_sp(V, TE_), m); return; }              \
-            if (precision == FM_PREC_F16X3) { L("edge_message", fm_k_edge_message<V, TE_, 512, 0, 3>, grid, blk, lds_gvp_sp(V, TE_), m); return; }               \
-            if (precision == FM_PREC_BF16X6) {                                                                                                                  \
-                if constexpr (TE_ <= 32) { L("edge_message", fm_k_edge_message<V, TE_, 512, 0, 2>, grid, blk, lds_gvp_sp(V, TE_, 3), m); return; }               \
-                else { L.rc = fail(L.c, FM_ERR_INVALID, "the three-term split precision runs 16- or 32-row edge tiles (three planes of a 64-row tile exceed the LDS)"); return; } \
-            }                                                                                                                                                   \
-            if (pq) { L("edge_message_pq", fm_k_edge_message<V, TE_, 512, 0, 0, 1>, grid, blk, lds_gvp(V, TE_, true, 0), m); return; }                           \
-            L("edge_message", fm_k_edge_message<V, TE_, 512, 0, 0>, grid, blk, lds_gvp(V, TE_, true, 0), m); return;                                            \
-        }                                                                                                                                                       \
-        if constexpr (TE_ <= 32) { if (HX == HXV && precision == FM_PREC_F32) { L("edge_message", fm_k_edge_message<V, TE_, 512, HXV, 0>, grid, blk, lds_gvp(V, TE_, true, HXV), m); return; } } \
-    }
-    FM_MSG_TE(16) FM_MSG_TE(32) FM_MSG_TE(64)
-#undef FM_MSG_TE
-    if (L.rc == FM_OK) L.rc = fail(L.c, FM_ERR_INVALID, "no edge-message instance for V=%d tile_edge=%d dst_vectors=%d precision=%d", V, TE, HX, precision);
+    static const InstList<MsgFn> list{"tile_edge, dst_vectors, split, pair_slab", {
+        msg_inst<V, 16, 0, 0>(), msg_inst<V, 16, 0, 0, 1>(), msg_inst<V, 16, 0, 1>(), msg_inst<V, 16, 0, 3>(), msg_inst<V, 16, 0, 2>(), msg_inst<V, 16, HXV, 0>(),
+        msg_inst<V, 32, 0, 0>(), msg_inst<V, 32, 0, 0, 1>(), msg_inst<V, 32, 0, 1>(), msg_inst<V, 32, 0, 3>(), msg_inst<V, 32, 0, 2>(), msg_inst<V, 32, HXV, 0>(),
+        msg_inst<V, 64, 0, 0>(), msg_inst<V, 64, 0, 0, 1>(), msg_inst<V, 64, 0, 1>(), msg_inst<V, 64, 0, 3>()}};
+    return list;
 }
 
 template <int V>
-void fm_set_lds_msg_v() {
-    constexpr int HXV = V / 4;
-#define FM_MSG_SET(T_) set_lds(fm_k_edge_message<V, T_, 512, 0, 0>, lds_gvp(V, T_, true)); set_lds(fm_k_edge_message<V, T_, 512, 0, 0, 1>, lds_gvp(V, T_, true)); \
-    set_lds(fm_k_edge_message<V, T_, 512, 0, 1>, lds_gvp_sp(V, T_)); set_lds(fm_k_edge_message<V, T_, 512, 0, 3>, lds_gvp_sp(V, T_));
-    FM_MSG_SET(16) FM_MSG_SET(32) FM_MSG_SET(64)
-#undef FM_MSG_SET
-    set_lds(fm_k_edge_message<V, 16, 512, 0, 2>, lds_gvp_sp(V, 16, 3)); set_lds(fm_k_edge_message<V, 32, 512, 0, 2>, lds_gvp_sp(V, 32, 3));
-    set_lds(fm_k_edge_message<V, 16, 512, HXV, 0>, lds_gvp(V, 16, true, HXV)); set_lds(fm_k_edge_message<V, 32, 512, HXV, 0>, lds_gvp(V, 32, true, HXV));
+void fm_launch_edge_message_v(Launch& L, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m) {
+    const int sp = precision == FM_PREC_BF16X3 ? 1 : precision == FM_PREC_BF16X6 ? 2 : precision == FM_PREC_F16X3 ? 3 : 0;
+    if (sp == 2 && TE > 32 && L.rc == FM_OK) {
+        L.rc = fail(L.c, FM_ERR_INVALID, "the three-term split precision runs 16- or 32-row edge tiles (three planes of a 64-row tile exceed the LDS)");
+        return;
+    }
+    launch_inst(L, msg_instances<V>(), {TE, HX, sp, pq}, pq ? "edge_message_pq" : "edge_message", grid, dim3(512), lds_msg(V, TE, HX, sp), m);
 }
 
 }  // namespace fmh

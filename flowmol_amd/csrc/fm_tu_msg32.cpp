@@ -3,5 +3,5 @@
 
 namespace fmh {
 void fm_launch_edge_message_v32(Launch& L, int TE, int HX, int precision, bool pq, dim3 grid, const FmMsgArgs& m) { fm_launch_edge_message_v<32>(L, TE, HX, precision, pq, grid, m); }
-void fm_set_lds_msg_v32() { fm_set_lds_msg_v<32>(); }
+void fm_opt_in_msg_v32() { opt_in(msg_instances<32>()); }
 }  // namespace fmh

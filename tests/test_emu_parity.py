@@ -652,3 +652,17 @@ def test_canonical_arithmetic_a_molecules_bits_do_not_depend_on_its_batch(emu_li
             for k in 'xace':
                 assert torch.equal(got[k], ref[k]), (tuning, len(batch), idx, k, float((got[k] - ref[k]).abs().max()))
         eng.close()
+
+
+def test_launch_beyond_its_opted_in_lds_is_refused_on_emulation(emu_lib):
+    """Every launch of an LDS-hungry kernel goes through its family's instance list (csrc/fm_host.h), which fm_create also opts in: a launch that needs
+    more dynamic LDS than its instance was opted into fails with FM_ERR_INVALID and a message before it reaches HIP (here: token embeddings wider than
+    the MLP tiles are sized for)."""
+    import dataclasses
+    from flowmol_amd.engine import Engine
+    cfg = dataclasses.replace(presets.qm9(), a_token_dim=200, c_token_dim=200)
+    eng = Engine(cfg, weights.synth_state_dict(cfg, 0), device='cpu', lib=emu_lib)
+    eng.bind(torch.tensor([3, 4]))
+    with pytest.raises(_lib.FlowMolHipError, match=r'fm_forward failed \(-1\): launch of embed_table asks for \d+ bytes of LDS'):
+        eng.forward(eng.prior_state(torch.randn(7, 3)), 0.5)
+    eng.close()
