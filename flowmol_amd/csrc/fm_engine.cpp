@@ -1,6 +1,6 @@
 // Host side of libflowmol_hip.so: the C ABI of include/flowmol_hip.h.
-//  - fm_create    : looks the reference's state-dict tensors up by name, repacks them into MFMA
-//                   B-fragment order (fm_device.h) with the algebraic hoists of SURVEY.md §7, uploads once
+//  - fm_create    : validates the config, decides the model's ModelPlan, looks the reference's state-dict tensors up by name, repacks them
+//                   module by module into MFMA B-fragment order (fm_device.h) with the algebraic hoists of SURVEY.md §7, uploads once
 //  - fm_batch_bind: carves the caller's workspace, builds the destination-sorted edge layout on device
 //  - fm_forward / fm_ctmc_step / fm_integrate: enqueue the kernel sequence on the caller's stream
 // Compiled as HIP for gfx950 (flowmol_amd/build.py).  No host synchronisation on the hot path.
@@ -31,6 +31,7 @@ struct Blob {
         if (err.empty()) err = "missing tensor " + name;
         return nullptr;
     }
+    bool ok() const { return err.empty(); }      // every get() so far found its tensor
 };
 
 // host-side staging arena; device pointers are offsets into the final device arena
@@ -42,11 +43,25 @@ struct Arena {
         h.insert(h.end(), v.begin(), v.end());
         return off;
     }
-    size_t add_raw(const float* p, size_t n) { return add(std::vector<float>(p, p + n)); }
 };
 
+// A logical weight matrix W[k][n] as the kernels' GEMMs see it.  Each is written once (linear() or a lambda) and packed into whichever layouts the
+// ModelPlan asks for: fragment order (pack), quad-row (pack4), split planes (pack_sp).
+using WFn = std::function<float(int, int)>;
+using KMap = std::function<int(int)>;
+
+// a row-major (out, in) Linear weight read through a k-map: W[k][n] = weight[n][kmap(k)], 0 for n >= out or an unmapped k
+WFn linear(const float* W, int out, int in, KMap kmap = [](int k) { return k; }) {
+    return [=](int k, int n) -> float {
+        if (n >= out) return 0.f;
+        const int kk = kmap(k);
+        return (kk >= 0 && kk < in) ? W[(size_t)n * in + kk] : 0.f;
+    };
+}
+KMap below(int n) { return [n](int k) { return k < n ? k : -1; }; }      // the first n input columns of a zero-padded tile
+
 // pack W_logical[k][n] (K x N, K%8==0, N%16==0) into fragment order
-std::vector<float> pack(int K, int N, const std::function<float(int, int)>& w) {
+std::vector<float> pack(int K, int N, const WFn& w) {
     const int K8 = K / 8, NT = N / 16;
     std::vector<float> out((size_t)K8 * NT * 64 * 2);
     for (int ks = 0; ks < K8; ++ks)
@@ -62,7 +77,7 @@ std::vector<float> pack(int K, int N, const std::function<float(int, int)>& w) {
 
 // quad-row packing for fm_wave_gemm4 (4-row tiles on v_mfma_f32_4x4x1_16B_f32): W_logical[k][n] (K x 256, K%4==0); entry (kq, g, lane) = the four
 // weights W[4kq .. 4kq+3][64g + lane] -- one 1-KB buffer_load_dwordx4 per quad step and wave
-std::vector<float> pack4(int K, const std::function<float(int, int)>& w, int G = 4) {      // G column groups of 64: N = 64 G
+std::vector<float> pack4(int K, const WFn& w, int G = 4) {      // G column groups of 64: N = 64 G
     const int KQ = K / 4;
     std::vector<float> out((size_t)KQ * G * 64 * 4);
     for (int kq = 0; kq < KQ; ++kq)
@@ -72,7 +87,7 @@ std::vector<float> pack4(int K, const std::function<float(int, int)>& w, int G =
     return out;
 }
 
-// split-precision packing (fm_device.h "bf16x3"): W_logical[k][n] (K x N, K%32==0, N%16==0) as hi/lo bf16 planes in
+// split-precision packing (fm_device.h "bf16x3"): W_logical[k][n] (K x N, K padded with zeros to a multiple of 32, N%16==0) as hi/lo bf16 planes in
 // v_mfma_f32_16x16x32_bf16 B-fragment order: entry (kb, nt, plane, lane) = 8 bf16 = W[32kb + 8(lane>>4) + q][16nt + (lane&15)], q = 0..7
 inline uint16_t bf16_rne(float f) {
     uint32_t u; memcpy(&u, &f, 4);
@@ -84,14 +99,15 @@ inline float bf16_f32(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; mem
 // 16-bit plane formats of the split modes (fm_device.h): 0 = bf16, 1 = IEEE half (round to nearest even, subnormals kept, clamped to +-65504)
 inline uint16_t f16_rne(float f) { f = std::fmin(std::fmax(f, -65504.f), 65504.f); const _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; }
 inline float f16_f32(uint16_t u) { _Float16 h; memcpy(&h, &u, 2); return (float)h; }
-std::vector<float> pack_sp(int K, int N, const std::function<float(int, int)>& w, int npl = 2, int fmt = 0) {      // npl planes: hi, lo (| hi, mid, lo of the three-term mode)
-    const int KB = K / 32, NT = N / 16;
+std::vector<float> pack_sp(int K, int N, const WFn& w, int npl, int fmt) {      // npl planes: hi, lo (| hi, mid, lo of the three-term mode)
+    const int KB = (K + 31) / 32, NT = N / 16;
     std::vector<uint16_t> out((size_t)KB * NT * npl * 64 * 8);
     for (int kb = 0; kb < KB; ++kb)
         for (int nt = 0; nt < NT; ++nt)
             for (int lane = 0; lane < 64; ++lane)
                 for (int q = 0; q < 8; ++q) {
-                    float r = w(32 * kb + 8 * (lane >> 4) + q, 16 * nt + (lane & 15)) * (fmt == 1 ? FM_F16_WSCALE : 1.0f);      // half planes: weights times 2^6 (fm_device.h)
+                    const int k = 32 * kb + 8 * (lane >> 4) + q;
+                    float r = k < K ? w(k, 16 * nt + (lane & 15)) * (fmt == 1 ? FM_F16_WSCALE : 1.0f) : 0.f;      // half planes: weights times 2^6 (fm_device.h)
                     const size_t e = (((size_t)kb * NT + nt) * npl) * 64 * 8;
                     for (int p_ = 0; p_ < npl; ++p_) {
                         const uint16_t h = fmt == 1 ? f16_rne(r) : bf16_rne(r);
@@ -106,55 +122,37 @@ std::vector<float> pack_sp(int K, int N, const std::function<float(int, int)>& w
 
 struct Fix { const void** slot; size_t off; };
 
+// One fm_create's packing: the weight blob, the host arena and the slots its entries are bound to after the upload, and the model's ModelPlan
 struct Builder {
+    Blob bl; const ModelPlan& m;
     Arena A; std::vector<Fix> fix;
-    int sp_fmt = 0;          // plane format of the split-precision copies this builder packs: 0 = bf16, 1 = IEEE half (weights times 2^6); set once by fm_create
     template <class T> void put(const T*& slot, const std::vector<float>& v) { fix.push_back({(const void**)&slot, A.add(v)}); }
-    void putv(const void*& slot, const std::vector<float>& v) { fix.push_back({&slot, A.add(v)}); }
+    std::vector<float> sp(int K, int N, const WFn& w, int npl) { return pack_sp(K, N, w, npl, m.half_planes ? 1 : 0); }
+    void pad_vec(const float*& slot, const float* v, int n, int np) {
+        std::vector<float> t(np, 0.f);
+        for (int i = 0; i < n; ++i) t[i] = v[i];
+        put(slot, t);
+    }
+    // a two-layer MLP on K1p -> H -> O tiles: biases of n1 / n2 real columns
+    void mlp(MlpW& w, int K1p, int H, int O, const WFn& w1, const float* b1, int n1, const WFn& w2, const float* b2, int n2) {
+        w.K1p = K1p; w.H = H; w.O = O;
+        put(w.W1, pack(K1p, H, w1)); pad_vec(w.b1, b1, n1, H);
+        put(w.W2, pack(H, O, w2)); pad_vec(w.b2, b2, n2, O);
+    }
 };
 
-// Linear weight W (out,in) row-major -> packed with K = Kp (logical input index remapped by kmap), N = Np
-void pack_linear(Builder& B, const float2*& slot, const float* W, int out, int in, int Kp, int Np,
-                 const std::function<int(int)>& kmap) {
-    B.put(slot, pack(Kp, Np, [&](int k, int n) -> float {
-        if (n >= out) return 0.f;
-        const int kk = kmap(k);
-        return (kk >= 0 && kk < in) ? W[(size_t)n * in + kk] : 0.f;
-    }));
-}
-// the same logical matrix as pack_linear, K padded to a multiple of 32, as split-precision planes
-void pack_linear_sp(Builder& B, const void*& slot, const float* W, int out, int in, int Kp, int Np, const std::function<int(int)>& kmap, int npl = 2) {
-    const int K32 = (Kp + 31) / 32 * 32;
-    B.putv(slot, pack_sp(K32, Np, [&](int k, int n) -> float {
-        if (n >= out || k >= Kp) return 0.f;
-        const int kk = kmap(k);
-        return (kk >= 0 && kk < in) ? W[(size_t)n * in + kk] : 0.f;
-    }, npl, B.sp_fmt));
-}
-void pack_linear4(Builder& B, const void*& slot, const float* W, int out, int in, int Kp, const std::function<int(int)>& kmap, int G = 4) {
-    B.putv(slot, pack4(Kp, [&](int k, int n) -> float {
-        if (n >= out) return 0.f;
-        const int kk = kmap(k);
-        return (kk >= 0 && kk < in) ? W[(size_t)n * in + kk] : 0.f;
-    }, G));
-}
-void pad_vec(Builder& B, const float*& slot, const float* v, int n, int np) {
-    std::vector<float> t(np, 0.f);
-    for (int i = 0; i < n; ++i) t[i] = v[i];
-    B.put(slot, t);
-}
-
-// one non-first GVP (vin = V, hidden = V, S real scalar channels in a 256-wide tile): reference gvp.py:30-88 parameter shapes
-bool pack_gvp(Builder& B, Blob& bl, const std::string& key, int V, int S, int vout, FmGvpW& g, int sp = 0 /* bf16 planes of the split-precision copies: 0 | 2 | 3 */, bool rows4 = false) {
+// one non-first GVP (vin = V, hidden = V, S real scalar channels in a 256-wide tile): reference gvp.py:30-88 parameter shapes.  npl: 16-bit planes of
+// the split copies of Ws / Wg (0: none); quad: the quad-row copy of Ws (RG node instances)
+bool pack_gvp(Builder& B, const std::string& key, int V, int S, int vout, FmGvpW& g, int npl, bool quad) {
     const int vop = vout < 16 ? 16 : vout;
-    const float* Wh = bl.get(key + ".Wh", V, V);
-    const float* Wcp = bl.get(key + ".Wcp", V, 8);
-    const float* Wu = bl.get(key + ".Wu", V + 4, vout);
-    const float* Ws = bl.get(key + ".to_feats_out.0.weight", S, V + 4 + S);
-    const float* bs = bl.get(key + ".to_feats_out.0.bias", S);
-    const float* Wg = bl.get(key + ".scalar_to_vector_gates.weight", vout, S);
-    const float* bg = bl.get(key + ".scalar_to_vector_gates.bias", vout);
-    if (!Wh || !Wcp || !Wu || !Ws || !bs || !Wg || !bg) return false;
+    const float* Wh = B.bl.get(key + ".Wh", V, V);
+    const float* Wcp = B.bl.get(key + ".Wcp", V, 8);
+    const float* Wu = B.bl.get(key + ".Wu", V + 4, vout);
+    const float* Ws = B.bl.get(key + ".to_feats_out.0.weight", S, V + 4 + S);
+    const float* bs = B.bl.get(key + ".to_feats_out.0.bias", S);
+    const float* Wg = B.bl.get(key + ".scalar_to_vector_gates.weight", vout, S);
+    const float* bg = B.bl.get(key + ".scalar_to_vector_gates.bias", vout);
+    if (!B.bl.ok()) return false;
     B.put(g.Wv1, pack(V, V + 16, [&](int k, int n) -> float {
         if (n < V) return Wh[k * V + n];
         if (n < V + 8) return Wcp[k * 8 + (n - V)];
@@ -163,18 +161,17 @@ bool pack_gvp(Builder& B, Blob& bl, const std::string& key, int V, int S, int vo
     // tile K order [s (256 columns, S real) | norms of the V hidden channels | cp norm 0, 0, cp norm 1, 0, cp norm 2, 0, cp norm 3, 0]: the four
     // cross-product norms sit on the even k-slots of the last k-superstep (fm_gvp_core: its all-zero second MFMA pass is skipped);
     // reference order [s (S) | sh (V+4)]
-    auto kmap_s = [&](int k) { if (k < 256) return k < S ? k : -1;
-                               const int o = k - 256; if (o < V) return S + o;
-                               return ((o - V) & 1) ? -1 : S + V + (o - V) / 2; };
-    pack_linear(B, g.Ws, Ws, S, V + 4 + S, 256 + V + 8, 256, kmap_s);
-    if (rows4) pack_linear4(B, g.Ws4, Ws, S, V + 4 + S, 256 + V + 8, kmap_s);      // node-side GVPs: second copy for the 4-node tiles (fm_wave_gemm4)
-    pad_vec(B, g.bs, bs, S, 256);
-    pack_linear(B, g.Wg, Wg, vout, S, 256, vop, [&](int k) { return k < S ? k : -1; });
-    pad_vec(B, g.bg, bg, vout, vop);
-    if (sp) {
-        pack_linear_sp(B, g.Ws_sp, Ws, S, V + 4 + S, 256 + V + 8, 256, kmap_s, sp);
-        pack_linear_sp(B, g.Wg_sp, Wg, vout, S, 256, vop, [&](int k) { return k < S ? k : -1; }, sp);
-    }
+    const int KS = 256 + V + 8;
+    const WFn ws = linear(Ws, S, V + 4 + S, [=](int k) { if (k < 256) return k < S ? k : -1;
+                                                          const int o = k - 256; if (o < V) return S + o;
+                                                          return ((o - V) & 1) ? -1 : S + V + (o - V) / 2; });
+    const WFn wg = linear(Wg, vout, S, below(S));
+    B.put(g.Ws, pack(KS, 256, ws));
+    if (quad) B.put(g.Ws4, pack4(KS, ws));
+    B.pad_vec(g.bs, bs, S, 256);
+    B.put(g.Wg, pack(256, vop, wg));
+    B.pad_vec(g.bg, bg, vout, vop);
+    if (npl) { B.put(g.Ws_sp, B.sp(KS, 256, ws, npl)); B.put(g.Wg_sp, B.sp(256, vop, wg, npl)); }
     return true;
 }
 
@@ -226,14 +223,14 @@ void launch_mlp(Launch& L, int mode, const char* name, FmMlpArgs a, const MlpW& 
 // While the batch is small they share one launch (two launches less per step where launches are what a step costs).  The shared launch allocates the
 // LARGER tile's LDS (node tiles: 147 KB -> one workgroup per CU) for every workgroup, so once the pair tiles alone fill the chip they run as a launch of
 // their own at two workgroups per CU (profiles/r02n: 1.16 -> 0.94 ms and 0.83 -> 0.68 ms per step at 1024 molecules).  BatchPlan::pair_mlps decides;
-// the node side runs 4-row tiles when mlp4 holds and the stage has quad-row weights (a4.W1q), the pair side 32-row tiles when pair32 holds and its
+// the node side runs 4-row tiles when mlp4 holds (BatchPlan::mlp4, never for dense inputs), the pair side 32-row tiles when pair32 holds and its
 // tiles are not small.  pair = nullptr: the node side only.
 void launch_mlp_stage(Launch& L, const BatchPlan& p, bool mlp4, int mode4, int mode_n, int mode_p, const char* both, const char* node, const char* pair,
                       const FmMlp4Args& a4, FmMlpArgs a, const MlpW& wn, FmMlpArgs e, const MlpW& wp, bool pair32) {
     const int N = p.N, U = p.U;
-    const bool quad = mlp4 && a4.W1q, small = p.small_node && p.small_pair;
+    const bool small = p.small_node && p.small_pair;
     const dim3 blk(FM_THREADS);
-    if (pair && p.pair_mlps && quad && small) {
+    if (pair && p.pair_mlps && mlp4 && small) {
         fill_mlp(e, wp, U);
         const int ta = (N + 3) / 4, tb = (U + 15) / 16;
         launch_inst(L, mlp4_pair_instances, {mode4, mode_p}, both, dim3(ta + tb), blk, std::max((size_t)FM_MLP4_LDS_BYTES, lds_mlp(e.ldx, e.ldh, 16)), a4, e, ta);
@@ -242,7 +239,7 @@ void launch_mlp_stage(Launch& L, const BatchPlan& p, bool mlp4, int mode4, int m
         const int tm = small ? 16 : FM_TM, ta = (N + tm - 1) / tm, tb = (U + tm - 1) / tm;
         launch_inst(L, mlp_pair_instances, {mode_n, mode_p, tm}, both, dim3(ta + tb), blk, std::max(lds_mlp(a.ldx, a.ldh, tm), lds_mlp(e.ldx, e.ldh, tm)), a, e, ta);
     } else {
-        if (quad) launch_inst(L, mlp4_instances, {mode4}, node, dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, a4);
+        if (mlp4) launch_inst(L, mlp4_instances, {mode4}, node, dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, a4);
         else launch_mlp(L, mode_n, node, a, wn, N, p.small_node ? 16 : FM_TM);
         if (pair) launch_mlp(L, mode_p, pair, e, wp, U, p.small_pair ? 16 : pair32 ? 32 : FM_TM);
     }
@@ -335,7 +332,7 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
             FmProjArgs pa{};
             pa.N = N; pa.s = c->s; pa.v = c->v; pa.Wps = cw.Wps; pa.Ps = c->Ps; pa.Wpv = cw.Wpv; pa.PV = c->PV; pa.pv_w = c->PVW;
             if (it == 0) { pa.v_init = c->v; pa.x_src = x_t; pa.x_dst = c->xw; }     // v = 0, working copy of x (no memset / memcpy nodes)
-            if (it == 0 && mlp4 && cw.Wps4) {
+            if (it == 0 && mlp4) {
                 FmMlp4Args p4{};
                 p4.N = N; p4.in = c->s; p4.Wps4 = cw.Wps4; p4.Ps = c->Ps; p4.PV = c->PV; p4.pv_w = c->PVW; p4.v_init = c->v; p4.V = V; p4.x_src = x_t; p4.x_dst = c->xw;
                 launch_inst(L, mlp4_instances, {FM_MLP4_PROJ0}, "node_proj", dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, p4);
@@ -386,7 +383,7 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
             }
             const int rg = p.node_rg;
             const size_t lds = p.node_sp ? lds_gvp_sp(V, TN) - (size_t)TN * 9 * 4 : lds_gvp(V, TN, false);
-            fm_launch_node_update(L, V, TN, p.node_sp || c->S != 256, p.node_sp, rg, rg ? dim3((N + 4 * rg - 1) / (4 * rg)) : gnt, lds, nu);
+            fm_launch_node_update(L, V, TN, p.node_sp || c->mp.narrow_s, p.node_sp, rg, rg ? dim3((N + 4 * rg - 1) / (4 * rg)) : gnt, lds, nu);
         }
         if (tagg) { tap(ci + ".agg.s", c->tap_s, (size_t)N * 256 * 4); tap(ci + ".agg.v", c->tap_v, (size_t)N * 3 * V * 4); }
         tap(ci + ".s", c->s, (size_t)N * 256 * 4);
@@ -405,9 +402,9 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
             eu.b = b; eu.x = c->xw; eu.Asd = c->Asd; eu.ef = c->ef; eu.W1 = uw.W1; eu.b1 = uw.b1; eu.W2 = uw.W2; eu.b2 = uw.b2;
             eu.ln_g = uw.ln_g; eu.ln_b = uw.ln_b; eu.rbf_mu_step = c->rbf_mu_step; eu.rbf_inv_sigma = c->rbf_inv_sigma;
             eu.f_real = c->F;
-            if (prec_two_plane(cf.precision)) {
+            if (c->mp.node_sp) {
                 const FmEdgeUpdSpW sw{uw.W1_sp, uw.W2_sp};
-                launch_inst(L, edge_update_sp_instances, {32, cf.precision == FM_PREC_F16X3}, "edge_update", dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
+                launch_inst(L, edge_update_sp_instances, {32, c->mp.half_planes}, "edge_update", dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
             } else if (it == n_pass - 1 && p.fuse_head && !(taps_on && c->taps.count("upd" + std::to_string(i) + ".ef"))) {
                 // the evaluation's last EdgeUpdate: its rows feed the edge head and nothing else -- tiles of 16 pairs, the head as the epilogue, no ef store
                 eu.hW1 = c->edge_head.W1; eu.hb1 = c->edge_head.b1; eu.hW2 = c->edge_head.W2; eu.hb2 = c->edge_head.b2; eu.out_e = out->e; eu.ne = c->ne;
@@ -415,7 +412,7 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
                 head_done = true;
             } else {
                 const int tm = p.tm_eupd;
-                launch_inst(L, edge_update_instances, {tm, c->F != 128, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
+                launch_inst(L, edge_update_instances, {tm, c->mp.narrow_f, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
             }
             const std::string ui = "upd" + std::to_string(i);
             tap(ui + ".x", c->xw, (size_t)N * 3 * 4);
@@ -532,6 +529,266 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
     return L.rc;
 }
 
+// ---------------------------------------------------------------------------------------- fm_create: validate, plan, pack by module, upload
+int validate(const fm_config& cf) {
+    if (cf.abi_version != FM_ABI_VERSION) return fail(nullptr, FM_ERR_INVALID, "fm_create: ABI version %d != %d", cf.abi_version, FM_ABI_VERSION);
+    // The kernels' tiles are 256 scalar / 128 edge-feature columns wide.  Narrower models (configs/dev.yml: 64 / 64) run on the
+    // same tiles: weights, biases and LayerNorm affine parameters are zero-padded when they are repacked, so the extra columns
+    // stay exactly 0 through every Linear / SiLU / residual, and LayerNorm takes its statistics over the REAL width only.
+    auto pow2 = [](int v) { return v >= 8 && (v & (v - 1)) == 0; };      // LayerNorm mean = sum * (1/n): exact division only for a power-of-two width
+    if (!pow2(cf.n_hidden_scalars) || cf.n_hidden_scalars > 256 || !pow2(cf.n_hidden_edge_feats) || cf.n_hidden_edge_feats > 128 || cf.rbf_dim != 32)
+        return fail(nullptr, FM_ERR_INVALID, "fm_create: need power-of-two widths 8 <= n_hidden_scalars <= 256, 8 <= n_hidden_edge_feats <= 128, and rbf_dim == 32");
+    if (cf.n_vec_channels != 16 && cf.n_vec_channels != 32) return fail(nullptr, FM_ERR_INVALID, "fm_create: n_vec_channels must be 16 or 32");
+    if (cf.n_convs < 1 || cf.n_convs > FM_MAX_CONVS) return fail(nullptr, FM_ERR_INVALID, "fm_create: bad n_convs");
+    if (cf.n_recycles < 0 || cf.n_recycles > 64) return fail(nullptr, FM_ERR_INVALID, "fm_create: n_recycles must be 0..64");
+    if (cf.msg_z == 0.f) return fail(nullptr, FM_ERR_INVALID, "fm_create: msg_z must be > 0 (divisor) or < 0 (mean over the in-edges)");
+    if (cf.n_atom_types + 1 > 16 || cf.n_charges + 1 > 16 || cf.n_bond_types + 1 > 16 || cf.n_atom_types + cf.n_charges > 32)
+        return fail(nullptr, FM_ERR_INVALID, "fm_create: categorical widths exceed kernel limits");
+    const bool tok = cf.a_token_dim > 0;
+    if (!cf.has_mask && (tok || cf.self_conditioning)) return fail(nullptr, FM_ERR_INVALID, "fm_create: endpoint-parameterised models (has_mask = 0) take raw categorical vectors (token dims 0) and no self-conditioning");
+    if ((cf.c_token_dim > 0) != tok || (cf.e_token_dim > 0) != tok) return fail(nullptr, FM_ERR_INVALID, "fm_create: token dims must be all zero or all non-zero");
+    const int HX = cf.v_dst_feats, SD = cf.s_dst_feats;
+    if ((HX > 0) != (SD > 0) || HX < 0 || HX > 8 || SD > 256 || (HX > 0 && HX != cf.n_vec_channels / 4))
+        return fail(nullptr, FM_ERR_INVALID, "fm_create: destination-feature widths must be both 0 or v = n_vec_channels/4 (<= 8), s <= 256");
+    if (cf.precision != FM_PREC_F32 && cf.precision != FM_PREC_BF16X3 && cf.precision != FM_PREC_BF16X6 && cf.precision != FM_PREC_F16X3) return fail(nullptr, FM_ERR_INVALID, "fm_create: unknown precision %d", cf.precision);
+    if (cf.precision != FM_PREC_F32 && HX > 0) return fail(nullptr, FM_ERR_INVALID, "fm_create: split precision is built for models without destination features");
+    // launch-tuning overrides (fm_config, ABI 5; 0 = automatic everywhere): read per batch by plan_batch
+    auto tile_ok = [](int t) { return t == 0 || t == 16 || t == 32 || t == 64; };
+    auto rg_tile = [](int t) { return t == 4 || t == 8 || t == 12 || t == 20; };
+    if (!tile_ok(cf.tile_edge) || !(tile_ok(cf.tile_node) || rg_tile(cf.tile_node)))
+        return fail(nullptr, FM_ERR_INVALID, "fm_create: fm_config.tile_edge must be 0 (automatic), 16, 32 or 64; tile_node additionally 4, 8, 12 or 20");
+    return FM_OK;
+}
+
+ModelPlan model_plan(const fm_config& cf) {
+    ModelPlan m;
+    const bool f32 = cf.precision == FM_PREC_F32, two_plane = prec_two_plane(cf.precision), dst = cf.v_dst_feats > 0;
+    m.narrow_s = cf.n_hidden_scalars != 256;
+    m.narrow_f = cf.n_hidden_edge_feats != 128;
+    m.quad_mlp = !m.narrow_s && !dst && !two_plane;
+    m.quad_node = m.quad_mlp && f32 && cf.fuse_node >= 0;      // the fused node sequence (BatchPlan::fuse_node) of full-width f32 models
+    m.msg_planes = two_plane ? 2 : cf.precision == FM_PREC_BF16X6 ? 3 : 0;
+    m.node_sp = two_plane ? (cf.precision == FM_PREC_F16X3 ? 3 : 1) : 0;
+    m.half_planes = cf.precision == FM_PREC_F16X3;
+    // the pair slab: self-conditioned f32 models without destination features; the slab GEMM reads [rbf | ef] rows at the pitch 164 of a 128-wide hidden tile
+    if (cf.pair_slab >= 0 && !dst && f32 && cf.self_conditioning && ld_for(128) <= 164)
+        m.slab_convs = cf.n_convs > 1 && cf.update_after[0] < 0 ? 2 : 1;      // the first two convolutions, unless a molecule update runs after the first
+    return m;
+}
+
+// token tables, the scalar embedding, and the edge embedding: its table of the ne+1 distinct inputs (ef_tab), and for endpoint models the dense MLP
+bool pack_embeddings(fm_ctx* c, Builder& B, std::vector<float>& ef_tab) {
+    const fm_config& cf = c->cfg;
+    const int S = c->S, F = c->F, na = c->na, nc = c->nc, ne = c->ne;
+    const bool tok = cf.a_token_dim > 0;
+    const int mk = cf.has_mask ? 1 : 0;       // CTMC models: one mask category per categorical input
+    const int ta = tok ? cf.a_token_dim : na + mk, tc = tok ? cf.c_token_dim : nc + mk, te = tok ? cf.e_token_dim : ne + mk;
+    const float* emb_e = nullptr;
+    if (tok) {
+        const float* ea = B.bl.get("token_embeddings.a.weight", na + 1, ta);
+        const float* ec = B.bl.get("token_embeddings.c.weight", nc + 1, tc);
+        emb_e = B.bl.get("token_embeddings.e.weight", ne + 1, te);
+        if (!B.bl.ok()) return false;
+        B.put(c->emb_a, std::vector<float>(ea, ea + (na + 1) * ta));
+        B.put(c->emb_c, std::vector<float>(ec, ec + (nc + 1) * tc));
+    }
+    const int kin = ta + tc + cf.time_embedding_dim;
+    const float* W1 = B.bl.get("scalar_embedding.0.weight", S, kin); const float* b1 = B.bl.get("scalar_embedding.0.bias", S);
+    const float* W2 = B.bl.get("scalar_embedding.2.weight", S, S); const float* b2 = B.bl.get("scalar_embedding.2.bias", S);
+    const float* g = B.bl.get("scalar_embedding.4.weight", S); const float* be = B.bl.get("scalar_embedding.4.bias", S);
+    if (!B.bl.ok()) return false;
+    B.mlp(c->node_embed, pad8(kin), 256, 256, linear(W1, S, kin), b1, S, linear(W2, S, S), b2, S);
+    B.pad_vec(c->node_ln_g, g, S, 256); B.pad_vec(c->node_ln_b, be, S, 256);
+    c->tab_rows = (na + 1) * (nc + 1);
+    const float* eW1 = B.bl.get("edge_embedding.0.weight", F, te); const float* eb1 = B.bl.get("edge_embedding.0.bias", F);
+    const float* eW2 = B.bl.get("edge_embedding.2.weight", F, F); const float* eb2 = B.bl.get("edge_embedding.2.bias", F);
+    const float* eg = B.bl.get("edge_embedding.4.weight", F); const float* ebe = B.bl.get("edge_embedding.4.bias", F);
+    if (!B.bl.ok()) return false;
+    // edge-embedding table (ne+1 rows): the edge embedding has only ne+1 distinct inputs (SURVEY.md §8a a6);
+    // evaluated once here on the host in f32 (same op order as a row of the device MLP is not required: 1e-7 class)
+    ef_tab.assign((size_t)(ne + 1) * 128, 0.f);
+    for (int t = 0; t <= ne; ++t) {
+        std::vector<float> in(te, 0.f), h1(F), h2(F);
+        if (tok) for (int k = 0; k < te; ++k) in[k] = emb_e[t * te + k]; else if (t < te) in[t] = 1.f;
+        for (int n = 0; n < F; ++n) { float acc = eb1[n]; for (int k = 0; k < te; ++k) acc = fmaf(eW1[n * te + k], in[k], acc); h1[n] = acc / (1.0f + expf(-acc)); }
+        for (int n = 0; n < F; ++n) { float acc = eb2[n]; for (int k = 0; k < F; ++k) acc = fmaf(eW2[n * F + k], h1[k], acc); h2[n] = acc / (1.0f + expf(-acc)); }
+        double mean = 0; for (float x : h2) mean += x; mean /= F;
+        double var = 0; for (float x : h2) var += (x - mean) * (x - mean); var /= F;
+        const float rstd = (float)(1.0 / std::sqrt(var + 1e-5));
+        for (int n = 0; n < F; ++n) ef_tab[(size_t)t * 128 + n] = (h2[n] - (float)mean) * rstd * eg[n] + ebe[n];      // columns F..127 stay 0
+    }
+    B.put(c->ef_tab, ef_tab);
+    if (!mk) {      // dense edge embedding of endpoint models: the same MLP as a device kernel over the pair rows
+        B.mlp(c->edge_embed, pad8(te), 128, 128, linear(eW1, F, te), eb1, F, linear(eW2, F, F), eb2, F);
+        B.pad_vec(c->edge_ln_g, eg, F, 128); B.pad_vec(c->edge_ln_b, ebe, F, 128);
+    }
+    return true;
+}
+
+// the self-conditioning layer's node and edge MLPs, and T1: its edge MLP's first layer applied to the edge-embedding table
+bool pack_self_conditioning(fm_ctx* c, Builder& B, const std::vector<float>& ef_tab) {
+    if (!c->cfg.self_conditioning) return true;
+    const int S = c->S, F = c->F, na = c->na, nc = c->nc, ne = c->ne;
+    const std::string p = "self_conditioning_residual_layer.";
+    const int kin = S + na + nc + 32, kinp = 256 + na + nc + 32;       // reference / tile input widths: [s | p_a | p_c | rbf]
+    const float* W1 = B.bl.get(p + "node_residual_mlp.0.weight", S, kin); const float* b1 = B.bl.get(p + "node_residual_mlp.0.bias", S);
+    const float* W2 = B.bl.get(p + "node_residual_mlp.2.weight", S, S); const float* b2 = B.bl.get(p + "node_residual_mlp.2.bias", S);
+    const int kie = F + ne + 32;
+    const float* E1 = B.bl.get(p + "edge_residual_mlp.0.weight", F, kie); const float* eb1 = B.bl.get(p + "edge_residual_mlp.0.bias", F);
+    const float* E2 = B.bl.get(p + "edge_residual_mlp.2.weight", F, F); const float* eb2 = B.bl.get(p + "edge_residual_mlp.2.bias", F);
+    if (!B.bl.ok()) return false;
+    const WFn w1 = linear(W1, S, kin, [=](int k) { return k < 256 ? (k < S ? k : -1) : S + (k - 256); }), w2 = linear(W2, S, S);
+    B.mlp(c->sc_node, pad8(kinp), 256, 256, w1, b1, S, w2, b2, S);
+    if (c->mp.quad_mlp) { B.put(c->sc_node_W1q, pack4(320, w1)); B.put(c->sc_node_W2q, pack4(256, w2)); }      // 4-row node tiles (fm_k_mlp4): K padded to 320
+    B.mlp(c->sc_edge, pad8(ne + 32), 128, 128, linear(E1, F, kie, [=](int k) { return k < ne + 32 ? F + k : -1; }), eb1, F, linear(E2, F, F), eb2, F);
+    std::vector<float> T1((size_t)(ne + 1) * 128, 0.f);
+    for (int t = 0; t <= ne; ++t)
+        for (int n = 0; n < F; ++n) {
+            float acc = eb1[n];
+            for (int k = 0; k < F; ++k) acc = fmaf(E1[(size_t)n * kie + k], ef_tab[(size_t)t * 128 + k], acc);
+            T1[(size_t)t * 128 + n] = acc;
+        }
+    B.put(c->T1, T1);
+    return true;
+}
+
+bool pack_convolution(fm_ctx* c, Builder& B, int i) {
+    const ModelPlan& m = c->mp;
+    const int V = c->V, S = c->S, F = c->F, HX = c->HX, SD = c->SD, PVW = c->PVW;
+    const int H0 = V + 1 + HX, KU0 = pad8(H0 + 4);
+    ConvW& cw = c->conv[i];
+    const std::string p = "conv_layers." + std::to_string(i) + ".", k0 = p + "edge_message.0";
+    const int kin0 = S + 32 + F + SD + H0 + 4;
+    const float* Wh = B.bl.get(k0 + ".Wh", H0, H0);        // input vectors [x_diff | v_src (V) | v_dst_msg (HX)], hidden = max(in, out) = H0
+    const float* Wcp = B.bl.get(k0 + ".Wcp", H0, 8);
+    const float* Wu = B.bl.get(k0 + ".Wu", H0 + 4, V);
+    const float* Ws = B.bl.get(k0 + ".to_feats_out.0.weight", S, kin0);
+    const float* bs = B.bl.get(k0 + ".to_feats_out.0.bias", S);
+    const float* Wg = B.bl.get(k0 + ".scalar_to_vector_gates.weight", V, S);
+    const float* bg = B.bl.get(k0 + ".scalar_to_vector_gates.bias", V);
+    if (!B.bl.ok()) return false;
+    // hoisted per-node parts (input vector 0 is the displacement; 1.. are v_src); the quad-row projection: conv 0's in fm_k_mlp4, every conv's in the RG
+    // node instances (the previous node_update projects the next conv)
+    const WFn ps = linear(Ws, S, kin0, below(S));
+    B.put(cw.Wps, pack(256, 256, ps));
+    if (m.quad_node || (i == 0 && m.quad_mlp)) B.put(cw.Wps4, pack4(256, ps));
+    if (m.node_sp) B.put(cw.Wps_sp, B.sp(256, 256, ps, 2));
+    // hidden-vector row layout (FmGvpTile): [hidden (H0) | cp (4, filled by the kernel) | 0 .. KU0) | Vcp sources (8) | 0 .. PVW)
+    auto hrow = [&](int vin_row, int n) -> float {
+        if (n < H0) return Wh[(size_t)vin_row * H0 + n];
+        if (n >= KU0 && n < KU0 + 8) return Wcp[(size_t)vin_row * 8 + (n - KU0)];
+        return 0.f; };
+    B.put(cw.Wpv, pack(V, PVW, [&](int k, int n) -> float { return hrow(1 + k, n); }));
+    std::vector<float> w0(PVW);
+    for (int n = 0; n < PVW; ++n) w0[n] = hrow(0, n);
+    B.put(cw.w0, w0);
+    FmGvpW& g0 = cw.msg[0];
+    g0.Wv1 = nullptr;
+    B.put(g0.Wu, pack(KU0, V, [&](int k, int n) -> float { return k < H0 + 4 ? Wu[k * V + n] : 0.f; }));
+    // K order of the first scalar linear: [rbf(32) | ef(128 columns, F real) | sh(V+5) | 0]; reference column order
+    // [s_src(S) | rbf(32) | ef(F) | sh(V+5)] (gvp.py:532-539,118)
+    const WFn g0s = linear(Ws, S, kin0, [=](int k) {
+        if (k < 32) return S + k;
+        if (k < 160) return k - 32 < F ? S + 32 + (k - 32) : -1;
+        return k < 160 + H0 + 4 ? S + 32 + F + SD + (k - 160) : -1; });
+    const WFn g0g = linear(Wg, V, S, below(S));
+    B.put(g0.Ws, pack(160 + KU0, 256, g0s));
+    if (i < m.slab_convs) {      // pair-slab convolutions: the [rbf | ef] rows (K = 160) and the hidden-vector norm rows (K = KU0) apart
+        B.put(cw.Ws_slab, pack(160, 256, g0s));
+        B.put(cw.Ws_sh, pack(KU0, 256, [&](int k, int n) { return g0s(160 + k, n); }));
+    }
+    B.pad_vec(g0.bs, bs, S, 256);
+    B.put(g0.Wg, pack(256, V, g0g));
+    B.pad_vec(g0.bg, bg, V, V);
+    if (m.msg_planes) { B.put(g0.Ws_sp, B.sp(160 + KU0, 256, g0s, m.msg_planes)); B.put(g0.Wg_sp, B.sp(256, V, g0g, m.msg_planes)); }
+    if (HX > 0) {
+        // destination-node terms of the first edge GVP, hoisted per node: vectors through [Wh | Wcp] rows V+1.., scalars through Ws columns S+32+F..
+        B.put(cw.Wpvd, pack(8, PVW, [&](int k, int n) -> float { return k < HX ? hrow(V + 1 + k, n) : 0.f; }));
+        B.put(cw.Wsd, pack(256, 256, linear(Ws, S, kin0, [=](int k) { return k < SD ? S + 32 + F + k : -1; })));
+        // the projection GVP itself (gvp.py:304-311): V -> HX vectors, S -> SD scalars, hidden V, no cross-product features
+        const std::string kp = p + "dst_feat_msg_projection";
+        const float* pWh = B.bl.get(kp + ".Wh", V, V); const float* pWu = B.bl.get(kp + ".Wu", V, HX);
+        const float* pWs = B.bl.get(kp + ".to_feats_out.0.weight", SD, V + S); const float* pbs = B.bl.get(kp + ".to_feats_out.0.bias", SD);
+        const float* pWg = B.bl.get(kp + ".scalar_to_vector_gates.weight", HX, SD); const float* pbg = B.bl.get(kp + ".scalar_to_vector_gates.bias", HX);
+        if (!B.bl.ok()) return false;
+        FmGvpW& dp = cw.dproj;
+        B.put(dp.Wv1, pack(V, V + 16, [&](int k, int n) -> float { return n < V ? pWh[k * V + n] : 0.f; }));         // Wcp = 0
+        B.put(dp.Wu, pack(V + 8, 16, [&](int k, int n) -> float { return (k < V && n < HX) ? pWu[k * HX + n] : 0.f; }));
+        B.put(dp.Ws, pack(256 + V + 8, 256, linear(pWs, SD, V + S, [=](int k) { return k < 256 ? (k < S ? k : -1) : (k < 256 + V ? S + (k - 256) : -1); })));
+        B.pad_vec(dp.bs, pbs, SD, 256);
+        B.put(dp.Wg, pack(256, 16, linear(pWg, HX, SD, below(SD))));
+        B.pad_vec(dp.bg, pbg, HX, 16);
+    }
+    for (int g = 1; g < 3; ++g) if (!pack_gvp(B, p + "edge_message." + std::to_string(g), V, S, V, cw.msg[g], m.msg_planes, false)) return false;
+    for (int g = 0; g < 3; ++g) if (!pack_gvp(B, p + "node_update." + std::to_string(g), V, S, V, cw.upd[g], m.node_sp ? 2 : 0, m.quad_node)) return false;
+    const float* l1g = B.bl.get(p + "message_layer_norm.feat_norm.weight", S); const float* l1b = B.bl.get(p + "message_layer_norm.feat_norm.bias", S);
+    const float* l2g = B.bl.get(p + "update_layer_norm.feat_norm.weight", S); const float* l2b = B.bl.get(p + "update_layer_norm.feat_norm.bias", S);
+    if (!B.bl.ok()) return false;
+    B.pad_vec(cw.ln1_g, l1g, S, 256); B.pad_vec(cw.ln1_b, l1b, S, 256);
+    B.pad_vec(cw.ln2_g, l2g, S, 256); B.pad_vec(cw.ln2_b, l2b, S, 256);
+    return true;
+}
+
+// one molecule updater: NodePositionUpdate's three GVPs and EdgeUpdate
+bool pack_updater(fm_ctx* c, Builder& B, int u) {
+    const ModelPlan& m = c->mp;
+    const int V = c->V, S = c->S, F = c->F;
+    UpdW& uw = c->upd[u];
+    const std::string p = "node_position_updaters." + std::to_string(u) + ".gvps.";
+    for (int g = 0; g < 3; ++g) if (!pack_gvp(B, p + std::to_string(g), V, S, g < 2 ? V : 1, uw.pos[g], m.node_sp ? 2 : 0, m.quad_node)) return false;
+    const std::string q = "edge_updaters." + std::to_string(u) + ".";
+    const bool with_d = !c->cfg.edge_update_no_distance;
+    const int kin = 2 * S + F + (with_d ? 32 : 0);
+    const float* W1 = B.bl.get(q + "edge_update_fn.0.weight", F, kin); const float* b1 = B.bl.get(q + "edge_update_fn.0.bias", F);
+    const float* W2 = B.bl.get(q + "edge_update_fn.2.weight", F, F); const float* b2 = B.bl.get(q + "edge_update_fn.2.bias", F);
+    const float* g = B.bl.get(q + "edge_norm.weight", F); const float* be = B.bl.get(q + "edge_norm.bias", F);
+    if (!B.bl.ok()) return false;
+    // input order [s_src(S) | s_dst(S) | ef(F) | d(32)] (vector_field.py:870-877); tile: Asd = [W1_src s | W1_dst s] (2 x 128 columns)
+    const WFn asd = [=](int k, int n) -> float {
+        const int o = n < 128 ? n : n - 128;
+        if (k >= S || o >= F) return 0.f;
+        return W1[(size_t)o * kin + (n < 128 ? 0 : S) + k]; };
+    // without update_edge_w_distance the rbf(d) block of the tile meets zero weights
+    const WFn w1 = linear(W1, F, kin, [=](int k) { return k < 128 ? (k < F ? 2 * S + k : -1) : (with_d ? 2 * S + F + (k - 128) : -1); });
+    const WFn w2 = linear(W2, F, F);
+    B.put(uw.Wasd, pack(256, 256, asd));
+    if (m.quad_node) B.put(uw.Wasd4, pack4(256, asd));
+    B.put(uw.W1, pack(160, 128, w1));
+    B.pad_vec(uw.b1, b1, F, 128);
+    B.put(uw.W2, pack(128, 128, w2));
+    B.pad_vec(uw.b2, b2, F, 128);
+    if (m.node_sp) { B.put(uw.Wasd_sp, B.sp(256, 256, asd, 2)); B.put(uw.W1_sp, B.sp(160, 128, w1, 2)); B.put(uw.W2_sp, B.sp(128, 128, w2, 2)); }
+    B.pad_vec(uw.ln_g, g, F, 128); B.pad_vec(uw.ln_b, be, F, 128);
+    return true;
+}
+
+bool pack_heads(fm_ctx* c, Builder& B) {
+    const int S = c->S, F = c->F, na = c->na, nc = c->nc, ne = c->ne;
+    const float* W1 = B.bl.get("node_output_head.0.weight", S, S); const float* b1 = B.bl.get("node_output_head.0.bias", S);
+    const float* W2 = B.bl.get("node_output_head.2.weight", na + nc, S); const float* b2 = B.bl.get("node_output_head.2.bias", na + nc);
+    const float* E1 = B.bl.get("to_edge_logits.0.weight", F, F); const float* eb1 = B.bl.get("to_edge_logits.0.bias", F);
+    const float* E2 = B.bl.get("to_edge_logits.2.weight", ne, F); const float* eb2 = B.bl.get("to_edge_logits.2.bias", ne);
+    if (!B.bl.ok()) return false;
+    const WFn w1 = linear(W1, S, S), w2 = linear(W2, na + nc, S);
+    B.mlp(c->node_head, 256, 256, pad16(na + nc), w1, b1, S, w2, b2, na + nc);
+    if (c->mp.quad_mlp) {
+        B.put(c->node_head_W1q, pack4(256, w1));
+        B.put(c->node_head_W2q, pack4(256, w2, 1));      // N = 64 (na + nc <= 32 real columns): one column group, K over all eight waves
+    }
+    B.mlp(c->edge_head, 128, 128, 16, linear(E1, F, F), eb1, F, linear(E2, ne, F), eb2, ne);
+    return true;
+}
+
+int upload(fm_ctx* c, const Builder& B) {
+    c->arena_bytes = B.A.h.size() * sizeof(float);
+    hipError_t e = hipMalloc((void**)&c->arena, c->arena_bytes);
+    if (e != hipSuccess) { c->arena = nullptr; return fail(nullptr, FM_ERR_NOMEM, "fm_create: hipMalloc(%zu) failed: %s", c->arena_bytes, hipGetErrorString(e)); }
+    e = hipMemcpy(c->arena, B.A.h.data(), c->arena_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(nullptr, FM_ERR_HIP, "fm_create: weight upload failed: %s", hipGetErrorString(e));
+    for (const Fix& f : B.fix) *f.slot = c->arena + f.off * sizeof(float);
+    return FM_OK;
+}
+
 }  // namespace
 
 // ================================================================================================= C ABI
@@ -542,283 +799,26 @@ int fm_abi_version(void) { return FM_ABI_VERSION; }
 
 int fm_create(const fm_config* cfg, const fm_tensor_desc* tensors, int n_tensors, const float* host_blob, fm_ctx** out) {
     if (!cfg || !tensors || !host_blob || !out) return fail(nullptr, FM_ERR_INVALID, "fm_create: null argument");
-    if (cfg->abi_version != FM_ABI_VERSION) return fail(nullptr, FM_ERR_INVALID, "fm_create: ABI version %d != %d", cfg->abi_version, FM_ABI_VERSION);
-    // The kernels' tiles are 256 scalar / 128 edge-feature columns wide.  Narrower models (configs/dev.yml: 64 / 64) run on the
-    // same tiles: weights, biases and LayerNorm affine parameters are zero-padded when they are repacked, so the extra columns
-    // stay exactly 0 through every Linear / SiLU / residual, and LayerNorm takes its statistics over the REAL width only.
-    auto pow2 = [](int v) { return v >= 8 && (v & (v - 1)) == 0; };      // LayerNorm mean = sum * (1/n): exact division only for a power-of-two width
-    if (!pow2(cfg->n_hidden_scalars) || cfg->n_hidden_scalars > 256 || !pow2(cfg->n_hidden_edge_feats) || cfg->n_hidden_edge_feats > 128 || cfg->rbf_dim != 32)
-        return fail(nullptr, FM_ERR_INVALID, "fm_create: need power-of-two widths 8 <= n_hidden_scalars <= 256, 8 <= n_hidden_edge_feats <= 128, and rbf_dim == 32");
-    if (cfg->n_vec_channels != 16 && cfg->n_vec_channels != 32) return fail(nullptr, FM_ERR_INVALID, "fm_create: n_vec_channels must be 16 or 32");
-    if (cfg->n_convs < 1 || cfg->n_convs > FM_MAX_CONVS) return fail(nullptr, FM_ERR_INVALID, "fm_create: bad n_convs");
-    if (cfg->n_recycles < 0 || cfg->n_recycles > 64) return fail(nullptr, FM_ERR_INVALID, "fm_create: n_recycles must be 0..64");
-    if (cfg->msg_z == 0.f) return fail(nullptr, FM_ERR_INVALID, "fm_create: msg_z must be > 0 (divisor) or < 0 (mean over the in-edges)");
-    if (cfg->n_atom_types + 1 > 16 || cfg->n_charges + 1 > 16 || cfg->n_bond_types + 1 > 16 || cfg->n_atom_types + cfg->n_charges > 32)
-        return fail(nullptr, FM_ERR_INVALID, "fm_create: categorical widths exceed kernel limits");
-    const bool tok = cfg->a_token_dim > 0;
-    const int mk = cfg->has_mask ? 1 : 0;       // CTMC models: one mask category per categorical input
-    if (!mk && (tok || cfg->self_conditioning)) return fail(nullptr, FM_ERR_INVALID, "fm_create: endpoint-parameterised models (has_mask = 0) take raw categorical vectors (token dims 0) and no self-conditioning");
-    if ((cfg->c_token_dim > 0) != tok || (cfg->e_token_dim > 0) != tok) return fail(nullptr, FM_ERR_INVALID, "fm_create: token dims must be all zero or all non-zero");
-
-    fm_ctx* c = new fm_ctx();
+    int rc = validate(*cfg);
+    if (rc) return rc;
+    std::unique_ptr<fm_ctx, int (*)(fm_ctx*)> c(new fm_ctx(), fm_destroy);      // an error below releases the context as fm_destroy does
     c->cfg = *cfg;
-    const int V = c->V = cfg->n_vec_channels;
-    const int S = c->S = cfg->n_hidden_scalars, F = c->F = cfg->n_hidden_edge_feats;
-    const int HX = c->HX = cfg->v_dst_feats, SD = c->SD = cfg->s_dst_feats;
-    if ((HX > 0) != (SD > 0) || HX < 0 || HX > 8 || SD > 256 || (HX > 0 && HX != V / 4))
-        { delete c; return fail(nullptr, FM_ERR_INVALID, "fm_create: destination-feature widths must be both 0 or v = n_vec_channels/4 (<= 8), s <= 256"); }
-    const int H0 = V + 1 + HX, KU0 = pad8(H0 + 4), PVW = c->PVW = pvw_of(V, HX);
-    if (cfg->precision != FM_PREC_F32 && cfg->precision != FM_PREC_BF16X3 && cfg->precision != FM_PREC_BF16X6 && cfg->precision != FM_PREC_F16X3) { delete c; return fail(nullptr, FM_ERR_INVALID, "fm_create: unknown precision %d", cfg->precision); }
-    if (cfg->precision != FM_PREC_F32 && HX > 0) { delete c; return fail(nullptr, FM_ERR_INVALID, "fm_create: split precision is built for models without destination features"); }
-    const int na = c->na = cfg->n_atom_types, nc = c->nc = cfg->n_charges, ne = c->ne = cfg->n_bond_types;
+    c->V = cfg->n_vec_channels; c->S = cfg->n_hidden_scalars; c->F = cfg->n_hidden_edge_feats;
+    c->HX = cfg->v_dst_feats; c->SD = cfg->s_dst_feats; c->PVW = pvw_of(c->V, c->HX);
+    c->na = cfg->n_atom_types; c->nc = cfg->n_charges; c->ne = cfg->n_bond_types;
     c->rbf_mu_step = cfg->rbf_dmax / (float)(cfg->rbf_dim - 1);
     c->rbf_inv_sigma = 1.0f / (cfg->rbf_dmax / (float)cfg->rbf_dim);
-    Blob bl{host_blob, tensors, n_tensors, {}};
-    Builder B;
-    B.sp_fmt = cfg->precision == FM_PREC_F16X3 ? 1 : 0;
-    auto bail = [&](const std::string& m) { std::string mm = m; delete c; return fail(nullptr, FM_ERR_WEIGHTS, "fm_create: %s", mm.c_str()); };
-    auto ident = [](int k) { return k; };
-
-    // ---- input embeddings
-    const int ta = tok ? cfg->a_token_dim : na + mk, tc = tok ? cfg->c_token_dim : nc + mk, te = tok ? cfg->e_token_dim : ne + mk;
-    const int tt = cfg->time_embedding_dim;
-    const float* emb_e = nullptr;
-    if (tok) {
-        const float* ea = bl.get("token_embeddings.a.weight", na + 1, ta);
-        const float* ec = bl.get("token_embeddings.c.weight", nc + 1, tc);
-        emb_e = bl.get("token_embeddings.e.weight", ne + 1, te);
-        if (!ea || !ec || !emb_e) return bail(bl.err);
-        B.put(c->emb_a, std::vector<float>(ea, ea + (na + 1) * ta));
-        B.put(c->emb_c, std::vector<float>(ec, ec + (nc + 1) * tc));
-    }
-    {
-        const int kin = ta + tc + tt;
-        const float* W1 = bl.get("scalar_embedding.0.weight", S, kin); const float* b1 = bl.get("scalar_embedding.0.bias", S);
-        const float* W2 = bl.get("scalar_embedding.2.weight", S, S); const float* b2 = bl.get("scalar_embedding.2.bias", S);
-        const float* g = bl.get("scalar_embedding.4.weight", S); const float* be = bl.get("scalar_embedding.4.bias", S);
-        if (!W1 || !b1 || !W2 || !b2 || !g || !be) return bail(bl.err);
-        c->node_embed.K1p = pad8(kin); c->node_embed.H = 256; c->node_embed.O = 256;
-        pack_linear(B, c->node_embed.W1, W1, S, kin, pad8(kin), 256, ident);
-        pad_vec(B, c->node_embed.b1, b1, S, 256);
-        pack_linear(B, c->node_embed.W2, W2, S, S, 256, 256, ident);
-        pad_vec(B, c->node_embed.b2, b2, S, 256);
-        pad_vec(B, c->node_ln_g, g, S, 256); pad_vec(B, c->node_ln_b, be, S, 256);
-        c->tab_rows = (na + 1) * (nc + 1);
-    }
-    const float *ee_W1, *ee_b1, *ee_W2, *ee_b2, *ee_g, *ee_b;
-    {
-        ee_W1 = bl.get("edge_embedding.0.weight", F, te); ee_b1 = bl.get("edge_embedding.0.bias", F);
-        ee_W2 = bl.get("edge_embedding.2.weight", F, F); ee_b2 = bl.get("edge_embedding.2.bias", F);
-        ee_g = bl.get("edge_embedding.4.weight", F); ee_b = bl.get("edge_embedding.4.bias", F);
-        if (!ee_W1 || !ee_b1 || !ee_W2 || !ee_b2 || !ee_g || !ee_b) return bail(bl.err);
-    }
-    // edge-embedding table (ne+1 rows): the edge embedding has only ne+1 distinct inputs (SURVEY.md §8a a6);
-    // evaluated once here on the host in f32 (same op order as a row of the device MLP is not required: 1e-7 class)
-    std::vector<float> ef_tab((size_t)(ne + 1) * 128), T1((size_t)(ne + 1) * 128, 0.f);
-    for (int t = 0; t <= ne; ++t) {
-        std::vector<float> in(te, 0.f), h1(F), h2(F);
-        if (tok) for (int k = 0; k < te; ++k) in[k] = emb_e[t * te + k]; else if (t < te) in[t] = 1.f;
-        for (int n = 0; n < F; ++n) { float acc = ee_b1[n]; for (int k = 0; k < te; ++k) acc = fmaf(ee_W1[n * te + k], in[k], acc); h1[n] = acc / (1.0f + expf(-acc)); }
-        for (int n = 0; n < F; ++n) { float acc = ee_b2[n]; for (int k = 0; k < F; ++k) acc = fmaf(ee_W2[n * F + k], h1[k], acc); h2[n] = acc / (1.0f + expf(-acc)); }
-        double mean = 0; for (float x : h2) mean += x; mean /= F;
-        double var = 0; for (float x : h2) var += (x - mean) * (x - mean); var /= F;
-        const float rstd = (float)(1.0 / std::sqrt(var + 1e-5));
-        for (int n = 0; n < F; ++n) ef_tab[(size_t)t * 128 + n] = (h2[n] - (float)mean) * rstd * ee_g[n] + ee_b[n];      // columns F..127 stay 0
-    }
-    if (!mk) {      // dense edge embedding of endpoint models: the same MLP as a device kernel over the pair rows
-        c->edge_embed.K1p = pad8(te); c->edge_embed.H = 128; c->edge_embed.O = 128;
-        pack_linear(B, c->edge_embed.W1, ee_W1, F, te, pad8(te), 128, ident); pad_vec(B, c->edge_embed.b1, ee_b1, F, 128);
-        pack_linear(B, c->edge_embed.W2, ee_W2, F, F, 128, 128, ident); pad_vec(B, c->edge_embed.b2, ee_b2, F, 128);
-        pad_vec(B, c->edge_ln_g, ee_g, F, 128); pad_vec(B, c->edge_ln_b, ee_b, F, 128);
-    }
-    // ---- self-conditioning
-    if (cfg->self_conditioning) {
-        const std::string p = "self_conditioning_residual_layer.";
-        const int kin = S + na + nc + 32, kinp = 256 + na + nc + 32;       // reference / tile input widths: [s | p_a | p_c | rbf]
-        const float* W1 = bl.get(p + "node_residual_mlp.0.weight", S, kin); const float* b1 = bl.get(p + "node_residual_mlp.0.bias", S);
-        const float* W2 = bl.get(p + "node_residual_mlp.2.weight", S, S); const float* b2 = bl.get(p + "node_residual_mlp.2.bias", S);
-        const int kie = F + ne + 32;
-        const float* E1 = bl.get(p + "edge_residual_mlp.0.weight", F, kie); const float* eb1 = bl.get(p + "edge_residual_mlp.0.bias", F);
-        const float* E2 = bl.get(p + "edge_residual_mlp.2.weight", F, F); const float* eb2 = bl.get(p + "edge_residual_mlp.2.bias", F);
-        if (!W1 || !b1 || !W2 || !b2 || !E1 || !eb1 || !E2 || !eb2) return bail(bl.err);
-        c->sc_node.K1p = pad8(kinp); c->sc_node.H = 256; c->sc_node.O = 256;
-        pack_linear(B, c->sc_node.W1, W1, S, kin, pad8(kinp), 256, [&](int k) { return k < 256 ? (k < S ? k : -1) : S + (k - 256); });
-        if (S == 256 && HX == 0 && !prec_two_plane(cfg->precision)) {      // 4-row node tiles of small batches (fm_k_mlp4): K padded to 320, quad-row packed
-            pack_linear4(B, c->sc_node_W1q, W1, S, kin, 320, [&](int k) { return k < 256 ? k : (k - 256 < na + nc + 32 ? S + (k - 256) : -1); });
-            pack_linear4(B, c->sc_node_W2q, W2, S, S, 256, ident);
-        }
-        pad_vec(B, c->sc_node.b1, b1, S, 256);
-        pack_linear(B, c->sc_node.W2, W2, S, S, 256, 256, ident);
-        pad_vec(B, c->sc_node.b2, b2, S, 256);
-        c->sc_edge.K1p = pad8(ne + 32); c->sc_edge.H = 128; c->sc_edge.O = 128;
-        pack_linear(B, c->sc_edge.W1, E1, F, kie, pad8(ne + 32), 128, [&](int k) { return k < ne + 32 ? F + k : -1; });
-        pad_vec(B, c->sc_edge.b1, eb1, F, 128);
-        pack_linear(B, c->sc_edge.W2, E2, F, F, 128, 128, ident);
-        pad_vec(B, c->sc_edge.b2, eb2, F, 128);
-        for (int t = 0; t <= ne; ++t)
-            for (int n = 0; n < F; ++n) {
-                float acc = eb1[n];
-                for (int k = 0; k < F; ++k) acc = fmaf(E1[(size_t)n * kie + k], ef_tab[(size_t)t * 128 + k], acc);
-                T1[(size_t)t * 128 + n] = acc;
-            }
-    }
-    B.put(c->ef_tab, ef_tab);
-    B.put(c->T1, T1);
-    // ---- convolutions
+    c->mp = model_plan(*cfg);
+    Builder B{{host_blob, tensors, n_tensors, {}}, c->mp};
+    std::vector<float> ef_tab;
+    bool ok = pack_embeddings(c.get(), B, ef_tab) && pack_self_conditioning(c.get(), B, ef_tab);
     c->conv.resize(cfg->n_convs);
-    for (int i = 0; i < cfg->n_convs; ++i) {
-        ConvW& cw = c->conv[i];
-        const std::string p = "conv_layers." + std::to_string(i) + ".";
-        const std::string k0 = p + "edge_message.0";
-        const int kin0 = S + 32 + F + SD + H0 + 4;
-        const float* Wh = bl.get(k0 + ".Wh", H0, H0);        // input vectors [x_diff | v_src (V) | v_dst_msg (HX)], hidden = max(in, out) = H0
-        const float* Wcp = bl.get(k0 + ".Wcp", H0, 8);
-        const float* Wu = bl.get(k0 + ".Wu", H0 + 4, V);
-        const float* Ws = bl.get(k0 + ".to_feats_out.0.weight", S, kin0);
-        const float* bs = bl.get(k0 + ".to_feats_out.0.bias", S);
-        const float* Wg = bl.get(k0 + ".scalar_to_vector_gates.weight", V, S);
-        const float* bg = bl.get(k0 + ".scalar_to_vector_gates.bias", V);
-        if (!Wh || !Wcp || !Wu || !Ws || !bs || !Wg || !bg) return bail(bl.err);
-        // hoisted per-node parts (input vector 0 is the displacement; 1.. are v_src)
-        pack_linear(B, cw.Wps, Ws, S, kin0, 256, 256, [&](int k) { return k < S ? k : -1; });
-        // hidden-vector row layout (FmGvpTile): [hidden (H0) | cp (4, filled by the kernel) | 0 .. KU0) | Vcp sources (8) | 0 .. PVW)
-        auto hrow = [&](int vin_row, int n) -> float {
-            if (n < H0) return Wh[(size_t)vin_row * H0 + n];
-            if (n >= KU0 && n < KU0 + 8) return Wcp[(size_t)vin_row * 8 + (n - KU0)];
-            return 0.f; };
-        B.put(cw.Wpv, pack(V, PVW, [&](int k, int n) -> float { return hrow(1 + k, n); }));
-        {
-            std::vector<float> w0(PVW, 0.f);
-            for (int n = 0; n < PVW; ++n) w0[n] = hrow(0, n);
-            B.put(cw.w0, w0);
-        }
-        FmGvpW& g0 = cw.msg[0];
-        g0.Wv1 = nullptr;
-        B.put(g0.Wu, pack(KU0, V, [&](int k, int n) -> float { return k < H0 + 4 ? Wu[k * V + n] : 0.f; }));
-        // K order of the first scalar linear: [rbf(32) | ef(128 columns, F real) | sh(V+5) | 0]; reference column order
-        // [s_src(S) | rbf(32) | ef(F) | sh(V+5)] (gvp.py:532-539,118)
-        pack_linear(B, g0.Ws, Ws, S, kin0, 160 + KU0, 256, [&](int k) {
-            if (k < 32) return S + k;
-            if (k < 160) return k - 32 < F ? S + 32 + (k - 32) : -1;
-            return k < 160 + H0 + 4 ? S + 32 + F + SD + (k - 160) : -1; });
-        pack_linear(B, cw.Ws_slab, Ws, S, kin0, 160, 256, [&](int k) { return k < 32 ? S + k : (k - 32 < F ? S + 32 + (k - 32) : -1); });
-        pack_linear(B, cw.Ws_sh, Ws, S, kin0, KU0, 256, [&](int k) { return k < H0 + 4 ? S + 32 + F + SD + k : -1; });
-        pad_vec(B, g0.bs, bs, S, 256);
-        pack_linear(B, g0.Wg, Wg, V, S, 256, V, [&](int k) { return k < S ? k : -1; });
-        pad_vec(B, g0.bg, bg, V, V);
-        const bool sp = prec_two_plane(cfg->precision);                                       // split-precision NODE / EdgeUpdate kernels: the two-plane modes only
-        const int sp_msg = prec_two_plane(cfg->precision) ? 2 : cfg->precision == FM_PREC_BF16X6 ? 3 : 0;      // 16-bit planes of the edge-message GEMM operands
-        if (sp_msg) {
-            pack_linear_sp(B, g0.Ws_sp, Ws, S, kin0, 160 + KU0, 256, [&](int k) {
-                if (k < 32) return S + k;
-                if (k < 160) return k - 32 < F ? S + 32 + (k - 32) : -1;
-                return k < 160 + H0 + 4 ? S + 32 + F + SD + (k - 160) : -1; }, sp_msg);
-            pack_linear_sp(B, g0.Wg_sp, Wg, V, S, 256, V, [&](int k) { return k < S ? k : -1; }, sp_msg);
-        }
-        if (HX > 0) {
-            // destination-node terms of the first edge GVP, hoisted per node: vectors through [Wh | Wcp] rows V+1.., scalars through Ws columns S+32+F..
-            B.put(cw.Wpvd, pack(8, PVW, [&](int k, int n) -> float { return k < HX ? hrow(V + 1 + k, n) : 0.f; }));
-            pack_linear(B, cw.Wsd, Ws, S, kin0, 256, 256, [&](int k) { return k < SD ? S + 32 + F + k : -1; });
-            // the projection GVP itself (gvp.py:304-311): V -> HX vectors, S -> SD scalars, hidden V, no cross-product features
-            const std::string kp = p + "dst_feat_msg_projection";
-            const float* pWh = bl.get(kp + ".Wh", V, V); const float* pWu = bl.get(kp + ".Wu", V, HX);
-            const float* pWs = bl.get(kp + ".to_feats_out.0.weight", SD, V + S); const float* pbs = bl.get(kp + ".to_feats_out.0.bias", SD);
-            const float* pWg = bl.get(kp + ".scalar_to_vector_gates.weight", HX, SD); const float* pbg = bl.get(kp + ".scalar_to_vector_gates.bias", HX);
-            if (!pWh || !pWu || !pWs || !pbs || !pWg || !pbg) return bail(bl.err);
-            FmGvpW& dp = cw.dproj;
-            B.put(dp.Wv1, pack(V, V + 16, [&](int k, int n) -> float { return n < V ? pWh[k * V + n] : 0.f; }));         // Wcp = 0
-            B.put(dp.Wu, pack(V + 8, 16, [&](int k, int n) -> float { return (k < V && n < HX) ? pWu[k * HX + n] : 0.f; }));
-            pack_linear(B, dp.Ws, pWs, SD, V + S, 256 + V + 8, 256, [&](int k) { return k < 256 ? (k < S ? k : -1) : (k < 256 + V ? S + (k - 256) : -1); });
-            pad_vec(B, dp.bs, pbs, SD, 256);
-            pack_linear(B, dp.Wg, pWg, HX, SD, 256, 16, [&](int k) { return k < SD ? k : -1; });
-            pad_vec(B, dp.bg, pbg, HX, 16);
-        }
-        for (int g = 1; g < 3; ++g) if (!pack_gvp(B, bl, p + "edge_message." + std::to_string(g), V, S, V, cw.msg[g], sp_msg)) return bail(bl.err);
-        const bool rows4 = S == 256 && HX == 0 && !sp;       // 4-node tiles exist for full-width f32 models on the fused node sequence
-        for (int g = 0; g < 3; ++g) if (!pack_gvp(B, bl, p + "node_update." + std::to_string(g), V, S, V, cw.upd[g], sp ? 2 : 0, rows4)) return bail(bl.err);
-        if (rows4) pack_linear4(B, cw.Wps4, Ws, S, kin0, 256, [&](int k) { return k < S ? k : -1; });
-        if (sp) pack_linear_sp(B, cw.Wps_sp, Ws, S, kin0, 256, 256, [&](int k) { return k < S ? k : -1; });
-        const float* l1g = bl.get(p + "message_layer_norm.feat_norm.weight", S); const float* l1b = bl.get(p + "message_layer_norm.feat_norm.bias", S);
-        const float* l2g = bl.get(p + "update_layer_norm.feat_norm.weight", S); const float* l2b = bl.get(p + "update_layer_norm.feat_norm.bias", S);
-        if (!l1g || !l1b || !l2g || !l2b) return bail(bl.err);
-        pad_vec(B, cw.ln1_g, l1g, S, 256); pad_vec(B, cw.ln1_b, l1b, S, 256);
-        pad_vec(B, cw.ln2_g, l2g, S, 256); pad_vec(B, cw.ln2_b, l2b, S, 256);
-    }
-    // ---- molecule updaters (only those the schedule uses; index 0 is dead when convs_per_update == 1)
+    for (int i = 0; ok && i < cfg->n_convs; ++i) ok = pack_convolution(c.get(), B, i);
     c->upd.resize(cfg->n_updaters);
-    for (int u = 0; u < cfg->n_updaters; ++u) {
-        bool used = false;
-        for (int i = 0; i < cfg->n_convs; ++i) used |= cfg->update_after[i] == u;
-        if (!used) continue;
-        UpdW& uw = c->upd[u];
-        const std::string p = "node_position_updaters." + std::to_string(u) + ".gvps.";
-        const bool spu = prec_two_plane(cfg->precision);
-        const bool rows4u = S == 256 && HX == 0 && !spu;
-        if (!pack_gvp(B, bl, p + "0", V, S, V, uw.pos[0], spu ? 2 : 0, rows4u) || !pack_gvp(B, bl, p + "1", V, S, V, uw.pos[1], spu ? 2 : 0, rows4u) || !pack_gvp(B, bl, p + "2", V, S, 1, uw.pos[2], spu ? 2 : 0, rows4u))
-            return bail(bl.err);
-        const std::string q = "edge_updaters." + std::to_string(u) + ".";
-        const bool with_d = !cfg->edge_update_no_distance;
-        const int kin = 2 * S + F + (with_d ? 32 : 0);
-        const float* W1 = bl.get(q + "edge_update_fn.0.weight", F, kin); const float* b1 = bl.get(q + "edge_update_fn.0.bias", F);
-        const float* W2 = bl.get(q + "edge_update_fn.2.weight", F, F); const float* b2 = bl.get(q + "edge_update_fn.2.bias", F);
-        const float* g = bl.get(q + "edge_norm.weight", F); const float* be = bl.get(q + "edge_norm.bias", F);
-        if (!W1 || !b1 || !W2 || !b2 || !g || !be) return bail(bl.err);
-        // input order [s_src(S) | s_dst(S) | ef(F) | d(32)] (vector_field.py:870-877); tile: Asd = [W1_src s | W1_dst s] (2 x 128 columns)
-        B.put(uw.Wasd, pack(256, 256, [&](int k, int n) -> float {
-            const int o = n < 128 ? n : n - 128;
-            if (k >= S || o >= F) return 0.f;
-            return W1[(size_t)o * kin + (n < 128 ? 0 : S) + k]; }));
-        if (rows4u) B.putv(uw.Wasd4, pack4(256, [&](int k, int n) -> float {
-            const int o = n < 128 ? n : n - 128;
-            if (k >= S || o >= F) return 0.f;
-            return W1[(size_t)o * kin + (n < 128 ? 0 : S) + k]; }));
-        // without update_edge_w_distance the rbf(d) block of the tile meets zero weights
-        pack_linear(B, uw.W1, W1, F, kin, 160, 128, [&](int k) { return k < 128 ? (k < F ? 2 * S + k : -1) : (with_d ? 2 * S + F + (k - 128) : -1); });
-        pad_vec(B, uw.b1, b1, F, 128);
-        pack_linear(B, uw.W2, W2, F, F, 128, 128, ident);
-        pad_vec(B, uw.b2, b2, F, 128);
-        if (prec_two_plane(cfg->precision)) {
-            B.putv(uw.Wasd_sp, pack_sp(256, 256, [&](int k, int n) -> float {
-                const int o = n < 128 ? n : n - 128;
-                if (k >= S || o >= F) return 0.f;
-                return W1[(size_t)o * kin + (n < 128 ? 0 : S) + k]; }, 2, B.sp_fmt));
-            pack_linear_sp(B, uw.W1_sp, W1, F, kin, 160, 128, [&](int k) { return k < 128 ? (k < F ? 2 * S + k : -1) : (with_d ? 2 * S + F + (k - 128) : -1); });
-            pack_linear_sp(B, uw.W2_sp, W2, F, F, 128, 128, ident);
-        }
-        pad_vec(B, uw.ln_g, g, F, 128); pad_vec(B, uw.ln_b, be, F, 128);
-    }
-    // ---- output heads
-    {
-        const float* W1 = bl.get("node_output_head.0.weight", S, S); const float* b1 = bl.get("node_output_head.0.bias", S);
-        const float* W2 = bl.get("node_output_head.2.weight", na + nc, S); const float* b2 = bl.get("node_output_head.2.bias", na + nc);
-        const float* E1 = bl.get("to_edge_logits.0.weight", F, F); const float* eb1 = bl.get("to_edge_logits.0.bias", F);
-        const float* E2 = bl.get("to_edge_logits.2.weight", ne, F); const float* eb2 = bl.get("to_edge_logits.2.bias", ne);
-        if (!W1 || !b1 || !W2 || !b2 || !E1 || !eb1 || !E2 || !eb2) return bail(bl.err);
-        c->node_head.K1p = 256; c->node_head.H = 256; c->node_head.O = pad16(na + nc);
-        pack_linear(B, c->node_head.W1, W1, S, S, 256, 256, ident); pad_vec(B, c->node_head.b1, b1, S, 256);
-        pack_linear(B, c->node_head.W2, W2, na + nc, S, 256, pad16(na + nc), ident); pad_vec(B, c->node_head.b2, b2, na + nc, pad16(na + nc));
-        if (S == 256 && HX == 0 && !prec_two_plane(cfg->precision)) {
-            pack_linear4(B, c->node_head_W1q, W1, S, S, 256, ident);
-            pack_linear4(B, c->node_head_W2q, W2, na + nc, S, 256, ident, 1);      // N = 64 (na + nc <= 32 real columns): one column group, K over all eight waves
-        }
-        c->edge_head.K1p = 128; c->edge_head.H = 128; c->edge_head.O = 16;
-        pack_linear(B, c->edge_head.W1, E1, F, F, 128, 128, ident); pad_vec(B, c->edge_head.b1, eb1, F, 128);
-        pack_linear(B, c->edge_head.W2, E2, ne, F, 128, 16, ident); pad_vec(B, c->edge_head.b2, eb2, ne, 16);
-    }
-    // ---- upload
-    c->arena_bytes = B.A.h.size() * sizeof(float);
-    hipError_t e = hipMalloc((void**)&c->arena, c->arena_bytes);
-    if (e != hipSuccess) { delete c; return fail(nullptr, FM_ERR_NOMEM, "fm_create: hipMalloc(%zu) failed: %s", B.A.h.size() * 4, hipGetErrorString(e)); }
-    e = hipMemcpy(c->arena, B.A.h.data(), c->arena_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(c->arena); delete c; return fail(nullptr, FM_ERR_HIP, "fm_create: weight upload failed: %s", hipGetErrorString(e)); }
-    for (const Fix& f : B.fix) *f.slot = c->arena + f.off * sizeof(float);
-    // launch-tuning overrides (fm_config, ABI 5; 0 = automatic everywhere): read per batch by plan_batch
-    auto tile_ok = [](int t) { return t == 0 || t == 16 || t == 32 || t == 64; };
-    auto rg_tile = [](int t) { return t == 4 || t == 8 || t == 12 || t == 20; };
-    if (!tile_ok(cfg->tile_edge) || !(tile_ok(cfg->tile_node) || rg_tile(cfg->tile_node))) {
-        (void)hipFree(c->arena); delete c;
-        return fail(nullptr, FM_ERR_INVALID, "fm_create: fm_config.tile_edge must be 0 (automatic), 16, 32 or 64; tile_node additionally 4, 8, 12 or 20");
-    }
+    for (int u = 0; ok && u < cfg->n_updaters; ++u)       // only the updaters the schedule uses (index 0 is dead when convs_per_update == 1)
+        if (std::count(cfg->update_after, cfg->update_after + cfg->n_convs, u)) ok = pack_updater(c.get(), B, u);
+    if (!ok || !pack_heads(c.get(), B)) return fail(nullptr, FM_ERR_WEIGHTS, "fm_create: %s", B.bl.err.c_str());
+    if ((rc = upload(c.get(), B))) return rc;
     {
         int dev = 0; hipDeviceProp_t prop{};
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
@@ -828,7 +828,7 @@ int fm_create(const fm_config* cfg, const fm_tensor_desc* tensors, int n_tensors
     fm_opt_in_msg_v32(); fm_opt_in_msg_v16(); fm_opt_in_node();      // the heavy families, in their own translation units
     opt_in(mlp_instances); opt_in(mlp_pair_instances); opt_in(mlp4_instances); opt_in(mlp4_pair_instances);
     opt_in(node_proj_instances); opt_in(edge_update_instances); opt_in(edge_update_sp_instances);
-    *out = c;
+    *out = c.release();
     return FM_OK;
 }
 
@@ -844,8 +844,8 @@ int fm_destroy(fm_ctx* c) {
 }
 
 // ---------------------------------------------------------------------------------------- batch plan
-// Every launch choice that depends on the batch, made here only, from the model, its fm_config overrides (0 = automatic), the CU count and the molecule
-// sizes: the workspace is laid out for the plan, fm_batch_bind keeps it in the context, evaluate / ctmc_impl read it.
+// Every launch choice that depends on the batch, made here only, from the model's ModelPlan (which instances have their weights), its fm_config overrides
+// (0 = automatic), the CU count and the molecule sizes: the workspace is laid out for the plan, fm_batch_bind keeps it in the context, evaluate / ctmc_impl read it.
 static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     if (B <= 0) return fail(c, FM_ERR_INVALID, "batch of %d molecules", B);
     long long N = 0, E = 0;
@@ -860,7 +860,7 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     if (N > 0x7fffffffLL / 1024) return fail(c, FM_ERR_INVALID, "batch too large: %lld nodes (limit %lld per bind; split the batch)", N, 0x7fffffffLL / 1024);
     const fm_config& cf = c->cfg;
     const int n_cus = c->n_cus;
-    const bool f32 = cf.precision == FM_PREC_F32, two_plane = prec_two_plane(cf.precision);
+    const ModelPlan& m = c->mp;
     p = BatchPlan{};
     p.B = B; p.N = (int)N; p.E = (int)E; p.U = (int)(E / 2); p.nmax = nmax;
     const int U = p.U;
@@ -889,28 +889,27 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     // tiles fit ONE per CU: the node kernel is a serial chain per tile whose scalar GEMMs scale with the tile height, so the smallest tile that
     // still gives every tile a CU of its own is the fastest (beyond one tile per CU the small tiles lose: each streams the full weights).
     // fm_config.tile_node (16 | 32 | 64, or 4 / 8 / 12 / 20 nodes) forces a size.
-    const bool rg_ok = c->S == 256 && c->HX == 0 && f32 && cf.fuse_node >= 0;
     int tn = cf.tile_node;
     if (!tn) {
         tn = (N + 31) / 32 <= n_cus ? 16 : 32;
-        if (rg_ok) {      // the 4 RG-node instances keep the regular tiles' summation order (fm_wave_gemm4): the choice may follow the batch size in canonical mode
+        if (m.quad_node) {      // the 4 RG-node instances keep the regular tiles' summation order (fm_wave_gemm4): the choice may follow the batch size in canonical mode
             static const int cand[] = {4, 8, 12, 16, 20};
             for (int r : cand) if ((N + r - 1) / r <= n_cus) { tn = r; break; }
         }
     }
     if (tn == 4 || tn == 8 || tn == 12 || tn == 20) {
-        if (rg_ok) p.node_rg = tn / 4;
+        if (m.quad_node) p.node_rg = tn / 4;
         tn = tn == 20 ? 32 : 16;          // models the instances do not exist for take the frame's regular tile
     }
     p.tm_node = tn;
     if ((c->HX || !cf.has_mask) && (p.tm_node > 32)) p.tm_node = 32;
     // split-precision node kernel: the fused sequence of the two-plane modes, 16- / 32-row tiles
-    p.node_sp = (p.fuse_node && p.tm_node <= 32 && two_plane) ? (cf.precision == FM_PREC_F16X3 ? 3 : 1) : 0;
+    p.node_sp = p.fuse_node && p.tm_node <= 32 ? m.node_sp : 0;
     // EdgeUpdate: fm_config.tile_edge_update = 64 selects 64-row tiles for full-width f32 models (the narrow and split-precision instances are 32 rows)
-    p.tm_eupd = cf.tile_edge_update == 64 && c->F == 128 && !two_plane ? 64 : 32;
+    p.tm_eupd = cf.tile_edge_update == 64 && !m.narrow_f && !m.node_sp ? 64 : 32;
     // the edge head as the epilogue of the last EdgeUpdate (fm_config.fuse_node = 2 | -1: separate): the tile's pair rows are gathered with 31-bit offsets
     // inside ONE molecule's edge rows (n < 2048 atoms); larger: separate head
-    p.fuse_head = (cf.fuse_node == 0 || cf.fuse_node == 1) && c->F == 128 && p.tm_eupd == 32 && !two_plane
+    p.fuse_head = (cf.fuse_node == 0 || cf.fuse_node == 1) && !m.narrow_f && p.tm_eupd == 32 && !m.node_sp
                   && (long long)nmax * (nmax - 1) * 512 < 0x7ffffe00LL;
     // Pair-slab convolutions: the convolutions that run before any molecule update see pair-symmetric edge features and distances (self-conditioned f32
     // models; fm_config.pair_slab = -1: none).  The hoist is on for batches with at least four rounds of 32-row pair tiles (measured neutral below: the
@@ -920,9 +919,7 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     // composition of its batch (see FM_CHUNK_E in fm_kernels.h for the aggregation order).  Tile heights -- incl. the 4 RG-node instances and the 4-row node
     // MLPs, whose GEMMs keep the regular tiles' order since round 6 (fm_wave_gemm4) -- follow the batch size in both modes.  -1: the pair slab follows the
     // batch size too (round 5's rule).  The Q tables (U KB each) exist in the workspace only when the batch uses them.
-    if (cf.pair_slab >= 0 && c->HX == 0 && f32 && cf.self_conditioning && U > 0 && ld_for(c->sc_edge.H) <= 164      // the slab GEMM reads [rbf | ef]
-        && (cf.pair_slab > 0 || cf.canonical >= 0 || (U + 31) / 32 >= 16LL * n_cus))                                  // rows at the pitch 164 of a 128-wide hidden tile
-        p.n_pq = cf.n_convs > 1 && cf.update_after[0] < 0 ? 2 : 1;      // the first two convolutions, unless a molecule update runs after the first
+    if (U > 0 && (cf.pair_slab > 0 || cf.canonical >= 0 || (U + 31) / 32 >= 16LL * n_cus)) p.n_pq = m.slab_convs;      // ModelPlan::slab_convs: which models
     // Node- and pair-side MLPs with the same inputs share one launch while the batch is small (launch_mlp_stage); fm_config.pair_mlps = 1 | -1 forces either
     const int mlp_tiles = (p.N + FM_TM - 1) / FM_TM + (U + FM_TM - 1) / FM_TM;
     p.pair_mlps = cf.fuse_node >= 0 && (cf.pair_mlps ? cf.pair_mlps > 0 : mlp_tiles <= n_cus);
@@ -933,7 +930,7 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     // node-side MLPs on 4-row tiles (fm_k_mlp4) while such tiles fit one per CU: a 16-row tile's two 256-wide layers are ~7 us of matrix time on one CU
     // whatever the batch, four rows on v_mfma_f32_4x4x1 are the layers' weight stream; fm_config.mlp_small_tiles = 2 forces it (1 / -1: never).  The regular
     // tiles' bits (fm_rows4_linear): the choice may follow the batch size in canonical mode
-    p.mlp4 = c->node_head_W1q && (cf.mlp_small_tiles ? cf.mlp_small_tiles == 2 : (p.N + 3) / 4 <= n_cus);
+    p.mlp4 = m.quad_mlp && (cf.mlp_small_tiles ? cf.mlp_small_tiles == 2 : (p.N + 3) / 4 <= n_cus);
     // large batches: a separate edge head is a gather of two 512-byte rows per pair in front of 17 k MAC -- latency / HBM work; 32-row tiles (34 KB of LDS)
     // put four workgroups on a CU instead of two
     p.edge_head32 = (U + 31) / 32 >= 16 * n_cus;

@@ -1,8 +1,9 @@
 // Host-side declarations shared by the translation units of libflowmol_hip.so, compiled in parallel (flowmol_amd/build.py) -- fm_engine.cpp: C ABI, weight
 // packing, the batch plan, workspace, the launch sequence and the small kernels; fm_tu_msg32.cpp / fm_tu_msg16.cpp: the edge-message instances; fm_tu_node.cpp:
 // the node-kernel instances.  The engine reaches the heavy kernels through the launcher functions declared at the end of this file (no unit instantiates
-// another unit's kernels).  Every launch choice that depends on the batch is made once, by plan_batch (fm_engine.cpp), into the BatchPlan that the workspace
-// layout and the launches read; every kernel family names its instances once, in an instance list that its launcher and the LDS opt-in both read.
+// another unit's kernels).  Which weight copies a model has is decided once, by fm_create (fm_engine.cpp), into the ModelPlan that the packing and plan_batch
+// read; every launch choice that depends on the batch is made once, by plan_batch, into the BatchPlan that the workspace layout and the launches read; every
+// kernel family names its instances once, in an instance list that its launcher and the LDS opt-in both read.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -50,6 +52,19 @@ struct UpdW {
     const void* Wasd4 = nullptr;       // quad-row packed (4-node tiles)
 };
 
+// The weight layouts of one model (model_plan, fm_engine.cpp): a function of its fm_config only.  fm_create packs a copy exactly when this says so, and
+// plan_batch selects an instance only when this says its copies exist.
+struct ModelPlan {
+    bool narrow_s = false;    // n_hidden_scalars < 256: LayerNorm statistics over the real width (narrow node instances)
+    bool narrow_f = false;    // n_hidden_edge_feats < 128 (narrow EdgeUpdate instance)
+    bool quad_mlp = false;    // quad-row copies of the 4-row node MLPs and conv 0's projection (fm_k_mlp4): sc_node_W1q / W2q, node_head_W1q / W2q, conv[0].Wps4
+    bool quad_node = false;   // quad-row copies of the RG node instances: node-side FmGvpW::Ws4, every conv's Wps4, UpdW::Wasd4
+    int msg_planes = 0;       // 16-bit planes of the edge-message split copies (FmGvpW::Ws_sp / Wg_sp of the message GVPs): 0 = none, 2, 3 (bf16x6)
+    int node_sp = 0;          // two-plane split copies of the node and EdgeUpdate kernels (BatchPlan::node_sp): 0 = none, 1 = bf16 planes, 3 = half planes
+    bool half_planes = false; // every split copy in IEEE-half planes (f16x3), else bf16
+    int slab_convs = 0;       // convolutions that carry the pair-slab rows ConvW::Ws_slab / Ws_sh (0..2; BatchPlan::n_pq)
+};
+
 // The launch choices of one bound batch (plan_batch, fm_engine.cpp): made from the model, its fm_config overrides, the CU count and the molecule
 // sizes.  What varies per call (prev given, dense inputs, taps, the last pass) is decided by the evaluation itself.
 struct BatchPlan {
@@ -81,6 +96,7 @@ struct fm_ctx {
     int V = 32, S = 256, F = 128, na = 0, nc = 0, ne = 0;
     int HX = 0, SD = 0, PVW = 48;     // use_dst_feats: destination vectors / scalars per message; width of the hoisted hidden-vector rows
     int n_cus = 256;          // compute units of the device (fm_create); read by plan_batch only
+    ModelPlan mp{};           // the weight copies this model has (fm_create)
     const void *sc_node_W1q = nullptr, *sc_node_W2q = nullptr, *node_head_W1q = nullptr, *node_head_W2q = nullptr;      // quad-row packed copies for fm_k_mlp4
     float* Q[2] = {nullptr, nullptr};      // (U,256) each, in the workspace
     float rbf_mu_step = 0.f, rbf_inv_sigma = 0.f;

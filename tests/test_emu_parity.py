@@ -601,6 +601,22 @@ def test_half_split_precision_on_emulation(emu_lib, name, sizes):
     assert not all(torch.equal(outs['f32'][k], outs['f16x3'][k]) for k in 'xace')
 
 
+@pytest.mark.parametrize('precision,bound', [('f32', 2e-5), ('bf16x3', 2e-5), ('bf16x6', 1e-5), ('f16x3', 1e-5)])
+def test_every_precision_and_tuning_finds_its_weights_on_emulation(emu_lib, precision, bound):
+    """fm_create packs the weight copies its ModelPlan names, and plan_batch selects only instances whose copies the ModelPlan names: flowmol3 under every
+    precision with automatic tuning, RG node tiles with 4-row MLPs, 16-row node tiles with 64-row MLPs, and the forced pair slab, each against the oracle
+    within the output bound of that precision's own test above.  A selected copy that was never packed would be a null weight pointer."""
+    from flowmol_amd.engine import Engine
+    cfg = presets.flowmol3()
+    sd = weights.synth_state_dict(cfg, 0)
+    orc = cpu_ref.OracleVF(cfg, sd)
+    for tuning in ({}, {'tile_node': 4, 'mlp_small_tiles': 2}, {'tile_node': 16, 'mlp_small_tiles': -1}, {'pair_slab': 1}):
+        eng = Engine(cfg, sd, device='cpu', lib=emu_lib, precision=precision, tuning=tuning)
+        errs, out, ref = forward_compare(eng, orc, cfg, torch.tensor([4, 3]), 0.5, True, taps=False)
+        bad = {k: v for k, v in errs.items() if not v < bound}
+        assert errs and not bad, (tuning, bad)
+
+
 def _one_molecule_inputs(cfg, n, seed):
     g = torch.Generator().manual_seed(seed)
     U = n * (n - 1) // 2
