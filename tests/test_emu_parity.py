@@ -11,7 +11,7 @@ import torch
 
 from flowmol_amd import _lib, presets, weights
 from oracle import cpu_ref
-from parity_util import forward_compare
+from parity_util import dx_gates, forward_compare, mutation_targets, out_of_tolerance, visible_weights
 
 
 
@@ -23,6 +23,8 @@ from parity_util import forward_compare
                                                ('geom_arom', [6, 3], 0.4, False), ('flowmol3_arom', [4, 5], 0.5, True),    # explicit aromaticity: 5 bond types + mask
                                                ('arch_variants', [5, 1, 4], 0.5, True)])      # n_recycles=2, message_norm='mean', EdgeUpdate without distances, shared updater
 def test_emulated_forward_matches_oracle(emu_lib, name, sizes, t, prev, tile):
+    """Every stage and output within 2e-5 at the weights as drawn, and again under parity_util.visible_weights() with the displacement stages
+    (`upd{i}.dx`, `out.dx`: what each position update ADDS, scored against its own size and gated by parity_util.dx_gates) next to them."""
     from flowmol_amd.engine import Engine
     cfg = presets.PRESETS[name]()
     sd = weights.synth_state_dict(cfg, 0)
@@ -31,6 +33,53 @@ def test_emulated_forward_matches_oracle(emu_lib, name, sizes, t, prev, tile):
     errs, out, ref = forward_compare(eng, orc, cfg, torch.tensor(sizes), t, prev)
     bad = {k: v for k, v in errs.items() if not v < 2e-5}
     assert not bad, bad
+    eng.close()
+    bad, errs, gates = visible_regime_failures(emu_lib, name, sizes, t, prev, {'tile_edge': tile, 'tile_node': tile})
+    assert not bad, (bad, gates)
+    assert any(k.startswith('upd') and k.endswith('.dx') for k in errs) and 'out.dx' in errs
+
+
+def visible_regime_failures(emu_lib, name, sizes, t, prev, tuning, mutate=None, stage_tol=2e-5, out_tol=2e-5, gates=None):
+    """One emulated evaluation under visible_weights() against the oracle, scored with the displacement stages -> (stages out of tolerance, all
+    errors, the dx gates).  mutate: a state-dict key the ENGINE gets x1.01 while the oracle keeps the true tensor."""
+    from flowmol_amd.engine import Engine
+    cfg = presets.PRESETS[name]()
+    sd = visible_weights(name, weights.synth_state_dict(cfg, 0))
+    sd_eng = sd if mutate is None else {**sd, mutate: sd[mutate] * 1.01}
+    eng = Engine(cfg, sd_eng, device='cpu', lib=emu_lib, tuning=tuning)
+    errs, out, ref = forward_compare(eng, cpu_ref.OracleVF(cfg, sd), cfg, torch.tensor(sizes), t, prev, dx=True)
+    gates = gates or dx_gates(cfg, sd, torch.tensor(sizes), t, prev)[0]
+    launches = {k: eng.profile_get(k)[1] for k in ('pos_update',)}
+    eng.close()
+    errs['launches'] = launches
+    return out_of_tolerance({k: v for k, v in errs.items() if k != 'launches'}, gates, stage_tol, out_tol), errs, gates
+
+
+@pytest.mark.parametrize('name,sizes,fuses', [('flowmol3', [4, 7, 2], True), ('dev_narrow', [5, 3, 6], True), ('dev', [5, 3, 6], False)])
+def test_emulated_position_update_kernel_and_fused_branch_are_both_scored(emu_lib, name, sizes, fuses):
+    """fm_config.fuse_node = -1 runs the position update as a kernel of its own (fm_k_pos_update); the default runs it as the last branch of the node
+    kernel (models with destination-node message features keep the separate kernels either way).  Both under the displacement stages, and the
+    profiler confirms which of the two ran."""
+    for fuse in (-1, 0):
+        bad, errs, gates = visible_regime_failures(emu_lib, name, sizes, 0.5, True, {'fuse_node': fuse, 'tile_edge': 16, 'tile_node': 16})
+        assert not bad, (fuse, bad, gates)
+        assert (errs['launches']['pos_update'] > 0) == (fuse < 0 or not fuses), (fuse, errs['launches'])
+
+
+@pytest.mark.parametrize('name', ['flowmol3', 'dev'])
+def test_emulated_engine_with_one_tensor_off_by_one_percent_fails_the_scoring(emu_lib, name):
+    """End to end through the kernels: an engine built with ONE tensor x1.01 against the oracle with the true weights must be reported out of tolerance,
+    for each of mutation_targets() -- the engine reads the tensor and the scoring sees it.  (tests/test_detection_power.py proves the same for every
+    tensor on the oracle alone.)"""
+    cfg = presets.PRESETS[name]()
+    targets = mutation_targets(cfg)
+    assert len(targets) <= 16
+    unseen, gates = [], None
+    for key in targets:
+        bad, errs, gates = visible_regime_failures(emu_lib, name, [5, 9, 12, 3, 2], 0.5, True, {}, mutate=key, gates=gates)
+        if not bad:
+            unseen.append(key)
+    assert not unseen, unseen
 
 
 def test_emulated_sample_api_short_trajectory(emu_lib):

@@ -12,7 +12,7 @@ import torch
 
 from flowmol_amd import presets, weights
 from oracle import cpu_ref
-from parity_util import forward_compare, integrate_golden
+from parity_util import add_dx_stages, dx_gates, forward_compare, integrate_golden, mutation_targets, out_of_tolerance, stage_errors, visible_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +33,47 @@ def _report(name, obj):
 _engines = {}
 
 
-def engine_for(name, tile=0):
+def engine_for(name, tile=0, visible=False):
     """Engine + oracle per preset.  tile = 0: the library chooses the row-tile size per batch (16 rows for batches that
     do not fill the chip, else 32); 16 / 32: forced through fm_config.tile_edge / tile_node.  precision is passed explicitly:
-    no environment variable can change what the parity tests verify."""
+    no environment variable can change what the parity tests verify.  visible: under parity_util.visible_weights(), the regime of the
+    displacement stages (cached like the weights as drawn: one engine per preset, tile and regime for the whole session)."""
     from flowmol_amd.engine import Engine
-    if (name, tile) not in _engines:
+    key = (name, tile, 'visible') if visible else (name, tile)
+    if key not in _engines:
         cfg = presets.PRESETS[name]()
         sd = weights.synth_state_dict(cfg, 0)
+        if visible:
+            sd = visible_weights(name, sd)
         eng = Engine(cfg, sd, device='cuda:0', precision='f32', tuning={'tile_edge': tile, 'tile_node': tile})
-        _engines[(name, tile)] = (cfg, sd, eng, cpu_ref.OracleVF(cfg, sd))
-    return _engines[(name, tile)]
+        _engines[key] = (cfg, sd, eng, cpu_ref.OracleVF(cfg, sd))
+    return _engines[key]
+
+
+_dx_gates = {}
+
+
+def dx_gates_for(name, sd, sizes, t, prev):
+    """parity_util.dx_gates of one case under visible_weights() (two oracle runs, one in float64), computed once per case: both tile heights and every
+    tuning share it."""
+    key = (name, tuple(sizes), float(t), bool(prev))
+    if key not in _dx_gates:
+        _dx_gates[key] = dx_gates(presets.PRESETS[name](), sd, torch.tensor(sizes), t, prev)
+    return _dx_gates[key]
+
+
+def visible_regime_failures(label, name, eng, orc, cfg, sd, sizes, t, prev):
+    """The same evaluation under visible_weights() with the displacement stages `upd{i}.dx` / `out.dx` next to every stage and output: what each position
+    update ADDS, scored against its own size (the coordinate stages are blind to it: a whole update is as large as their tolerance) and gated by the
+    reference arithmetic alone -- max(8 x the oracle's f32-vs-f64 discrepancy of that stage, 4 ulp(max|x|) / max|ref dx|).  Measured yardsticks
+    (flowmol3, [5, 9, 12, 3, 2], t = 0.5): f32-vs-f64 1.0e-6 .. 3.5e-6, floor 3.5e-6 .. 1.1e-5 per displacement stage, displacements 3 .. 9 % of max|x|.
+    The errors go into the parity report with both yardsticks beside them.  Returns the stages out of tolerance."""
+    errs, out, ref = forward_compare(eng, orc, cfg, torch.tensor(sizes), t, prev, dx=True)
+    gates, detail = dx_gates_for(name, sd, sizes, t, prev)
+    _report(label, {**errs, 'dx_gate': gates, 'dx_oracle_f32_vs_f64': {k: d['f32_vs_f64'] for k, d in detail.items()},
+                    'dx_subtraction_floor': {k: d['floor'] for k, d in detail.items()}})
+    assert 'out.dx' in errs and any(k.startswith('upd') and k.endswith('.dx') for k in errs)
+    return out_of_tolerance(errs, gates, STAGE_TOL, OUT_TOL)
 
 
 def test_native_library_is_the_hip_build():
@@ -81,6 +111,9 @@ def test_forward_matches_oracle(name, sizes, t, prev, tile):
     assert not bad, f'stages out of tolerance: {bad}\nall: {errs}'
     for k in 'ace':     # probabilities are normalised
         assert torch.allclose(out[k].sum(-1).cpu(), torch.ones(out[k].shape[0]), atol=1e-5)
+    cfg, sd, eng, orc = engine_for(name, tile, visible=True)
+    bad = visible_regime_failures(f'forward_visible[{name},{sizes},{t},tile{tile}]', name, eng, orc, cfg, sd, sizes, t, prev)
+    assert not bad, f'visible weights, stages out of tolerance: {bad}'
 
 
 @pytest.mark.parametrize('tuning', [{'tile_edge': 64, 'tile_node': 64}, {'tile_edge_update': 64}, {'tile_edge': 64, 'tile_node': 64, 'tile_edge_update': 64, 'pair_slab': -1},
@@ -102,6 +135,11 @@ def test_forward_matches_oracle_under_every_accepted_tuning(name, sizes, t, prev
     _report(f'forward_tuning[{name},{sizes},{t},{tuning}]', errs)
     bad = {k: v for k, v in errs.items() if not (v < (OUT_TOL if k.startswith('out.') else STAGE_TOL))}
     assert not bad, f'stages out of tolerance: {bad}'
+    eng.close()
+    sd = visible_weights(name, sd)
+    eng = Engine(cfg, sd, device='cuda:0', precision='f32', tuning=tuning)
+    bad = visible_regime_failures(f'forward_tuning_visible[{name},{sizes},{t},{tuning}]', name, eng, cpu_ref.OracleVF(cfg, sd), cfg, sd, sizes, t, prev)
+    assert not bad, f'visible weights, stages out of tolerance: {bad}'
     eng.close()
 
 
@@ -836,8 +874,15 @@ def test_full_size_forward_matches_oracle_on_selected_molecules(B, mols):
     job on ONE GPU: one network evaluation at t = 0.5 with a previous endpoint; the listed molecules (1024: 0, 127 | 128 = either side of the
     first XCD tile-chunk boundary, 69,184 tiles / 8 XCDs = 8,648 tiles = 128 molecules, 600 and 1023) are compared with the oracle run on each
     molecule ALONE, per stage (node state after every conv, positions after every update, the last edge features) and on the outputs --
-    norm-wise like the small-batch tests and element-wise (atol + rtol) on the outputs."""
-    cfg, sd, eng, orc = engine_for('flowmol3')
+    norm-wise like the small-batch tests and element-wise (atol + rtol) on the outputs.  Then the same under parity_util.visible_weights() with the
+    displacement stages, each molecule's against the gate measured on that molecule (worst error / gate over the molecules must stay below 1); the
+    8192-molecule job too: a second engine's 31.5 GB workspace next to the cached one's fits the device several times over."""
+    for visible in (False, True):
+        _full_size_forward(B, mols, visible)
+
+
+def _full_size_forward(B, mols, visible):
+    cfg, sd, eng, orc = engine_for('flowmol3', visible=visible)
     n = 47
     u = n * (n - 1) // 2
     n_atoms = torch.full((B,), n)
@@ -862,7 +907,7 @@ def test_full_size_forward_matches_oracle_on_selected_molecules(B, mols):
     bufs[f'upd{last_upd}.ef'] = torch.zeros(E, 128, device='cuda:0')
     out = eng.forward(state, 0.5, prev={k: v.cuda().contiguous() for k, v in prev.items()}, remove_com=True, taps=bufs)
     eng.synchronize()
-    worst = {}
+    worst, yard = {}, {}
     one = torch.tensor([n])
     batch1 = cpu_ref.build_batch(one)
     # internal (destination-major) index of the reference's edge (src, dst) inside one molecule
@@ -878,6 +923,15 @@ def test_full_size_forward_matches_oracle_on_selected_molecules(B, mols):
             ref = orc.forward(batch1, x[ns_], a1h, c1h, e1h, torch.full((1,), 0.5), prev={'x': prev['x'][ns_], 'a': prev['a'][ns_], 'c': prev['c'][ns_], 'e': prev['e'][ps_]},
                               apply_softmax=True, remove_com=True)
         taps_o, orc.taps = orc.taps, None
+        if visible:       # displacement stages of this molecule (parity_util.add_dx_stages on both sides), each scored in units of its own gate
+            inp = {'batch': batch1, 'x': x[ns_], 'a': a[ns_], 'c': c[ns_], 'eu': eu[ps_], 'prev': {'x': prev['x'][ns_], 'a': prev['a'][ns_], 'c': prev['c'][ns_], 'e': prev['e'][ps_]}}
+            upd = [k for k in bufs if k.endswith('.x')]
+            got_m = add_dx_stages({**{k: bufs[k][ns_].cpu() for k in upd}, 'out.x': out['x'][ns_].cpu()}, cfg, inp)
+            want_m = add_dx_stages({**{k: taps_o[k] for k in upd}, 'out.x': ref['x']}, cfg, inp)
+            gates, detail = dx_gates(cfg, sd, one, 0.5, True, inp=inp)
+            for k, e in stage_errors({k: v for k, v in got_m.items() if k.endswith('.dx')}, want_m).items():
+                worst[k + ' / gate'] = max(worst.get(k + ' / gate', 0.0), e / gates[k] if e == e else float('inf'))
+                yard[k] = {'gate': max(yard.get(k, {}).get('gate', 0.0), gates[k]), 'oracle_f32_vs_f64': max(yard.get(k, {}).get('oracle_f32_vs_f64', 0.0), detail[k]['f32_vs_f64'])}
         for k, buf in bufs.items():
             if k.endswith('.ef'):
                 got = buf[m * n * (n - 1):(m + 1) * n * (n - 1)].cpu()[internal]
@@ -894,9 +948,11 @@ def test_full_size_forward_matches_oracle_on_selected_molecules(B, mols):
         got = out['e'][ps_].cpu()
         worst['out.e'] = max(worst.get('out.e', 0.0), float((got - ref['e']).abs().max() / ref['e'].abs().max()))
         torch.testing.assert_close(got, ref['e'], rtol=2e-4, atol=2e-6)
-    _report('c3_size_forward' if B == 1024 else f'c4_whole_job_forward[{B}x{n}]', {**worst, 'ef_bytes': E * 512, 'workspace_bytes': eng.workspace_bytes})
-    bad = {k: v for k, v in worst.items() if not (v < (OUT_TOL if k.startswith('out.') else STAGE_TOL))}
+    _report(('c3_size_forward' if B == 1024 else f'c4_whole_job_forward[{B}x{n}]') + ('_visible' if visible else ''),
+            {**worst, 'ef_bytes': E * 512, 'workspace_bytes': eng.workspace_bytes, **({'dx_yardsticks_worst_molecule': yard} if visible else {})})
+    bad = {k: v for k, v in worst.items() if not (v < (1.0 if k.endswith('.dx / gate') else OUT_TOL if k.startswith('out.') else STAGE_TOL))}
     assert not bad, worst
+    assert not visible or ('out.dx / gate' in worst and any(k.startswith('upd') for k in yard))
     if B == 8192:       # release the 13 GB of taps (the cached engine keeps its 31.5 GB workspace for the next 8192-molecule test)
         del bufs, out, state
         torch.cuda.empty_cache()
@@ -1177,6 +1233,31 @@ def test_endpoint_parameterization_matches_reference_golden(golden_dir):
     assert all(v < 1e-5 for v in res.values()), res
 
 
+@pytest.mark.parametrize('name', ['flowmol3', 'dev'])
+def test_engine_with_one_tensor_off_by_one_percent_fails_the_scoring(name):
+    """End to end through the HIP kernels: an engine built with ONE tensor x1.01 against the oracle with the true weights must be reported out of
+    tolerance by the scoring of the forward tests (visible weights, displacement stages), for each of parity_util.mutation_targets() -- the three GVPs
+    of the last position updater, an EdgeUpdate matrix, the last convolution's last cross-product matrix: the engine reads the tensor and the test sees
+    it.  One Engine per tensor (<= 16), each closed."""
+    from flowmol_amd.engine import Engine
+    cfg = presets.PRESETS[name]()
+    sd = visible_weights(name, weights.synth_state_dict(cfg, 0))
+    orc = cpu_ref.OracleVF(cfg, sd)
+    sizes, t, prev = [5, 9, 12, 3, 2], 0.5, True
+    gates, _ = dx_gates_for(name, sd, sizes, t, prev)
+    targets = mutation_targets(cfg)
+    assert len(targets) <= 16
+    seen = {}
+    for key in targets:
+        eng = Engine(cfg, {**sd, key: sd[key] * 1.01}, device='cuda:0', precision='f32')
+        errs, out, ref = forward_compare(eng, orc, cfg, torch.tensor(sizes), t, prev, dx=True)
+        eng.close()
+        bad = out_of_tolerance(errs, gates, STAGE_TOL, OUT_TOL)
+        seen[key] = max(v / (gates[k] if k.endswith('.dx') else OUT_TOL if k.startswith('out.') else STAGE_TOL) for k, v in errs.items()) if bad else 0.0
+    _report(f'engine_mutation[{name}] worst error / tolerance per tensor x1.01', seen)
+    assert all(v > 0 for v in seen.values()), {k: v for k, v in seen.items() if not v > 0}
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # opt-in split precision (bf16x3 edge-message GEMMs): NOT the reference's f32 arithmetic -- errors are reported, gates are the
 # same as the f32 path's where they hold, and nothing here feeds a parity claim of the default path
@@ -1267,6 +1348,15 @@ def test_forward_matches_oracle_on_random_batches(seed):
     _report(f'forward_random[{seed}: {name},{sizes},{t:.3f},prev={prev},tile{tile},pair_slab={"forced" if pq else "auto"}]', errs)
     bad = {k: v for k, v in errs.items() if not (v < (OUT_TOL if k.startswith('out.') else STAGE_TOL))}
     assert not bad, f'{name} {sizes} t={t} tile={tile}: {bad}'
+    if pq:
+        if (name, tile, 'visible') not in _pq_engines:
+            sd = visible_weights(name, weights.synth_state_dict(cfg, 0))
+            _pq_engines[(name, tile, 'visible')] = (cfg, sd, Engine(cfg, sd, device='cuda:0', precision='f32', tuning={'tile_edge': tile, 'tile_node': tile, 'pair_slab': 1}), cpu_ref.OracleVF(cfg, sd))
+        cfg, sd, eng, orc = _pq_engines[(name, tile, 'visible')]
+    else:
+        cfg, sd, eng, orc = engine_for(name, tile, visible=True)
+    bad = visible_regime_failures(f'forward_random_visible[{seed}: {name},{sizes},{t:.3f},prev={prev},tile{tile}]', name, eng, orc, cfg, sd, sizes, t, prev)
+    assert not bad, f'visible weights, {name} {sizes} t={t} tile={tile}: {bad}'
 
 
 @pytest.mark.parametrize('regime,scale', [('unit weights', 1.0), ('all weights x3', 3.0)])
