@@ -11,11 +11,13 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 7
+FM_ABI_VERSION = 8
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
 FM_MAX_CONVS = 16
+# fm_prior_kind, by the reference's prior names (flowmol/data_processing/priors.py)
+FM_PRIOR_KINDS = {'gaussian': 0, 'uniform-simplex': 1, 'barycenter': 2, 'biased-simplex': 3, 'marginal': 4, 'c-given-a': 5}
 
 LIB_NAME = 'libflowmol_hip.so'
 PKG_DIR = Path(__file__).resolve().parent
@@ -36,10 +38,12 @@ class fm_config(C.Structure):
         ('fuse_node', C.c_int32), ('pair_mlps', C.c_int32), ('mlp_small_tiles', C.c_int32), ('pair_slab', C.c_int32),
         # ABI 7: 0 / 1 = canonical arithmetic (a molecule's bits do not depend on its batch), -1 = the pair slab follows the batch size (results then equal to f32 summation order)
         ('canonical', C.c_int32),
+        # ABI 8: workgroup size of the fused CTMC kernels, 0 = per batch | 256 | 1024 (same bits)
+        ('ctmc_threads', C.c_int32),
     ]
 
 
-TUNING_FIELDS = ('tile_edge', 'tile_node', 'tile_edge_update', 'xcd_swizzle', 'fuse_node', 'pair_mlps', 'mlp_small_tiles', 'pair_slab', 'canonical')
+TUNING_FIELDS = ('tile_edge', 'tile_node', 'tile_edge_update', 'xcd_swizzle', 'fuse_node', 'pair_mlps', 'mlp_small_tiles', 'pair_slab', 'canonical', 'ctmc_threads')
 
 
 class fm_tensor_desc(C.Structure):
@@ -82,6 +86,15 @@ class fm_traj_sink(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('x', 'a', 'c', 'e', 'x1', 'a1', 'c1', 'e1')]
 
 
+class fm_prior_mod(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('std', C.c_float), ('simplex_center', C.c_int32), ('blur', C.c_float), ('has_blur', C.c_int32),
+                ('vertex_prob', C.c_float), ('vertex_idx', C.c_int32), ('p', C.c_void_p)]
+
+
+class fm_prior_spec(C.Structure):
+    _fields_ = [('mod', fm_prior_mod * 3)]
+
+
 class FlowMolHipError(RuntimeError):
     pass
 
@@ -97,6 +110,8 @@ _EXPORTS = {
     'fm_remove_com': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'fm_set_molecule_ids': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'fm_prior_philox': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    'fm_prior_philox_dense': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fm_prior_spec), C.POINTER(fm_dense_state)]),
+    'fm_philox_tape': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_step_scalars), C.POINTER(fm_step_noise)]),
     'fm_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_void_p, C.POINTER(fm_dst), C.c_int, C.c_int,
                              C.POINTER(fm_dst)]),
     'fm_forward_dense': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_dense_state), C.c_void_p, C.c_int, C.POINTER(fm_dst)]),

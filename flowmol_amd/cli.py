@@ -2,7 +2,7 @@
 
     python -m flowmol_amd.cli --model_dir <dir> | --checkpoint <ckpt> | --preset flowmol3
         [--n_mols 100] [--n_atoms_per_mol N] [--n_timesteps 250] [--max_batch_size 128]
-        [--xt_traj] [--ep_traj] [--stochasticity eta] [--hc_thresh p] [--seed s] [--output_file out.sdf]
+        [--xt_traj] [--ep_traj] [--stochasticity eta] [--hc_thresh p] [--seed s] [--rng torch|philox] [--output_file out.sdf]
 
 Under ``torchrun --nproc-per-node N`` the molecules of every batch are sharded over the N GPUs of the node
 (``FlowMol.sample_distributed``: one RCCL all-gather per batch) and rank 0 writes the files.
@@ -49,6 +49,9 @@ def parse_args(argv=None):
     p.add_argument('--stochasticity', type=float, default=None)
     p.add_argument('--hc_thresh', type=float, default=None)
     p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--rng', choices=('torch', 'philox'), default='torch',
+                   help="(not a reference flag) noise source: torch = the reference's draws from torch's generator (default); philox = per-molecule counter-based "
+                        "streams inside the kernels, keyed by --seed and the molecule's index in the run: a molecule's result does not depend on batch size or GPU count")
     p.add_argument('--device', type=str, default='cuda:0')
     args = p.parse_args(argv)
     if sum(x is not None for x in (args.model_dir, args.checkpoint, args.preset)) != 1:
@@ -129,13 +132,18 @@ def run(args, engine_lib=None):
     model = load_model(args, engine_lib).to(args.device).eval()
     molecules = []
     n_batches = math.ceil(args.n_mols / args.max_batch_size)
+    philox = getattr(args, 'rng', 'torch') == 'philox'
+    if philox:      # one seed for the whole run (--seed, else one draw from torch's generator); molecule i of the run owns stream i whatever its batch
+        philox_seed = args.seed if args.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
     start = time.time()
     for b in range(n_batches):
         bs = min(args.n_mols - len(molecules), args.max_batch_size)
         common = dict(n_timesteps=args.n_timesteps, stochasticity=args.stochasticity, high_confidence_threshold=args.hc_thresh)
         n_atoms = model.sample_n_atoms(bs) if args.n_atoms_per_mol is None else torch.full((bs,), args.n_atoms_per_mol, dtype=torch.long)
+        if philox:
+            common.update(seed=philox_seed, mol_ids=torch.arange(len(molecules), len(molecules) + bs))
         if world == 0:
-            molecules.extend(model.sample(n_atoms, device=args.device, xt_traj=args.xt_traj, ep_traj=args.ep_traj, **common))
+            molecules.extend(model.sample(n_atoms, device=args.device, xt_traj=args.xt_traj, ep_traj=args.ep_traj, **({'rng': 'philox'} if philox else {}), **common))
         else:
             # every rank must shard the SAME size list: rank 0's draw is broadcast; noise streams differ per rank
             import torch.distributed as dist
@@ -143,7 +151,7 @@ def run(args, engine_lib=None):
             dist.broadcast(nb, src=0)
             if args.seed is not None:
                 torch.manual_seed(args.seed + 7919 * (b + 1) + rank)
-            molecules.extend(model.sample_distributed(nb.cpu(), xt_traj=args.xt_traj, ep_traj=args.ep_traj, **common))      # trajectories: a second gather of the frames
+            molecules.extend(model.sample_distributed(nb.cpu(), xt_traj=args.xt_traj, ep_traj=args.ep_traj, **({'noise': 'philox'} if philox else {}), **common))      # trajectories: a second gather of the frames
     sampling_time = time.time() - start
     if rank != 0:            # every rank holds the gathered batch; rank 0 writes
         return molecules, sampling_time

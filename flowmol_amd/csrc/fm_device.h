@@ -972,6 +972,17 @@ __device__ __forceinline__ void fm_row_stats8(const float* row, int n, int sub, 
 // Counter-based noise for sharded sampling (SURVEY.md §8e "performance mode"): Philox4x32-10 keyed by the run's seed, counter =
 // (global molecule id, row inside the molecule, step * 4 + modality, draw block).  A molecule's draws depend on nothing else,
 // so its trajectory is the same on 1 or 8 GPUs, in any batch composition; no noise tensors exist in HBM.
+// STREAM LAYOUT -- counter (c0, c1, c2, c3) = (global molecule id, row inside the molecule: atom or unordered pair, c2, block); every entry is disjoint from the others,
+// and an existing entry never moves (tests/golden/philox_streams_v7.npz pins the first three):
+//   c2 = step * 4 + job (job 0 / 1 / 2 = a / c / e), campbell step:  blocks 0..3 = the row's K <= 16 Exp(1) draws of the categorical sample (draw k = word k % 4 of block
+//        k / 4, fm_exp1); block 4 words 0, 1 = the uniforms u1 (unmask), u2 (re-mask) (fm_u01)
+//   c2 = step * 4 + job, gat step:  blocks 0..3 = the row's K + 1 <= 16 Exp(1) draws over the classes incl. the mask, same word order (a plan is campbell OR gat, so the
+//        two never share a run; fm_k_ctmc_gat_fused)
+//   c2 = 0xFFFFFFFF, position prior:  block 0 of atom c1 = Box-Muller on (fm_exp1(w0), fm_u01(w1)) -> x, y and (fm_exp1(w2), fm_u01(w3)) -> z (fm_prior_x_molecule)
+//   c2 = 0xFFFFFFFE - job, categorical priors of endpoint models (fm_k_prior_philox_dense):  blocks 0..3 = the row's d <= 16 NORMAL draws, the position prior's Box-Muller,
+//        block b -> normals 4b..4b+3 = r0 cos t0, r0 sin t0, r1 cos t1, r1 sin t1 (normal j belongs to category j; every prior kind that needs normals reads these);
+//        blocks 4..7 = the row's d Exp(1) draws (uniform simplex; Exp race of marginal / c-given-a), same word order as the CTMC draws
+// (step * 4 + job reaches 0xFFFFFFFC only after 2^30 steps.)  fm_philox_tape writes a step's draws out through the same functions.
 struct FmPhilox4 { unsigned v[4]; };
 __device__ __forceinline__ FmPhilox4 fm_philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
 #pragma unroll

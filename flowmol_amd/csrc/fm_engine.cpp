@@ -496,8 +496,23 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
         {b.N, c->nc, dst->c, b.node_mol, state->c_t, (smp && smp->c1) ? smp->c1 : c->sc1, nz->q_c, nz->u1_c, nz->u2_c},
         {b.U, c->ne, dst->e, b.pair_mol, state->e_t, (smp && smp->e1) ? smp->e1 : c->se1, nz->q_e, nz->u1_e, nz->u2_e},
     };
-    if (sc->dfm_type == FM_DFM_GAT && (sc->noise_mode == FM_NOISE_PHILOX || !nz->q_a))
-        return fail(c, FM_ERR_INVALID, "fm_ctmc_step: dfm_type 'gat' needs the caller's noise tensors");
+    if (sc->dfm_type == FM_DFM_GAT && sc->noise_mode == FM_NOISE_PHILOX) {      // in-kernel noise: the whole step in one launch (fm_k_ctmc_gat_fused)
+        FmGatFusedArgs f{};
+        const int* offs[3] = {b.mol_node_off, b.mol_node_off, b.mol_pair_off};
+        for (int m = 0; m < 3; ++m) {
+            FmGatMod& d = f.mod[m];
+            d.K = mods[m].K; d.p = mods[m].p; d.xt = mods[m].xt; d.x1 = mods[m].x1; d.off = offs[m]; d.cf = sc->gat_cf[m]; d.cb = sc->gat_cb[m];
+            d.sink_t = frame ? (m == 0 ? frame->a : m == 1 ? frame->c : frame->e) : nullptr;
+        }
+        f.temp = sc->cat_temperature; f.fw = sc->gat_fw; f.bw = sc->gat_bw; f.dt_cat = sc->dt;
+        f.x_t = state->x_t; f.x1 = dst->x; f.node_off = b.mol_node_off; f.coef = sc->x_coef; f.dt = sc->dt; f.scale = sc->x_scale;
+        f.x_raw = x_raw; f.x1_out = dst->x;
+        if (frame) { f.sink_x = frame->x; f.sink_x1 = frame->x1; }
+        f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->mol_gid;
+        launch_inst(L, ctmc_gat_instances(), {c->plan.ctmc_threads}, "ctmc", dim3(b.B, 4), dim3(c->plan.ctmc_threads), 0, f);
+        return L.rc;
+    }
+    if (sc->dfm_type == FM_DFM_GAT && !nz->q_a) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
     if (sc->dfm_type == FM_DFM_GAT) {
         L("x_step", fm_k_x_step, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3);
         for (int m = 0; m < 3; ++m) {
@@ -557,6 +572,7 @@ int validate(const fm_config& cf) {
     auto rg_tile = [](int t) { return t == 4 || t == 8 || t == 12 || t == 20; };
     if (!tile_ok(cf.tile_edge) || !(tile_ok(cf.tile_node) || rg_tile(cf.tile_node)))
         return fail(nullptr, FM_ERR_INVALID, "fm_create: fm_config.tile_edge must be 0 (automatic), 16, 32 or 64; tile_node additionally 4, 8, 12 or 20");
+    if (cf.ctmc_threads != 0 && cf.ctmc_threads != 256 && cf.ctmc_threads != 1024) return fail(nullptr, FM_ERR_INVALID, "fm_create: fm_config.ctmc_threads must be 0 (automatic), 256 or 1024");
     return FM_OK;
 }
 
@@ -937,7 +953,9 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     // CTMC: a few molecules: 1024-thread workgroups (one per molecule and modality is all the parallelism there is) -- and batches whose LARGEST molecule has
     // more than 4096 pairs (n >= 92): its pair rows are one workgroup's serial loop, 35 rounds of 256 threads at 134 atoms (GEOM size distribution: 135 us of a
     // 67.8-ms step against 39 us at 1024 x 47 atoms); else 256.  Same arithmetic either way (integer counts, per-row decisions).
-    p.ctmc_threads = (B * 4 <= n_cus && nmax > 23) || nmax >= 92 ? 1024 : 256;
+    // The fused gat kernel (fm_k_ctmc_gat_fused) has the same shape -- one workgroup per (molecule, modality), a serial loop over its rows -- and takes the
+    // same choice.  fm_config.ctmc_threads (256 | 1024) forces a size.
+    p.ctmc_threads = cf.ctmc_threads ? cf.ctmc_threads : (B * 4 <= n_cus && nmax > 23) || nmax >= 92 ? 1024 : 256;
     return FM_OK;
 }
 
@@ -1093,6 +1111,50 @@ int fm_prior_philox(fm_ctx* c, void* stream, uint64_t seed, float* x0) {
     return L.rc;
 }
 
+int fm_prior_philox_dense(fm_ctx* c, void* stream, uint64_t seed, const fm_prior_spec* spec, const fm_dense_state* out) {
+    if (!c || !spec || !out || !out->x_t || !out->a_t || !out->c_t || !out->e_t) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: null argument");
+    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_prior_philox_dense: no batch bound");
+    if (c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: this is a CTMC model (masked prior): use fm_prior_philox");
+    const FmBatch& b = c->b;
+    FmPriorDenseArgs a{};
+    const int d[3] = {c->na, c->nc, c->ne};
+    float* outs[3] = {out->a_t, out->c_t, out->e_t};
+    const int* offs[3] = {b.mol_node_off, b.mol_node_off, b.mol_pair_off};
+    static const char* const tag[3] = {"a", "c", "e"};
+    for (int m = 0; m < 3; ++m) {
+        const fm_prior_mod& s = spec->mod[m];
+        if (s.kind < FM_PRIOR_GAUSSIAN || s.kind > FM_PRIOR_C_GIVEN_A) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: unknown prior kind %d for modality %s", s.kind, tag[m]);
+        if (s.kind == FM_PRIOR_C_GIVEN_A && m != 1) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: the c-given-a prior is for modality c, not %s", tag[m]);
+        if ((s.kind == FM_PRIOR_MARGINAL || s.kind == FM_PRIOR_C_GIVEN_A) && !s.p) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: modality %s needs its distribution p", tag[m]);
+        if (s.kind == FM_PRIOR_BIASED_SIMPLEX && (d[m] < 2 || s.vertex_idx < 0 || s.vertex_idx >= d[m])) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: biased-simplex vertex_idx %d outside the %d categories of %s", s.vertex_idx, d[m], tag[m]);
+        FmPriorMod& k = a.mod[m];
+        k.kind = s.kind; k.d = d[m]; k.std = s.std; k.simplex_center = s.simplex_center; k.blur = s.blur; k.has_blur = s.has_blur;
+        k.vertex_prob = s.vertex_prob; k.vertex_idx = s.vertex_idx; k.p = s.p; k.out = outs[m]; k.off = offs[m];
+    }
+    a.x = out->x_t; a.node_off = b.mol_node_off; a.mol_gid = c->mol_gid;
+    a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
+    Launch L{c, (hipStream_t)stream};
+    L("prior_philox_dense", fm_k_prior_philox_dense, dim3(b.B, 4), dim3(256), 0, a);
+    return L.rc;
+}
+
+int fm_philox_tape(fm_ctx* c, void* stream, const fm_step_scalars* sc, const fm_step_noise* out) {
+    if (!c || !sc || !out || !out->q_a || !out->q_c || !out->q_e) return fail(c, FM_ERR_INVALID, "fm_philox_tape: null argument");
+    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_philox_tape: no batch bound");
+    if (sc->noise_mode != FM_NOISE_PHILOX) return fail(c, FM_ERR_INVALID, "fm_philox_tape: the step's noise_mode is not FM_NOISE_PHILOX");
+    if (sc->dfm_type != FM_DFM_CAMPBELL && sc->dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "fm_philox_tape: unknown dfm_type %d", sc->dfm_type);
+    const FmBatch& b = c->b;
+    FmTapeArgs a{};
+    auto w = [](const float* p) { return const_cast<float*>(p); };      // caller-owned output tensors travelling in the (read-only) noise struct
+    a.mod[0] = {c->na, b.mol_node_off, w(out->q_a), w(out->u1_a), w(out->u2_a)};
+    a.mod[1] = {c->nc, b.mol_node_off, w(out->q_c), w(out->u1_c), w(out->u2_c)};
+    a.mod[2] = {c->ne, b.mol_pair_off, w(out->q_e), w(out->u1_e), w(out->u2_e)};
+    a.gat = sc->dfm_type == FM_DFM_GAT; a.seed_lo = sc->philox_seed_lo; a.seed_hi = sc->philox_seed_hi; a.step = sc->step_index; a.mol_gid = c->mol_gid;
+    Launch L{c, (hipStream_t)stream};
+    L("philox_tape", fm_k_philox_tape, dim3(b.B, 3), dim3(256), 0, a);
+    return L.rc;
+}
+
 int fm_forward(fm_ctx* c, void* stream, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap, int remove_com,
                const fm_dst* out) {
     if (!c || !state || !temb || !out) return fail(c, FM_ERR_INVALID, "fm_forward: null argument");
@@ -1145,7 +1207,8 @@ int fm_integrate(fm_ctx* c, void* stream, const fm_state* state, int n_steps, co
         const fm_dst* out = cur == 0 ? dst_a : dst_b;
         const int boot = (!prev && steps[i].t == 0.0f) ? 1 : 0;      // prev is None and (t == 0).all(), vector_field.py:269-272
         // campbell steps: the COM removal of the endpoint positions runs inside the fused CTMC kernel (one launch and one copy less)
-        const bool defer_com = steps[i].dfm_type == FM_DFM_CAMPBELL;
+        // (so do gat steps with in-kernel noise: fm_k_ctmc_gat_fused shares the campbell kernel's position job)
+        const bool defer_com = steps[i].dfm_type == FM_DFM_CAMPBELL || (steps[i].dfm_type == FM_DFM_GAT && steps[i].noise_mode == FM_NOISE_PHILOX);
         // embedding tables of the next FM_TAB_SLOTS steps in one launch
         if (i % FM_TAB_SLOTS == 0) {
             const int nt = n_steps - i < FM_TAB_SLOTS ? n_steps - i : FM_TAB_SLOTS;
@@ -1166,10 +1229,10 @@ int fm_integrate(fm_ctx* c, void* stream, const fm_state* state, int n_steps, co
             frame.e = sink->e ? sink->e + (size_t)i * b.U : nullptr;
             frame.x1 = sink->x1 ? sink->x1 + (size_t)i * b.N * 3 : nullptr;
         }
-        const bool in_kernel = sink && steps[i].dfm_type == FM_DFM_CAMPBELL;
+        const bool in_kernel = sink && defer_com;      // the fused kernels write the frames too
         rc = ctmc_impl(c, st, state, out, noise ? &noise[i] : nullptr, &steps[i], &smp, defer_com ? c->xw : nullptr, in_kernel ? &frame : nullptr);
         if (rc) return rc;
-        if (sink && !in_kernel) {      // 'gat' steps (three small kernels): frames by copy
+        if (sink && !in_kernel) {      // tensor-noise 'gat' steps (three small kernels): frames by copy
             Launch L{c, st};
             L.copy(frame.x, state->x_t, frame.x ? (size_t)b.N * 12 : 0);
             L.copy(frame.a, state->a_t, frame.a ? (size_t)b.N * 4 : 0);

@@ -84,7 +84,7 @@ struct BatchPlan {
     bool small_node = false, small_pair = false;      // 16-row MLP / node_proj tiles on the node / pair side
     bool mlp4 = false;        // node-side MLPs on 4-row tiles (fm_k_mlp4)
     bool edge_head32 = false; // a separate edge head runs 32-row tiles
-    int ctmc_threads = 256;   // workgroup size of fm_k_ctmc_fused (256 | 1024)
+    int ctmc_threads = 256;   // workgroup size of fm_k_ctmc_fused and fm_k_ctmc_gat_fused (256 | 1024)
 };
 
 }  // namespace fmh
@@ -230,6 +230,13 @@ void launch_inst(Launch& L, const InstList<Fn>& list, const InstKey& key, const 
     for (int f = 0, nf = 1 + (int)std::count(list.key_names, list.key_names + strlen(list.key_names), ','); f < nf; ++f)
         n += snprintf(k + n, sizeof k - n, f ? ", %d" : "%d", key[f]);
     L.rc = fail(L.c, FM_ERR_INVALID, "no %s instance for (%s) = (%s)", name, list.key_names, k);
+}
+
+// fused gat step (fm_k_ctmc_gat_fused<NT>): no dynamic LDS; the workgroup size is BatchPlan::ctmc_threads
+using GatFusedFn = decltype(&fm_k_ctmc_gat_fused<256>);
+inline const InstList<GatFusedFn>& ctmc_gat_instances() {
+    static const InstList<GatFusedFn> list{"ctmc_threads", {{{256}, fm_k_ctmc_gat_fused<256>, 0}, {{1024}, fm_k_ctmc_gat_fused<1024>, 0}}};
+    return list;
 }
 
 // ---------------------------------------------------------------------------------------- launchers of the heavy kernel families (one translation unit each)

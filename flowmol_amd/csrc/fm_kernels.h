@@ -1600,12 +1600,9 @@ static __global__ void __launch_bounds__(256) fm_k_x_step(float* __restrict__ x_
 }
 
 // Position prior of the Philox mode: x0 ~ N(0, I) per atom from the molecule's own stream (Box-Muller on draw block
-// (atom, 0xFFFFFFFF, 0)), then minus the molecule's mean (priors.py:27-35) -- one 64-lane workgroup per molecule.
-static __global__ void __launch_bounds__(64) fm_k_prior_philox(float* __restrict__ x, const int* __restrict__ mol_node_off,
-                                                         const int* __restrict__ mol_gid, unsigned seed_lo, unsigned seed_hi) {
-    const int m = blockIdx.x, lane = threadIdx.x;
-    const int n0 = mol_node_off[m], n1 = mol_node_off[m + 1];
-    const unsigned gid = (unsigned)mol_gid[m];
+// (atom, 0xFFFFFFFF, 0)), then minus the molecule's mean (priors.py:27-35) -- the 64 lanes of ONE wave per molecule (shared by
+// fm_k_prior_philox and job 3 of fm_k_prior_philox_dense: one body, one rounding).
+__device__ __forceinline__ void fm_prior_x_molecule(float* __restrict__ x, int n0, int n1, unsigned gid, int lane, unsigned seed_lo, unsigned seed_hi) {
     float sx = 0.f, sy = 0.f, sz = 0.f;
     for (int n = n0 + lane; n < n1; n += 64) {
         const FmPhilox4 rn = fm_philox4x32(gid, (unsigned)(n - n0), 0xFFFFFFFFu, 0u, seed_lo, seed_hi);
@@ -1620,6 +1617,27 @@ static __global__ void __launch_bounds__(64) fm_k_prior_philox(float* __restrict
     const float inv = 1.0f / (float)(n1 - n0);
     sx *= inv; sy *= inv; sz *= inv;
     for (int n = n0 + lane; n < n1; n += 64) { x[n * 3] -= sx; x[n * 3 + 1] -= sy; x[n * 3 + 2] -= sz; }
+}
+static __global__ void __launch_bounds__(64) fm_k_prior_philox(float* __restrict__ x, const int* __restrict__ mol_node_off,
+                                                         const int* __restrict__ mol_gid, unsigned seed_lo, unsigned seed_hi) {
+    const int m = blockIdx.x;
+    fm_prior_x_molecule(x, mol_node_off[m], mol_node_off[m + 1], (unsigned)mol_gid[m], threadIdx.x, seed_lo, seed_hi);
+}
+
+// The n <= CAP Exp(1) draws of one row's stream: draw k is word k % 4 of block blk0 + k / 4 (fm_exp1).  The ONE place that maps a categorical draw to its
+// counter: the CTMC kernels, the dense prior and the noise tape (fm_k_philox_tape) all call it.
+template <int CAP>
+__device__ __forceinline__ void fm_philox_exp_row(float (&qv)[CAP], int n, unsigned gid, unsigned row, unsigned ctr2, unsigned blk0, unsigned seed_lo, unsigned seed_hi) {
+    for (int blk = 0; blk * 4 < n; ++blk) {
+        const FmPhilox4 rn = fm_philox4x32(gid, row, ctr2, blk0 + (unsigned)blk, seed_lo, seed_hi);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) qv[(blk * 4 + j) & (CAP - 1)] = fm_exp1(rn.v[j]);
+    }
+}
+// The two uniforms of a campbell row (unmask / re-mask thresholds): words 0, 1 of block 4, clear of the <= 16 categorical draws
+__device__ __forceinline__ void fm_philox_u_row(float& u1, float& u2, unsigned gid, unsigned row, unsigned ctr2, unsigned seed_lo, unsigned seed_hi) {
+    const FmPhilox4 rn = fm_philox4x32(gid, row, ctr2, 4u, seed_lo, seed_hi);
+    u1 = fm_u01(rn.v[0]); u2 = fm_u01(rn.v[1]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1658,38 +1676,25 @@ struct FmCtmcFusedArgs {
     float* sink_x; float* sink_x1;
 };
 
-// NT threads per workgroup: 256, or 1024 for batches of a few molecules -- there one workgroup per (molecule, modality) is all the parallelism the kernel has,
-// and a 47-atom molecule's 1081 pair rows are five dependent load-compute rounds of 256 threads but two of 1024 (one molecule: 13.9 -> 8 us per step)
-template <int NT>
-__global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
-    __shared__ int red[2][NT / 64];
-    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
-    if (job == 3) {
-        const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
-        if (a.x_raw) {
-            __shared__ float com[3];
-            if (tid < 64) {          // the 64-lane strided sum + xor tree of fm_k_remove_com: identical rounding
-                float sx = 0.f, sy = 0.f, sz = 0.f;
-                for (int n = n0 + tid; n < n1; n += 64) { sx += a.x_raw[n * 3]; sy += a.x_raw[n * 3 + 1]; sz += a.x_raw[n * 3 + 2]; }
+// Job 3 of the fused CTMC kernels (campbell: fm_k_ctmc_fused, gat: fm_k_ctmc_gat_fused): the Euler step of one molecule's positions, the deferred COM removal of
+// the raw endpoint positions and the trajectory-sink stores.  A: the kernel's argument struct (x_t, x1, node_off, coef, dt, scale, x_raw, x1_out, sink_x, sink_x1).
+template <int NT, class A>
+__device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
+    const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
+    if (a.x_raw) {
+        __shared__ float com[3];
+        if (tid < 64) {          // the 64-lane strided sum + xor tree of fm_k_remove_com: identical rounding
+            float sx = 0.f, sy = 0.f, sz = 0.f;
+            for (int n = n0 + tid; n < n1; n += 64) { sx += a.x_raw[n * 3]; sy += a.x_raw[n * 3 + 1]; sz += a.x_raw[n * 3 + 2]; }
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
-                const float inv = 1.0f / (float)(n1 - n0);
-                if (tid == 0) { com[0] = sx * inv; com[1] = sy * inv; com[2] = sz * inv; }
-            }
-            __syncthreads();
-            for (int i = n0 * 3 + tid; i < n1 * 3; i += NT) {
-                const float x1 = a.x_raw[i] - com[(i - n0 * 3) % 3];
-                a.x1_out[i] = x1;
-                const float vf = fm_mul_rn(a.coef, fm_sub_rn(x1, a.x_t[i]));
-                const float xn = fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale));
-                a.x_t[i] = xn;
-                if (a.sink_x) a.sink_x[i] = xn;
-                if (a.sink_x1) a.sink_x1[i] = x1;
-            }
-            return;
+            for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+            const float inv = 1.0f / (float)(n1 - n0);
+            if (tid == 0) { com[0] = sx * inv; com[1] = sy * inv; com[2] = sz * inv; }
         }
+        __syncthreads();
         for (int i = n0 * 3 + tid; i < n1 * 3; i += NT) {
-            const float x1 = a.x1[i];
+            const float x1 = a.x_raw[i] - com[(i - n0 * 3) % 3];
+            a.x1_out[i] = x1;
             const float vf = fm_mul_rn(a.coef, fm_sub_rn(x1, a.x_t[i]));
             const float xn = fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale));
             a.x_t[i] = xn;
@@ -1698,6 +1703,23 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
         }
         return;
     }
+    for (int i = n0 * 3 + tid; i < n1 * 3; i += NT) {
+        const float x1 = a.x1[i];
+        const float vf = fm_mul_rn(a.coef, fm_sub_rn(x1, a.x_t[i]));
+        const float xn = fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale));
+        a.x_t[i] = xn;
+        if (a.sink_x) a.sink_x[i] = xn;
+        if (a.sink_x1) a.sink_x1[i] = x1;
+    }
+}
+
+// NT threads per workgroup: 256, or 1024 for batches of a few molecules -- there one workgroup per (molecule, modality) is all the parallelism the kernel has,
+// and a 47-atom molecule's 1081 pair rows are five dependent load-compute rounds of 256 threads but two of 1024 (one molecule: 13.9 -> 8 us per step)
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
+    __shared__ int red[2][NT / 64];
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
     const FmCtmcMod md = a.mod[job];
     const int r0 = md.off[mol], r1 = md.off[mol + 1], K = md.K;
     const unsigned gid = a.philox ? (unsigned)a.mol_gid[mol] : 0u, ctr2 = (unsigned)a.step * 4u + (unsigned)job;
@@ -1705,11 +1727,7 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
     for (int i = r0 + tid; i < r1; i += NT) {
         float lp[16], qv[16];
         if (a.philox) {            // draws 0..K-1 of this row's stream: Exp(1) for the categorical sample
-            for (int blk = 0; blk * 4 < K; ++blk) {
-                const FmPhilox4 rn = fm_philox4x32(gid, (unsigned)(i - r0), ctr2, (unsigned)blk, a.seed_lo, a.seed_hi);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) qv[(blk * 4 + j) & 15] = fm_exp1(rn.v[j]);
-            }
+            fm_philox_exp_row(qv, K, gid, (unsigned)(i - r0), ctr2, 0u, a.seed_lo, a.seed_hi);
         } else {
             for (int k = 0; k < K; ++k) qv[k] = md.q[(size_t)i * K + k];
         }
@@ -1751,8 +1769,7 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
         const bool masked = tok == K;
         float u1, u2 = 1.f;
         if (a.philox) {            // draws 16, 17 of the row's stream (block 4), clear of the <= 16 categorical draws
-            const FmPhilox4 rn = fm_philox4x32(gid, (unsigned)(i - r0), ctr2, 4u, a.seed_lo, a.seed_hi);
-            u1 = fm_u01(rn.v[0]); u2 = fm_u01(rn.v[1]);
+            fm_philox_u_row(u1, u2, gid, (unsigned)(i - r0), ctr2, a.seed_lo, a.seed_hi);
         } else {
             u1 = md.u1[i];
             if (!a.last_step) u2 = md.u2[i];
@@ -1788,36 +1805,246 @@ struct FmGatArgs {
     float temp, cf, cb, fw, bw, dt;
 };
 
-static __global__ void __launch_bounds__(256) fm_k_ctmc_gat(FmGatArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.rows) return;
+// One row of the gat update: p (K) endpoint probabilities, tok the row's token, q(k) the k-th of the row's K+1 Exp(1) draws (a callable: the flat kernel reads
+// the draw from memory where it is used, the fused one from its registers) -> the new token (return value) and argmax(p~).
+// The one body of the flat tensor-noise kernel (fm_k_ctmc_gat) and the fused one (fm_k_ctmc_gat_fused): same never-contracted ops in the same order,
+// first-index ties, the reference's clamp.
+template <class Q>
+__device__ __forceinline__ int fm_gat_row(const float* __restrict__ p, int K, int tok, Q q, float temp, float cf, float cb, float fw, float bw, float dt, int& amax) {
     float lp[17];
     float mx = -INFINITY;
-    for (int k = 0; k < a.K; ++k) { lp[k] = fm_div_rn(logf(a.p[(size_t)i * a.K + k]), a.temp); mx = fmaxf(mx, lp[k]); }
+    for (int k = 0; k < K; ++k) { lp[k] = fm_div_rn(logf(p[k]), temp); mx = fmaxf(mx, lp[k]); }
     float sum = 0.f;
-    for (int k = 0; k < a.K; ++k) { lp[k] = expf(fm_sub_rn(lp[k], mx)); sum = fm_add_rn(sum, lp[k]); }
-    int amax = 0; float amaxv = -1.f;
-    for (int k = 0; k < a.K; ++k) { lp[k] = fm_div_rn(lp[k], sum); if (lp[k] > amaxv) { amaxv = lp[k]; amax = k; } }
-    lp[a.K] = 0.f;
-    const int tok = a.xt[i];
+    for (int k = 0; k < K; ++k) { lp[k] = expf(fm_sub_rn(lp[k], mx)); sum = fm_add_rn(sum, lp[k]); }
+    amax = 0; float amaxv = -1.f;
+    for (int k = 0; k < K; ++k) { lp[k] = fm_div_rn(lp[k], sum); if (lp[k] > amaxv) { amaxv = lp[k]; amax = k; } }
+    lp[K] = 0.f;
     float psum = 0.f;
-    for (int k = 0; k <= a.K; ++k) {
-        const float dx = (k == tok) ? 1.f : 0.f, dm = (k == a.K) ? 1.f : 0.f;
-        const float uf = fm_mul_rn(a.cf, fm_sub_rn(lp[k], dx));
-        const float ub = fm_mul_rn(a.cb, fm_sub_rn(dx, dm));
-        const float pv = fm_sub_rn(fm_mul_rn(a.fw, uf), fm_mul_rn(a.bw, ub));
-        float ps = fm_add_rn(dx, fm_mul_rn(a.dt, pv));
+    for (int k = 0; k <= K; ++k) {
+        const float dx = (k == tok) ? 1.f : 0.f, dm = (k == K) ? 1.f : 0.f;
+        const float uf = fm_mul_rn(cf, fm_sub_rn(lp[k], dx));
+        const float ub = fm_mul_rn(cb, fm_sub_rn(dx, dm));
+        const float pv = fm_sub_rn(fm_mul_rn(fw, uf), fm_mul_rn(bw, ub));
+        float ps = fm_add_rn(dx, fm_mul_rn(dt, pv));
         ps = fminf(fmaxf(ps, 1.0e-9f), 1.0f);
         lp[k] = ps;
         psum = fm_add_rn(psum, ps);
     }
     int best = 0; float bestv = -1.f;
-    for (int k = 0; k <= a.K; ++k) {
-        const float v = fm_div_rn(fm_div_rn(lp[k], psum), a.q[(size_t)i * (a.K + 1) + k]);
+    for (int k = 0; k <= K; ++k) {
+        const float v = fm_div_rn(fm_div_rn(lp[k], psum), q(k));
         if (v > bestv) { bestv = v; best = k; }
     }
+    return best;
+}
+
+static __global__ void __launch_bounds__(256) fm_k_ctmc_gat(FmGatArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.rows) return;
+    const float* qrow = a.q + (size_t)i * (a.K + 1);
+    int amax;
+    const int best = fm_gat_row(a.p + (size_t)i * a.K, a.K, a.xt[i], [qrow](int k) { return qrow[k]; }, a.temp, a.cf, a.cb, a.fw, a.bw, a.dt, amax);
     a.xt[i] = best;
     a.x1[i] = amax;
+}
+
+// The whole gat update of one integration step in ONE launch with in-kernel noise (FM_NOISE_PHILOX), on fm_k_ctmc_fused's footing: grid (B, 4), one workgroup
+// per (molecule, job); jobs 0..2 = modality a / c / e over the molecule's contiguous rows, job 3 = fm_ctmc_x_job (Euler step, deferred COM removal, position
+// frames).  A row's K + 1 Exp(1) draws are draws 0..K of its stream (global molecule id, row inside the molecule, step * 4 + job): fm_philox_exp_row, the
+// campbell kernel's convention (K + 1 <= 16: blocks 0..3).  The rows need no workgroup reduction; the only LDS is fm_ctmc_x_job's three floats.
+struct FmGatMod {
+    int K;
+    const float* p;                 // (rows,K)
+    int* xt; int* x1;               // (rows)
+    const int* off;                 // [B+1] first row of every molecule
+    float cf, cb;
+    int* sink_t;                    // trajectory sink: this step's frame of the new state tokens, null = off
+};
+struct FmGatFusedArgs {
+    FmGatMod mod[3];
+    float temp, fw, bw, dt_cat;
+    float* x_t; const float* x1; const int* node_off; float coef, dt, scale;     // fm_ctmc_x_job
+    unsigned seed_lo, seed_hi; int step; const int* mol_gid;
+    const float* x_raw; float* x1_out;
+    float* sink_x; float* sink_x1;
+};
+
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_gat_fused(FmGatFusedArgs a) {
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
+    const FmGatMod md = a.mod[job];
+    const int r0 = md.off[mol], r1 = md.off[mol + 1], K = md.K;
+    const unsigned gid = (unsigned)a.mol_gid[mol], ctr2 = (unsigned)a.step * 4u + (unsigned)job;
+    for (int i = r0 + tid; i < r1; i += NT) {
+        float q[16];
+        fm_philox_exp_row(q, K + 1, gid, (unsigned)(i - r0), ctr2, 0u, a.seed_lo, a.seed_hi);
+        int amax;
+        const int best = fm_gat_row(md.p + (size_t)i * K, K, md.xt[i], [&q](int k) { return q[k & 15]; }, a.temp, md.cf, md.cb, a.fw, a.bw, a.dt_cat, amax);
+        md.xt[i] = best;
+        md.x1[i] = amax;
+        if (md.sink_t) md.sink_t[i] = best;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Noise tape (fm_philox_tape): the draws the in-kernel mode consumes in one step, written out in the reference's shapes and order -- campbell: q (rows,K),
+// u1, u2 (rows); gat: q (rows,K+1) -- through the SAME device functions and counters as the kernels above, so that the tensor-noise path fed with the tape
+// reproduces a Philox run bit for bit.  Grid (B, 3); off the hot path.
+// ------------------------------------------------------------------------------------------------
+struct FmTapeMod { int K; const int* off; float* q; float* u1; float* u2; };
+struct FmTapeArgs { FmTapeMod mod[3]; int gat; unsigned seed_lo, seed_hi; int step; const int* mol_gid; };
+
+static __global__ void __launch_bounds__(256) fm_k_philox_tape(FmTapeArgs a) {
+    const int mol = blockIdx.x, job = blockIdx.y;
+    const FmTapeMod md = a.mod[job];
+    const int r0 = md.off[mol], r1 = md.off[mol + 1], nq = md.K + (a.gat ? 1 : 0);
+    const unsigned gid = (unsigned)a.mol_gid[mol], ctr2 = (unsigned)a.step * 4u + (unsigned)job;
+    for (int i = r0 + (int)threadIdx.x; i < r1; i += 256) {
+        float q[16];
+        fm_philox_exp_row(q, nq, gid, (unsigned)(i - r0), ctr2, 0u, a.seed_lo, a.seed_hi);
+        for (int k = 0; k < nq; ++k) md.q[(size_t)i * nq + k] = q[k & 15];
+        if (!a.gat) {
+            float u1, u2;
+            fm_philox_u_row(u1, u2, gid, (unsigned)(i - r0), ctr2, a.seed_lo, a.seed_hi);
+            if (md.u1) md.u1[i] = u1;
+            if (md.u2) md.u2[i] = u2;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Priors of the endpoint-parameterised models from the per-molecule Philox streams (fm_prior_philox_dense; reference flowmol/data_processing/priors.py:8-107 as
+// FlowMol.sample_prior calls them, flowmol.py:417-448).  Grid (B, 4): jobs 0..2 = a_0 / c_0 / e_0 over the molecule's rows (e: unordered pairs), job 3 = the
+// position prior (fm_prior_x_molecule: fm_prior_philox's bits).  Stream of a row: counter (global molecule id, row, 0xFFFFFFFE - job, block);
+//   blocks 0..3: the row's d <= 16 NORMAL draws, normal j for category j -- the position prior's Box-Muller, block b gives normals 4b..4b+3 =
+//                r0 cos t0, r0 sin t0, r1 cos t1, r1 sin t1 with r = sqrt(2 exp1(word 0 | 2)), t = 2 pi u01(word 1 | 3);
+//   blocks 4..7: the row's d Exp(1) draws (fm_philox_exp_row): the uniform simplex, and the Exp race argmax((p_k / sum p) / q_k) of marginal / c-given-a.
+// Every kind that needs normals reads the same ones, so the gaussian kind with std = 1 returns the normals any other kind of that seed consumed.
+// ------------------------------------------------------------------------------------------------
+enum { FM_PK_GAUSSIAN = 0, FM_PK_UNIFORM_SIMPLEX = 1, FM_PK_BARYCENTER = 2, FM_PK_BIASED_SIMPLEX = 3, FM_PK_MARGINAL = 4, FM_PK_C_GIVEN_A = 5 };
+struct FmPriorMod {
+    int kind, d;
+    float std; int simplex_center;
+    float blur; int has_blur;
+    float vertex_prob; int vertex_idx;
+    const float* p;                 // marginal: (d); c-given-a: (n_atom_types, d)
+    float* out;                     // (rows, d)
+    const int* off;                 // [B+1]
+};
+struct FmPriorDenseArgs { FmPriorMod mod[3]; float* x; const int* node_off; const int* mol_gid; unsigned seed_lo, seed_hi; };
+
+__device__ __forceinline__ void fm_philox_normal_row(float (&g)[16], int d, unsigned gid, unsigned row, unsigned ctr2, unsigned seed_lo, unsigned seed_hi) {
+    for (int blk = 0; blk * 4 < d; ++blk) {
+        const FmPhilox4 rn = fm_philox4x32(gid, row, ctr2, (unsigned)blk, seed_lo, seed_hi);
+        const float r0 = sqrtf(2.0f * fm_exp1(rn.v[0])), r1 = sqrtf(2.0f * fm_exp1(rn.v[2]));
+        const float t0 = 6.283185307179586f * fm_u01(rn.v[1]), t1 = 6.283185307179586f * fm_u01(rn.v[3]);
+        g[(blk * 4) & 15] = r0 * cosf(t0); g[(blk * 4 + 1) & 15] = r0 * sinf(t0);
+        g[(blk * 4 + 2) & 15] = r1 * cosf(t1); g[(blk * 4 + 3) & 15] = r1 * sinf(t1);
+    }
+}
+
+// softmax(v / (1/d)) over d values in place (priors.py:55, :78, :97: F.softmax(x / (1/d), dim=1)); IEEE division and expf as in the CTMC kernels
+__device__ __forceinline__ void fm_prior_softmax(float (&v)[16], int d) {
+    const float inv_d = 1.0f / (float)d;
+    float mx = -INFINITY;
+    for (int k = 0; k < d; ++k) { v[k] = fm_div_rn(v[k], inv_d); mx = fmaxf(mx, v[k]); }
+    float sum = 0.f;
+    for (int k = 0; k < d; ++k) { v[k] = expf(fm_sub_rn(v[k], mx)); sum = fm_add_rn(sum, v[k]); }
+    for (int k = 0; k < d; ++k) v[k] = fm_div_rn(v[k], sum);
+}
+
+// Euclidean projection onto the simplex (the host simplex_projection of flowmol_amd/model.py; reference flowmol/utils/dirflow.py:35-49): u = v sorted descending,
+// c_j = (sum_{i<=j} u_i - 1) / j, rho = #{j : u_j > c_j}, result max(v - c_rho, 0).  d <= 16 values sorted by insertion in registers.
+__device__ __forceinline__ void fm_simplex_projection(float (&v)[16], int d) {
+    float u[16];
+    for (int k = 0; k < d; ++k) {
+        const float x = v[k];
+        int j = k;
+        while (j > 0 && u[j - 1] < x) { u[j] = u[j - 1]; --j; }
+        u[j] = x;
+    }
+    float cs = 0.f, tau = 0.f;
+    int rho = 0;
+    float c[16];
+    for (int k = 0; k < d; ++k) {
+        cs = fm_add_rn(cs, u[k]);
+        c[k] = fm_div_rn(fm_sub_rn(cs, 1.0f), (float)(k + 1));
+        rho += (u[k] > c[k]) ? 1 : 0;
+    }
+    tau = c[(rho > 0 ? rho : d) - 1];      // rho >= 1 for finite input (u_1 > u_1 - 1); rho = 0 (NaN input): torch.gather(c, rho - 1) reads the last column
+    for (int k = 0; k < d; ++k) v[k] = fmaxf(fm_sub_rn(v[k], tau), 0.f);
+}
+
+// one row of one categorical prior -> v[0..d-1].  a_row: the atom-type prior of the same node (c-given-a only)
+__device__ __forceinline__ void fm_prior_row(const FmPriorMod& md, float (&v)[16], unsigned gid, unsigned row, unsigned ctr2, unsigned seed_lo, unsigned seed_hi,
+                                             const float* a_row, int na) {
+    const int d = md.d;
+    float g[16];
+    const bool blur = md.has_blur != 0;
+    const bool normals = md.kind == FM_PK_GAUSSIAN || md.kind == FM_PK_BIASED_SIMPLEX || (md.kind == FM_PK_BARYCENTER && md.blur != 0.0f)
+                         || ((md.kind == FM_PK_MARGINAL || md.kind == FM_PK_C_GIVEN_A) && blur);
+    if (normals) fm_philox_normal_row(g, d, gid, row, ctr2, seed_lo, seed_hi);
+    if (md.kind == FM_PK_GAUSSIAN) {              // priors.py:8-13: randn * std (+ 1/d)
+        const float ctr = (float)(1.0 / (double)d);
+        for (int k = 0; k < d; ++k) { v[k] = fm_mul_rn(g[k], md.std); if (md.simplex_center) v[k] = fm_add_rn(v[k], ctr); }
+    } else if (md.kind == FM_PK_UNIFORM_SIMPLEX) {      // priors.py:15-22: Exp(1) draws over their sum
+        float q[16];
+        fm_philox_exp_row(q, d, gid, row, ctr2, 4u, seed_lo, seed_hi);
+        float sum = 0.f;
+        for (int k = 0; k < d; ++k) sum = fm_add_rn(sum, q[k]);
+        for (int k = 0; k < d; ++k) v[k] = fm_div_rn(q[k], sum);
+    } else if (md.kind == FM_PK_BARYCENTER) {           // priors.py:36-44
+        const float b = 1.0f / (float)d;
+        for (int k = 0; k < d; ++k) v[k] = b;
+        if (md.blur != 0.0f) {
+            for (int k = 0; k < d; ++k) v[k] = fm_add_rn(b, fm_mul_rn(g[k], md.blur));
+            fm_simplex_projection(v, d);
+        }
+    } else if (md.kind == FM_PK_BIASED_SIMPLEX) {       // priors.py:47-56
+        const float rest = fm_div_rn(fm_sub_rn(1.0f, md.vertex_prob), (float)(d - 1));
+        for (int k = 0; k < d; ++k) v[k] = fm_add_rn(k == md.vertex_idx ? md.vertex_prob : rest, fm_mul_rn(g[k], md.std));
+        fm_prior_softmax(v, d);
+    } else {                                            // marginal (priors.py:67-79) / c-given-a (:81-98): Exp race, one-hot, optional blur
+        const float* p = md.p;
+        if (md.kind == FM_PK_C_GIVEN_A) {
+            int am = 0; float av = a_row[0];
+            for (int k = 1; k < na; ++k) if (a_row[k] > av) { av = a_row[k]; am = k; }
+            p += (size_t)am * d;
+        }
+        float q[16];
+        fm_philox_exp_row(q, d, gid, row, ctr2, 4u, seed_lo, seed_hi);
+        float psum = 0.f;
+        for (int k = 0; k < d; ++k) psum = fm_add_rn(psum, p[k]);
+        int best = 0; float bestv = -1.f;
+        for (int k = 0; k < d; ++k) {
+            const float w = fm_div_rn(fm_div_rn(p[k], psum), q[k]);
+            if (w > bestv) { bestv = w; best = k; }
+        }
+        for (int k = 0; k < d; ++k) v[k] = (k == best) ? 1.f : 0.f;
+        if (blur) {
+            for (int k = 0; k < d; ++k) v[k] = fm_add_rn(v[k], fm_mul_rn(g[k], md.blur));
+            fm_prior_softmax(v, d);
+        }
+    }
+}
+
+static __global__ void __launch_bounds__(256) fm_k_prior_philox_dense(FmPriorDenseArgs a) {
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    const unsigned gid = (unsigned)a.mol_gid[mol];
+    if (job == 3) {
+        if (tid < 64) fm_prior_x_molecule(a.x, a.node_off[mol], a.node_off[mol + 1], gid, tid, a.seed_lo, a.seed_hi);
+        return;
+    }
+    const FmPriorMod md = a.mod[job];
+    const int r0 = md.off[mol], r1 = md.off[mol + 1];
+    for (int i = r0 + tid; i < r1; i += 256) {
+        float v[16], av[16];
+        if (md.kind == FM_PK_C_GIVEN_A)       // the charge prior is conditioned on the atom-type prior of the same node: recomputed here (same stream, same bits as job 0)
+            fm_prior_row(a.mod[0], av, gid, (unsigned)(i - r0), 0xFFFFFFFEu, a.seed_lo, a.seed_hi, nullptr, 0);
+        fm_prior_row(md, v, gid, (unsigned)(i - r0), 0xFFFFFFFEu - (unsigned)job, a.seed_lo, a.seed_hi, av, a.mod[0].d);
+        for (int k = 0; k < md.d; ++k) md.out[(size_t)i * md.d + k] = v[k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

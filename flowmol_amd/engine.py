@@ -15,8 +15,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 
 from . import _lib
-from ._lib import (FM_DFM_CAMPBELL, FM_DFM_GAT, FM_NOISE_PHILOX, FlowMolHipError, fm_dense_state, fm_endpoint_scalars, fm_config, fm_dst, fm_sampled, fm_state, fm_step_noise, fm_step_scalars,
-                   fm_tensor_desc, fm_traj_sink)
+from ._lib import (FM_DFM_CAMPBELL, FM_DFM_GAT, FM_NOISE_PHILOX, FlowMolHipError, fm_dense_state, fm_endpoint_scalars, fm_config, fm_dst, fm_prior_spec, fm_sampled, fm_state, fm_step_noise,
+                   fm_step_scalars, fm_tensor_desc, fm_traj_sink)
 from .config import VFConfig
 from .weights import check_state_dict, state_dict_shapes
 
@@ -135,9 +135,7 @@ def make_step_plan(n_timesteps: int, eta: float, hc_thresh: float, cat_temperatu
                 sc.gat_cf[k] = float(ap_i[k + 1] / (1 - a_i[k + 1]))
                 sc.gat_cb[k] = float(ap_i[k + 1] / (a_i[k + 1] + 1e-8))
             sc.gat_fw, sc.gat_bw = _f32(fw), _f32(bw)
-        if philox_seed is not None:        # noise drawn inside the CTMC kernel from per-molecule counter-based streams (fm_noise_mode)
-            if dfm_type != 'campbell':
-                raise NotImplementedError("the in-kernel Philox noise covers dfm_type='campbell'")
+        if philox_seed is not None:        # noise drawn inside the CTMC kernel from per-molecule counter-based streams (fm_noise_mode), campbell and gat
             sc.noise_mode = FM_NOISE_PHILOX
             sc.step_index = s_idx - 1
             sc.philox_seed_lo, sc.philox_seed_hi = philox_seed & 0xffffffff, (philox_seed >> 32) & 0xffffffff
@@ -209,8 +207,8 @@ class Engine:
         GEMMs on the bf16 matrix cores: faster, ~10x larger per-stage error, never used for parity claims) or 'bf16x6' (OPT-IN three-term split of the
         edge-message GEMMs only: f32-class accuracy on the bf16 matrix cores; round 5's measurement of whether that beats the f32 roof).  It is an explicit argument
         only -- no environment variable changes what an Engine computes -- and is recorded in ``self.precision``.
-        ``tuning``: launch-tuning overrides of fm_config (ABI 5 / 6: tile_edge, tile_node, tile_edge_update, xcd_swizzle, fuse_node, pair_mlps, pair_slab,
-        mlp_small_tiles; 0 / absent = automatic) for A/B measurements and the parity tests that run every tile size."""
+        ``tuning``: launch-tuning overrides of fm_config (ABI 5 / 6 / 8: tile_edge, tile_node, tile_edge_update, xcd_swizzle, fuse_node, pair_mlps, pair_slab,
+        mlp_small_tiles, ctmc_threads; 0 / absent = automatic) for A/B measurements and the parity tests that run every tile size."""
         precision = precision or 'f32'
         if precision not in ('f32', 'bf16x3', 'bf16x6', 'f16x3'):
             raise ValueError(f"precision must be 'f32', 'bf16x3', 'bf16x6' or 'f16x3', got {precision!r}")
@@ -401,6 +399,66 @@ class Engine:
         with self._dev():
             self._check(self.lib.fm_prior_philox(self._ctx, self._stream(), C.c_uint64(seed), _ptr(x0)), 'fm_prior_philox')
         return x0
+
+    def prior_philox_dense(self, seed: int, prior_types: Optional[Dict[str, str]] = None, prior_kwargs: Optional[Dict[str, dict]] = None,
+                           default_p: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The whole prior of an endpoint-parameterised model for the bound batch from the per-molecule Philox streams, in one launch
+        (fm_prior_philox_dense): a dense state dict x_t (N,3) = ``prior_philox(seed)``'s bits, a_t (N,na), c_t (N,nc), e_t (U,ne) per unordered pair.
+        ``prior_types`` / ``prior_kwargs`` (default: the model's config) name the reference's prior functions and their keyword arguments
+        (priors.py:8-107); 'marginal' / 'c-given-a' take ``p`` / ``p_c_given_a`` from the kwargs or, when absent, from ``default_p`` (keys 'a', 'c', 'e')."""
+        cfg, d = self.cfg, self.device
+        types = prior_types if prior_types is not None else cfg.prior_types
+        kws = prior_kwargs if prior_kwargs is not None else cfg.prior_kwargs
+        spec, keep = fm_prior_spec(), []
+        for i, (tag, width) in enumerate((('a', cfg.n_atom_types), ('c', cfg.n_charges), ('e', cfg.n_bond_types))):
+            kind, kw, m = types[tag], kws.get(tag, {}) or {}, spec.mod[i]
+            if kind not in _lib.FM_PRIOR_KINDS:
+                raise NotImplementedError(f'prior type {kind!r}')
+            m.kind = _lib.FM_PRIOR_KINDS[kind]
+            m.std = float(kw.get('std', 0.2 if kind == 'biased-simplex' else 1.0))
+            m.simplex_center = int(bool(kw.get('simplex_center', False)))
+            m.has_blur = int(kw.get('blur') is not None)
+            m.blur = float(kw.get('blur') or 0.0)
+            m.vertex_prob, m.vertex_idx = float(kw.get('vertex_prob', 0.75)), int(kw.get('vertex_idx', 0))
+            if kind in ('marginal', 'c-given-a'):
+                key = 'p' if kind == 'marginal' else 'p_c_given_a'
+                p = kw.get(key, (default_p or {}).get(tag))
+                if p is None:
+                    raise ValueError(f"prior {kind!r} needs kwargs[{key!r}] (or a dataset whose shipped marginals have {width} categories)")
+                p = torch.as_tensor(p, dtype=torch.float32).to(d).contiguous()          # uploaded once per call
+                want = (width,) if kind == 'marginal' else (cfg.n_atom_types, width)
+                if tuple(p.shape) != want:
+                    raise ValueError(f"prior {kind!r}: distribution has shape {tuple(p.shape)}, the model needs {want}")
+                keep.append(p)
+                m.p = _ptr(p)
+        st = {'x_t': torch.empty(self.N, 3, device=d), 'a_t': torch.empty(self.N, cfg.n_atom_types, device=d),
+              'c_t': torch.empty(self.N, cfg.n_charges, device=d), 'e_t': torch.empty(self.U, cfg.n_bond_types, device=d)}
+        ds = self._dense_struct(st)
+        with self._dev():
+            self._check(self.lib.fm_prior_philox_dense(self._ctx, self._stream(), C.c_uint64(seed), C.byref(spec), C.byref(ds)), 'fm_prior_philox_dense')
+        self._keep = [keep, st]
+        return st
+
+    def philox_tape(self, plan: "StepPlan", step: int) -> "StepNoise":
+        """The draws the in-kernel noise mode consumes in step ``step`` of a Philox ``plan`` for the bound batch (and its molecule ids), as the tensors
+        the reference draws (fm_philox_tape): campbell q_* (rows,K), u1_*, u2_* (u2 absent on the last step, as in ``StepNoise.draw``); gat q_* (rows,K+1).
+        Fed back through the tensor-noise path -- or to the reference's integrate in place of its RNG -- it replays the Philox run."""
+        sc = plan.scalars[step]
+        if sc.noise_mode != FM_NOISE_PHILOX:
+            raise ValueError('philox_tape needs a plan made with philox_seed')
+        cfg, d = self.cfg, self.device
+        gat = sc.dfm_type == FM_DFM_GAT
+        out = {}
+        for tag, rows, k in (('a', self.N, cfg.n_atom_types), ('c', self.N, cfg.n_charges), ('e', self.U, cfg.n_bond_types)):
+            out[f'q_{tag}'] = torch.empty(rows, k + 1 if gat else k, device=d)
+            if not gat:
+                out[f'u1_{tag}'] = torch.empty(rows, device=d)
+                out[f'u2_{tag}'] = None if sc.last_step else torch.empty(rows, device=d)
+        nz = StepNoise(**out)
+        cs = nz.c_struct()
+        with self._dev():
+            self._check(self.lib.fm_philox_tape(self._ctx, self._stream(), C.byref(sc), C.byref(cs)), 'fm_philox_tape')
+        return nz
 
     def stability(self, state, table: torch.Tensor, fake_atom_token: int = -1, explicit_aromaticity: bool = False) -> torch.Tensor:
         """Valence stability + connectivity of the bound batch's molecules from their tokens, on the device

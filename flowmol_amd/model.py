@@ -228,6 +228,7 @@ class FlowMol:
         ``noise='philox'`` (performance mode): prior and CTMC noise are drawn INSIDE the kernels from per-molecule Philox4x32-10
         streams keyed by (seed, original molecule index, step, modality): no noise tensors at all, and every molecule's
         trajectory is the same for any world size or batch composition -- bit for bit with canonical arithmetic (the default).
+        It covers every model family: campbell and gat CTMC steps, and the priors of endpoint-parameterised models.
 
         Everything one ``sample()`` call of the reference takes (flowmol.py:489-493) shards too: ``prior`` (a reference-format prior dict of the WHOLE
         batch: every rank keeps its molecules' rows, flowmol.py:534-545) and ``xt_traj`` / ``ep_traj`` (flowmol.py:564-589, test.py:212-257): each rank
@@ -254,10 +255,14 @@ class FlowMol:
         if noise == 'philox':
             # performance mode of SURVEY.md section 8e: per-molecule counter-based streams keyed by (seed, ORIGINAL molecule index, step,
             # modality); rank 0's seed is broadcast; nothing but the shard's own noise is generated, and it is generated in-kernel
-            seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64)
-            sd = seed.to(dev if dist.get_backend(group) == 'nccl' else 'cpu')
-            dist.broadcast(sd, src=0, group=group)
-            kwargs.update(rng='philox', _philox=int(sd.item()), _mol_ids=parts[rank])
+            # ``seed=`` / ``mol_ids=`` (the same on every rank; ids of the WHOLE batch, default 0..B-1) fix the streams from outside
+            if kwargs.get('seed') is None:
+                seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64)
+                sd = seed.to(dev if dist.get_backend(group) == 'nccl' else 'cpu')
+                dist.broadcast(sd, src=0, group=group)
+                kwargs['seed'] = int(sd.item())
+            ids = kwargs.get('mol_ids')
+            kwargs.update(rng='philox', mol_ids=parts[rank] if ids is None else torch.as_tensor(ids)[parts[rank]])
         local_frames = None
         if len(parts[rank]):
             got = self.sample(n_atoms[parts[rank]], n_timesteps=n_timesteps, return_tensors='device', xt_traj=visualize, _frames=visualize, **kwargs)   # stays in HBM
@@ -287,7 +292,13 @@ class FlowMol:
 
         RNG use mirrors the reference: ``randn(N,3)`` on the device for the position prior, then per step
         and per modality (a, c, e) ``Exp(1)`` of shape (rows, K), ``rand(rows)``, ``rand(rows)`` (the last
-        one skipped on the final step)."""
+        one skipped on the final step).
+
+        ``rng='philox'`` instead draws the prior and every step's noise inside the kernels from per-molecule counter-based streams
+        (campbell and gat steps, and the priors of endpoint-parameterised models): no noise tensors, and a molecule's result depends only on
+        ``seed=`` (default: one draw from torch's CPU generator) and on its id in ``mol_ids=`` (default 0..B-1), not on its batch.  So
+        ``model.sample(n_atoms[i:i+1], rng='philox', seed=s, mol_ids=[i])`` regenerates molecule *i* of an earlier
+        ``model.sample(n_atoms, rng='philox', seed=s)`` on its own, bit for bit with canonical arithmetic (the default)."""
         if device is not None and torch.device(device) != self.device:
             self.to(device)
         eng = self.engine
@@ -299,7 +310,7 @@ class FlowMol:
         dfm_type = kwargs.get('dfm_type') or self.cfg.dfm_type
         if dfm_type not in ('campbell', 'gat'):
             raise ValueError(f"Invalid dfm_type: {dfm_type}")
-        unknown = set(kwargs) - {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', '_rows', '_noise_for_step', 'rng', '_philox', '_mol_ids', '_frames'}
+        unknown = set(kwargs) - {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', '_rows', '_noise_for_step', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids', '_frames'}
         if unknown:
             raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
         visualize = bool(xt_traj or ep_traj)
@@ -316,12 +327,9 @@ class FlowMol:
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
         philox_seed = None
         if rng == 'philox':
-            if dfm_type != 'campbell' or rows is not None or kwargs.get('_noise_for_step') is not None:
-                raise NotImplementedError("rng='philox' covers the default campbell integrator")
-            philox_seed = kwargs.get('_philox')
-            if philox_seed is None:                       # one 62-bit seed per call from torch's CPU generator: torch.manual_seed controls it
-                philox_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            eng.set_molecule_ids(kwargs.get('_mol_ids'))
+            if rows is not None or kwargs.get('_noise_for_step') is not None:
+                raise NotImplementedError("rng='philox' draws inside the kernels: it does not combine with replicated row slicing (_rows) or a noise callback (_noise_for_step)")
+            philox_seed = self._philox_setup(kwargs)
         if prior is None and philox_seed is not None:
             state = eng.prior_state(eng.prior_philox(philox_seed))
         elif prior is None:
@@ -374,6 +382,15 @@ class FlowMol:
         mols = self._package(out, n_atoms, frames, xt_traj, ep_traj)
         self.last_timing['package'] = time.perf_counter() - t2
         return mols
+
+    def _philox_setup(self, kwargs) -> int:
+        """Seed and molecule ids of a Philox run: ``seed`` / ``mol_ids`` (``_philox`` / ``_mol_ids`` are their earlier, private spellings)."""
+        seed = kwargs.get('seed') if kwargs.get('seed') is not None else kwargs.get('_philox')
+        if seed is None:                              # one 62-bit seed per call from torch's CPU generator: torch.manual_seed controls it
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        ids = kwargs.get('mol_ids') if kwargs.get('mol_ids') is not None else kwargs.get('_mol_ids')
+        self.engine.set_molecule_ids(None if ids is None else torch.as_tensor(ids))
+        return int(seed)
 
     # ------------------------------------------------------------------ endpoint-parameterised models
     @staticmethod
@@ -433,18 +450,28 @@ class FlowMol:
         """FlowMol.sample for parameterization='endpoint' (flowmol.py:489-589 with EndpointVectorField.integrate, vector_field.py:388-499):
         the categorical modalities are continuous vectors integrated with the same Euler step as the positions; the sampled
         molecule takes their argmax.  RNG order = the reference's: randn(N,3) on the device, then a, c, e priors on the CPU generator."""
-        if kwargs.get('rng', 'torch') != 'torch' or '_philox' in kwargs:
-            raise NotImplementedError("per-molecule Philox noise covers CTMC models; endpoint models draw their priors with torch (noise='per_rank' / 'replicated')")
-        unknown = set(kwargs) - {'inv_temp_func', 'tspan', '_rows', 'rng', '_frames'}
+        rng = kwargs.get('rng', 'torch')
+        if rng not in ('torch', 'philox'):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        unknown = set(kwargs) - {'inv_temp_func', 'tspan', '_rows', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids', '_frames'}
         if unknown:
             raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
+        if rng == 'philox' and kwargs.get('_rows') is not None:
+            raise NotImplementedError("rng='philox' draws inside the kernels: it does not combine with replicated row slicing (_rows)")
         eng, cfg = self.engine, self.cfg
         dev = eng.device
         n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
         eng.bind(n_atoms)
         N, U = eng.N, eng.U
         rows = kwargs.get('_rows')      # sample_distributed(noise='replicated'): (N_full, U_full, node rows, pair rows) -- draw the full batch's priors, keep this shard's
-        if prior is None:
+        if prior is None and rng == 'philox':
+            # the whole prior in one launch from the per-molecule streams (fm_prior_philox_dense); the integration itself is deterministic
+            seed = self._philox_setup(kwargs)
+            ck = cfg.prior_types['c']
+            p0 = eng.prior_philox_dense(seed, default_p={'a': self._default_marginal('a', cfg.n_atom_types), 'e': self._default_marginal('e', cfg.n_bond_types),
+                                                         'c': self._default_marginal('c|a' if ck == 'c-given-a' else 'c', cfg.n_charges)})
+            x0, a0, c0, e0 = p0['x_t'], p0['a_t'], p0['c_t'], p0['e_t']
+        elif prior is None:
             nN, nU = (rows[0], rows[1]) if rows is not None else (N, U)
             x0 = torch.randn(nN, 3, device=dev)
             pk = cfg.prior_kwargs

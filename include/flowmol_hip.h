@@ -14,6 +14,10 @@
  *   fm_ctmc_step        the part of CTMCVectorField.step after the network evaluation,
  *                       ctmc_vector_field.py:328-411 + campbell_step :414-461 + purity_sampling ctmc_utils.py:4-34
  *   fm_integrate        CTMCVectorField.integrate, ctmc_vector_field.py:145-285
+ *   fm_prior_philox_dense   the categorical priors of flowmol/data_processing/priors.py:8-107 as FlowMol.sample_prior draws them
+ *                       (flowmol/models/flowmol.py:417-448), from per-molecule counter-based streams instead of the CPU generator
+ *   fm_philox_tape      the draws of CTMCVectorField.step's torch.multinomial / torch.rand calls (ctmc_vector_field.py:349-357,
+ *                       373-388, 414-510) as the in-kernel noise mode makes them, materialised in the reference's shapes
  *
  * Conventions
  *   - every function returns 0 on success or a negative fm_status; the message is available from
@@ -46,7 +50,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 7
+#define FM_ABI_VERSION 8
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -129,6 +133,9 @@ typedef struct fm_config {
      * -1: the pair slab follows the batch size (round 5's rule); results then agree between differently composed batches to f32 summation order only.  (Up to
      * round 5 this was a "latency mode" with its own 4-row kernels; since the 4-row kernels are canonical it gains nothing measurable: one molecule 0.55 vs 0.56 ms.) */
     int32_t canonical;
+    /* --- ABI 8: workgroup size of the fused CTMC kernels (campbell and gat): 0 = per batch (1024 for a few molecules or a very large one, else 256) | 256 | 1024.
+     * Same bits either way (per-row decisions, integer counts); exists for the parity tests that run both instances on small batches. */
+    int32_t ctmc_threads;
 } fm_config;
 
 enum fm_precision { FM_PREC_F32 = 0, FM_PREC_BF16X3 = 1, FM_PREC_BF16X6 = 2, FM_PREC_F16X3 = 3 };
@@ -193,10 +200,11 @@ typedef struct fm_step_scalars {  /* host-computed with the reference's float32 
     float gat_cf[3];              /* a, c, e: alpha'/(1 - alpha)        (gat_step, ctmc_vector_field.py:481) */
     float gat_cb[3];              /* a, c, e: alpha'/(alpha + 1e-8)     (:488) */
     float gat_fw, gat_bw;         /* forward_weight_func(t_i) and forward_weight - 1 (:491-492) */
-    /* --- ABI 3: noise source of this step (campbell only).  FM_NOISE_TENSORS: the caller's fm_step_noise (the reference's draws,
+    /* --- ABI 3: noise source of this step (campbell; since ABI 8 also gat).  FM_NOISE_TENSORS: the caller's fm_step_noise (the reference's draws,
      * bit-exact parity mode).  FM_NOISE_PHILOX: drawn inside the kernel from Philox4x32-10 streams keyed by (philox_seed, global
      * molecule id, step_index, modality, row) -- no noise tensors, and a molecule's trajectory does not depend on how the
-     * batch is sharded; fm_step_noise may then be NULL */
+     * batch is sharded; fm_step_noise may then be NULL.  A gat step with FM_NOISE_PHILOX is ONE launch (Euler step, the three
+     * modalities, trajectory frames) instead of four; its K+1 Exp(1) draws per row are draws 0..K of the row's stream (fm_philox_tape writes them out) */
     int32_t noise_mode;
     int32_t step_index;
     uint32_t philox_seed_lo, philox_seed_hi;
@@ -212,6 +220,28 @@ typedef struct fm_traj_sink {     /* optional per-step frames (xt_traj / ep_traj
     float* x;  int32_t* a;  int32_t* c;  int32_t* e;             /* (n_steps, ...) state after each step */
     float* x1; int32_t* a1; int32_t* c1; int32_t* e1;            /* (n_steps, ...) endpoint predictions */
 } fm_traj_sink;
+
+/* --- ABI 8: categorical priors of the endpoint-parameterised models, one fm_prior_mod per modality (a, c, e).  Replaces the prior functions of
+ * flowmol/data_processing/priors.py as flowmol/models/flowmol.py:417-448 (FlowMol.sample_prior) calls them; the fields are their keyword arguments. */
+enum fm_prior_kind {
+    FM_PRIOR_GAUSSIAN = 0,        /* priors.py:8-13   gaussian: randn * std (+ 1/d when simplex_center) */
+    FM_PRIOR_UNIFORM_SIMPLEX = 1, /* priors.py:15-22  Exp(1) draws over their row sum */
+    FM_PRIOR_BARYCENTER = 2,      /* priors.py:36-44  1/d; blur != 0: simplex projection (flowmol/utils/dirflow.py:35-49) of 1/d + randn * blur */
+    FM_PRIOR_BIASED_SIMPLEX = 3,  /* priors.py:47-56  softmax((mu + randn * std) / (1/d)), mu = vertex_prob at vertex_idx, (1 - vertex_prob)/(d - 1) elsewhere */
+    FM_PRIOR_MARGINAL = 4,        /* priors.py:67-79  one-hot of a draw from p; has_blur: softmax((one_hot + randn * blur) / (1/d)) */
+    FM_PRIOR_C_GIVEN_A = 5        /* priors.py:81-98  the same with p = p_c_given_a[argmax of the node's atom-type prior]; modality c only */
+};
+typedef struct fm_prior_mod {
+    int32_t kind;                 /* fm_prior_kind */
+    float std;
+    int32_t simplex_center;
+    float blur;
+    int32_t has_blur;             /* marginal / c-given-a: blur given (the reference tests `blur is not None`) */
+    float vertex_prob;
+    int32_t vertex_idx;
+    const float* p;               /* DEVICE: marginal p (d) | c-given-a p_c_given_a (n_atom_types, d); else NULL */
+} fm_prior_mod;
+typedef struct fm_prior_spec { fm_prior_mod mod[3]; } fm_prior_spec;      /* a, c, e */
 
 const char* fm_last_error(const fm_ctx* ctx);
 int fm_abi_version(void);
@@ -234,6 +264,11 @@ int fm_remove_com(fm_ctx* ctx, void* stream, float* x);
 int fm_set_molecule_ids(fm_ctx* ctx, void* stream, const int32_t* ids_host);
 int fm_prior_philox(fm_ctx* ctx, void* stream, uint64_t seed, float* x0);
 
+/* Philox mode of the endpoint-parameterised models (has_mask == 0): the whole prior of the bound batch in one launch -- out->x_t = fm_prior_philox's
+ * bits, out->a_t / c_t / e_t (e per unordered pair) = the categorical priors of `spec` (priors.py:8-107 through flowmol.py:417-448), every row from the
+ * stream (global molecule id, row inside the molecule): normals and Exp(1) draws as laid out in csrc/fm_device.h (fm_philox4x32) and DESIGN.md section 6. */
+int fm_prior_philox_dense(fm_ctx* ctx, void* stream, uint64_t seed, const fm_prior_spec* spec, const fm_dense_state* out);
+
 /* one network evaluation.  temb: device (time_embedding_dim) floats (raw t when dim == 1).
  * prev: previous endpoint for self-conditioning or NULL.  bootstrap != 0 reproduces the reference's
  * first-step behaviour (vector_field.py:269-282): an extra evaluation with remove_com=False whose
@@ -250,6 +285,12 @@ int fm_endpoint_step(fm_ctx* ctx, void* stream, const fm_dense_state* state, con
 /* Euler step for x and the CTMC update of a, c, e given the endpoint prediction `dst` */
 int fm_ctmc_step(fm_ctx* ctx, void* stream, const fm_state* state, const fm_dst* dst,
                  const fm_step_noise* noise, const fm_step_scalars* sc, const fm_sampled* sampled);
+
+/* Noise tape: the draws a FM_NOISE_PHILOX step with these scalars (philox seed, step_index, dfm_type) consumes for the bound batch, written to the
+ * caller's tensors `out` in the reference's shapes and order (ctmc_vector_field.py:349-357 campbell: q (rows,K), u1, u2 (rows); :373-388 gat: q (rows,K+1);
+ * u1 / u2 pointers may be NULL).  Same device functions and counters as the kernels: fm_ctmc_step with FM_NOISE_TENSORS and this tape gives the
+ * FM_NOISE_PHILOX step's bits, and the reference's integrate fed with it replays the run. */
+int fm_philox_tape(fm_ctx* ctx, void* stream, const fm_step_scalars* sc, const fm_step_noise* out);
 
 /* n_steps Euler/CTMC steps: per step fm_forward (+bootstrap on step 0 for self-conditioned models when
  * steps[0].t == 0) then fm_ctmc_step.  temb: device (n_steps, time_embedding_dim); noise: host array of
