@@ -305,15 +305,37 @@ class Engine:
             torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------ batch
-    def bind(self, n_atoms: torch.Tensor):
-        """Bind a batch of molecules given their sizes (order preserved).  Replaces the reference's
-        dgl.graph / dgl.batch / upper-edge-mask / batch-index construction (flowmol.py:509-529)."""
-        n = n_atoms.detach().to('cpu', torch.int32).contiguous()
+    def workspace_need(self, n_atoms: torch.Tensor) -> int:
+        """Bytes of workspace a batch of these molecule sizes needs (fm_workspace_bytes)."""
+        n = torch.as_tensor(n_atoms).detach().to('cpu', torch.int32).contiguous()
         if n.dim() != 1 or n.numel() == 0:
             raise ValueError('n_atoms must be a non-empty 1-D tensor')
         need = C.c_size_t()
         self._check(self.lib.fm_workspace_bytes(self._ctx, C.c_void_p(n.data_ptr()), n.numel(), C.byref(need)), 'fm_workspace_bytes')
-        if self._ws is None or self._ws.numel() < need.value:
+        return int(need.value)
+
+    def bind(self, n_atoms: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+        """Bind a batch of molecules given their sizes (order preserved).  Replaces the reference's
+        dgl.graph / dgl.batch / upper-edge-mask / batch-index construction (flowmol.py:509-529).
+        ``workspace``: a caller-owned uint8 tensor on the engine's device, 256-byte aligned and of at least ``workspace_need(n_atoms)``
+        bytes, used as the batch's arena as it is (what fm_batch_bind takes in C).  The engine keeps a reference and never reallocates it: later
+        binds without ``workspace`` stay in it while it is large enough, and move to an allocation of the engine's own when it is not."""
+        n = n_atoms.detach().to('cpu', torch.int32).contiguous()
+        if n.dim() != 1 or n.numel() == 0:
+            raise ValueError('n_atoms must be a non-empty 1-D tensor')
+        need = C.c_size_t(self.workspace_need(n))
+        if workspace is not None:
+            if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+                raise ValueError('workspace must be a contiguous 1-D uint8 tensor')
+            if workspace.device != self.device and not (workspace.device.type == self.device.type == 'cuda' and
+                                                        workspace.device.index == (self.device.index or 0)):
+                raise ValueError(f'workspace must be on {self.device}, got {workspace.device}')
+            if workspace.data_ptr() % 256 != 0:
+                raise ValueError('workspace must be 256-byte aligned (data_ptr() % 256 == 0)')
+            if workspace.numel() < need.value:
+                raise ValueError(f'workspace has {workspace.numel()} bytes, the batch needs {need.value}')
+            self._ws = workspace
+        elif self._ws is None or self._ws.numel() < need.value + (-self._ws.data_ptr()) % 256:
             self._ws = None
             self._ws = torch.empty(need.value + 256, dtype=torch.uint8, device=self.device)
         base = self._ws.data_ptr()
@@ -334,6 +356,8 @@ class Engine:
         cnt = {'e_src': self.E, 'e_dst': self.E, 'e_pair': self.E, 'p_e0': self.U, 'p_e1': self.U,
                'node_mol': self.N, 'pair_mol': self.U}[name]
         out = torch.empty(cnt, dtype=torch.int32, device=self.device)
+        if cnt == 0:          # a batch without edges: nothing to copy (and an empty tensor has no pointer to pass)
+            return out
         with self._dev():
             self._check(self.lib.fm_batch_query(self._ctx, self._stream(), name.encode(), _ptr(out)), 'fm_batch_query')
         self.synchronize()
