@@ -83,6 +83,297 @@ def seeded_inputs(cfg, n_atoms, with_prev, seed=3, frac_masked=0.4):
     return {'batch': batch, 'x': x, 'a': a, 'c': c, 'eu': eu, 'prev': prev}
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# input regimes outside the Gaussian cloud of seeded_inputs (tests/test_input_regimes.py)
+REGIMES = ('base', 'coincident', 'nearclamp', 'stretched', 'translated', 'lattice', 'allmasked', 'unmasked_onehot_prev')
+NEARCLAMP_DELTAS = (3e-5, 9.9e-5, 1.01e-4, 3e-4, 1e-3)      # either side of fm_norm3's clamp at |dx|^2 = 1e-8, cycled over the molecules
+STRETCH_K = 0.35                                             # 'stretched': coordinates x STRETCH_K * cfg.rbf_dmax (regime_occupancy holds the shares it must give)
+TRANSLATION = (300.0, -200.0, 500.0)
+LATTICE_STEP = 1.5
+
+
+def _mol_offsets(n_atoms):
+    n = [int(v) for v in n_atoms.tolist()]
+    off = [0]
+    for v in n:
+        off.append(off[-1] + v)
+    return n, off[:-1]
+
+
+def regime_inputs(cfg, n_atoms, with_prev, regime, seed=3):
+    """seeded_inputs() moved into one of REGIMES: the same generator and draw order ('base' IS seeded_inputs, bit for bit), then a deterministic
+    edit of coordinates, tokens or the previous endpoint.  'r1+r2' applies two edits in turn.  regime_occupancy() asserts that the edit really put
+    the inputs where the regime's name says."""
+    parts = regime.split('+')
+    assert all(r in REGIMES for r in parts), regime
+    inp = seeded_inputs(cfg, n_atoms, with_prev, seed, 0.0 if 'unmasked_onehot_prev' in parts else 0.4)
+    for r in parts:
+        inp = _regime_edit(cfg, inp, r)
+    return inp
+
+
+def _regime_edit(cfg, inp, regime):
+    if regime == 'base':
+        return inp
+    x = inp['x'].clone()
+    prev = None if inp['prev'] is None else {k: v.clone() for k, v in inp['prev'].items()}
+    a, c, eu = inp['a'].clone(), inp['c'].clone(), inp['eu'].clone()
+    sizes, offs = _mol_offsets(inp['batch'].n_atoms)
+    if regime == 'coincident':
+        for n, o in zip(sizes, offs):
+            if n >= 2:
+                x[o + 1] = x[o]
+            if n >= 4:
+                x[o + 3] = x[o]
+        if prev is not None:
+            prev['x'][:sizes[0]] = x[:sizes[0]]
+    elif regime == 'nearclamp':
+        used = set()
+        for m, (n, o) in enumerate(zip(sizes, offs)):
+            if n >= 2:
+                d = NEARCLAMP_DELTAS[m % len(NEARCLAMP_DELTAS)]
+                x[o + 1] = x[o] + torch.tensor([d, 0.0, 0.0])
+                used.add(d)
+        # a batch of fewer than five molecules with a pair (e.g. [70, 47]) would see only the first deltas, all below the clamp: the deltas no molecule
+        # got go to further pairs (atom 2k + 1 := atom 2k + delta, k = 1, 2, ...) of the molecules in turn, so every batch straddles the clamp
+        left, k = [d for d in NEARCLAMP_DELTAS if d not in used], 1
+        while left and any(n >= 2 * k + 2 for n in sizes):
+            for n, o in zip(sizes, offs):
+                if left and n >= 2 * k + 2:
+                    x[o + 2 * k + 1] = x[o + 2 * k] + torch.tensor([left.pop(0), 0.0, 0.0])
+            k += 1
+    elif regime == 'stretched':
+        k = STRETCH_K * cfg.rbf_dmax
+        x = x * k
+        if prev is not None:
+            prev['x'] = prev['x'] * k
+    elif regime == 'translated':
+        s = torch.tensor(TRANSLATION)
+        x = x + s
+        if prev is not None:
+            prev['x'] = prev['x'] + s
+    elif regime == 'lattice':
+        for n, o in zip(sizes, offs):
+            i = torch.arange(n)
+            x[o:o + n] = LATTICE_STEP * torch.stack([i % 3, (i // 3) % 3, i // 9], dim=1).float()
+        if prev is not None:
+            prev['x'] = x.clone()
+    elif regime == 'allmasked':
+        a.fill_(cfg.n_atom_types)
+        c.fill_(cfg.n_charges)
+        eu.fill_(cfg.n_bond_types)
+    elif regime == 'unmasked_onehot_prev':
+        if prev is not None:
+            for k in 'ace':
+                prev[k] = F.one_hot(prev[k].argmax(-1), prev[k].shape[-1]).float()
+    return {'batch': inp['batch'], 'x': x, 'a': a, 'c': c, 'eu': eu, 'prev': prev}
+
+
+def _upper_pairs(batch):
+    m = batch.upper_edge_mask
+    return batch.src[m], batch.dst[m]
+
+
+def lattice_distance_bound(n):
+    """Distinct non-zero distances of the first n sites of the 3 x 3 x L lattice of regime 'lattice': 12 as long as L <= 3 (n <= 27; squared distances
+    (a^2 + b^2 + c^2) with a, b, c in {0, 1, 2} take 9 values).  A longer lattice adds at most the 6 values {0, 1, 2, 4, 5, 8} + c^2 per further layer
+    distance c, so a 33-atom molecule has 14: there the bound is 6 L, against n (n - 1) / 2 distinct distances in the Gaussian cloud."""
+    layers = -(-n // 9)
+    return 12 if layers <= 3 else 6 * layers
+
+
+def regime_occupancy(cfg, inp, regime, all_masked=False):
+    """The regime's occupancy condition, computed from the inputs alone in float32 as the kernels see them, ASSERTED -> the measured numbers."""
+    if '+' in regime:          # (with every token the mask, coincident atoms cannot differ in their tokens: that one condition is dropped by 'allmasked')
+        occ = {}
+        for r in regime.split('+'):
+            occ.update(regime_occupancy(cfg, inp, r, all_masked or 'allmasked' in regime.split('+')))
+        return occ
+    batch, x, prev = inp['batch'], inp['x'].float(), inp['prev']
+    sizes, offs = _mol_offsets(batch.n_atoms)
+    i, j = _upper_pairs(batch)
+    dx = x[i] - x[j]
+    d2 = (dx * dx).sum(-1)
+    occ = {'pairs': int(i.numel()), 'max_abs_x': float(x.abs().max())}
+    masks = {'a': cfg.n_atom_types, 'c': cfg.n_charges, 'e': cfg.n_bond_types}
+    tok = {'a': inp['a'], 'c': inp['c'], 'e': inp['eu']}
+    occ['masked_share'] = {k: float((tok[k] == masks[k]).float().mean()) if tok[k].numel() else 0.0 for k in 'ace'}
+    if regime == 'coincident':
+        zero = (dx == 0).all(-1)
+        occ['exact_zero_pairs'] = int(zero.sum())
+        need = sum(1 for n in sizes if n >= 2) + 2 * sum(1 for n in sizes if n >= 4)
+        assert occ['exact_zero_pairs'] >= need, (occ, need)
+        occ['coincident_pairs_with_different_tokens'] = int((zero & ((inp['a'][i] != inp['a'][j]) | (inp['c'][i] != inp['c'][j]))).sum())
+        assert occ['coincident_pairs_with_different_tokens'] >= 1 or all_masked, occ
+        if prev is not None:
+            occ['nodes_at_their_previous_endpoint'] = int((x == prev['x'].float()).all(-1).sum())
+            assert occ['nodes_at_their_previous_endpoint'] >= 1, occ
+    elif regime == 'nearclamp':
+        occ['pairs_below_clamp'] = int(((d2 > 0) & (d2 < 1e-8)).sum())
+        occ['pairs_just_above_clamp'] = int(((d2 > 1e-8) & (d2 < 1e-6)).sum())
+        assert occ['pairs_below_clamp'] >= 1 and occ['pairs_just_above_clamp'] >= 1, occ
+    elif regime == 'stretched':
+        d = cpu_ref.norm_no_nan(dx) + 1e-8
+        r = cpu_ref.rbf(d, D_max=cfg.rbf_dmax, D_count=cfg.rbf_dim)
+        assert r.dtype == torch.float32
+        tiny = float(torch.finfo(torch.float32).tiny)
+        occ['share_all_zero_rbf_rows'] = float((r == 0).all(-1).float().mean())
+        occ['share_below_rbf_dmax'] = float((d < cfg.rbf_dmax).float().mean())
+        occ['rows_with_a_denormal'] = int(((r > 0) & (r < tiny)).any(-1).sum())
+        occ['max_distance'] = float(d.max())
+        assert occ['share_all_zero_rbf_rows'] >= 0.2 and occ['share_below_rbf_dmax'] >= 0.2 and occ['rows_with_a_denormal'] >= 1, occ
+    elif regime == 'translated':
+        assert occ['max_abs_x'] > 400, occ
+    elif regime == 'lattice':
+        triples, worst = 0, 0
+        for n, o in zip(sizes, offs):
+            xm = x[o:o + n]
+            if n >= 3:
+                p, q, r_ = torch.combinations(torch.arange(n), 3).unbind(1)
+                cr = torch.linalg.cross(xm[q] - xm[p], xm[r_] - xm[p], dim=-1)
+                triples += int((cr == 0).all(-1).sum())
+            if n >= 2:
+                p, q = torch.combinations(torch.arange(n), 2).unbind(1)
+                distinct = int(torch.unique((xm[p] - xm[q]).pow(2).sum(-1).sqrt()).numel())
+                assert distinct <= lattice_distance_bound(n), (n, distinct)
+                worst = max(worst, distinct)
+        occ['exactly_collinear_triples'], occ['most_distinct_distances_in_a_molecule'] = triples, worst
+        assert triples >= 1, occ
+        assert prev is None or torch.equal(prev['x'], inp['x'])
+    elif regime == 'allmasked':
+        assert all(bool((tok[k] == masks[k]).all()) for k in 'ace'), occ
+    elif regime == 'unmasked_onehot_prev':
+        assert all(not bool((tok[k] == masks[k]).any()) for k in 'ace'), occ
+        if prev is not None:
+            for k in 'ace':
+                p = prev[k]
+                assert bool(((p == 1).sum(-1) == 1).all()) and bool(((p == 0).sum(-1) == p.shape[-1] - 1).all()), k
+    return occ
+
+
+def slice_molecule(inp, m):
+    """The inputs of molecule ``m`` of a batch as a one-molecule batch."""
+    n_atoms = inp['batch'].n_atoms
+    pr = n_atoms * (n_atoms - 1) // 2
+    no, po = int(n_atoms[:m].sum()), int(pr[:m].sum())
+    n, u = int(n_atoms[m]), int(pr[m])
+    prev = inp['prev']
+    if prev is not None:
+        prev = {k: (v[po:po + u] if k == 'e' else v[no:no + n]).clone() for k, v in prev.items()}
+    return {'batch': cpu_ref.build_batch(n_atoms[m:m + 1]), 'x': inp['x'][no:no + n].clone(), 'a': inp['a'][no:no + n].clone(), 'c': inp['c'][no:no + n].clone(),
+            'eu': inp['eu'][po:po + u].clone(), 'prev': prev}
+
+
+def seeded_rotation(seed=5, proper=True):
+    """A seeded orthogonal 3 x 3 matrix (float64, QR of a Gaussian matrix) with det = +1 (proper) or -1."""
+    q, r = torch.linalg.qr(torch.randn(3, 3, generator=torch.Generator().manual_seed(seed), dtype=torch.float64))
+    q = q * torch.sign(torch.diagonal(r))
+    if (torch.linalg.det(q) > 0) != proper:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def moved_inputs(inp, R, shift):
+    """x -> x R^T + shift for the coordinates and the previous endpoint (computed in float64, rounded once to float32)."""
+    f = lambda v: (v.double() @ R.T + shift).float()
+    prev = inp['prev']
+    return {**inp, 'x': f(inp['x']), 'prev': None if prev is None else {**prev, 'x': f(prev['x'])}}
+
+
+def moved_stages(st, R, shift):
+    """The stages of an evaluation as a rigid motion of its inputs must move them: scalars, probabilities and edge features unchanged, vector taps
+    (rows, 3, V) rotated, coordinate taps rotated and shifted, the COM-removed output and displacements rotated."""
+    out = {}
+    for k, v in st.items():
+        w = v.detach().cpu().double()
+        if k.endswith('.v'):
+            w = torch.einsum('ij,njv->niv', R, w)
+        elif k == 'out.x' or k.endswith('.dx'):
+            w = w @ R.T
+        elif k.endswith('.x'):
+            w = w @ R.T + shift
+        out[k] = w.to(v.dtype)
+    return out
+
+
+def relabelled_inputs(inp, seed=7):
+    """The same molecules with the atoms of each permuted (seeded) and the molecule order reversed -> (inputs, node_map, pair_map):
+    new node g' is old node node_map[g'], new upper-triangle pair row u' is old pair row pair_map[u']."""
+    gen = torch.Generator().manual_seed(seed)
+    sizes, offs = _mol_offsets(inp['batch'].n_atoms)
+    poff, acc = [], 0
+    for n in sizes:
+        poff.append(acc)
+        acc += n * (n - 1) // 2
+    node_map, pair_map = [], []
+    for m in reversed(range(len(sizes))):
+        n = sizes[m]
+        p = torch.randperm(n, generator=gen)
+        node_map.append(offs[m] + p)
+        if n >= 2:
+            k, l = torch.triu_indices(n, n, offset=1)
+            lo, hi = torch.minimum(p[k], p[l]), torch.maximum(p[k], p[l])
+            pair_map.append(poff[m] + lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))       # row of (lo, hi) in the row-major upper triangle
+    node_map = torch.cat(node_map)
+    pair_map = torch.cat(pair_map) if pair_map else torch.zeros(0, dtype=torch.int64)
+    prev = inp['prev']
+    if prev is not None:
+        prev = {k: (v[pair_map] if k == 'e' else v[node_map]).clone() for k, v in prev.items()}
+    new = {'batch': cpu_ref.build_batch(torch.tensor(list(reversed(sizes)))), 'x': inp['x'][node_map].clone(), 'a': inp['a'][node_map].clone(),
+           'c': inp['c'][node_map].clone(), 'eu': inp['eu'][pair_map].clone(), 'prev': prev}
+    return new, node_map, pair_map
+
+
+def relabelled_stages(st, batch, new_batch, node_map, pair_map):
+    """The stages of an evaluation (directed-edge rows in the REFERENCE's edge order, see to_reference_edge_order) as a relabelling must permute them."""
+    N = batch.N
+    ref = torch.full((N * N,), -1, dtype=torch.int64)
+    ref[batch.src * N + batch.dst] = torch.arange(batch.E)
+    edge_map = ref[node_map[new_batch.src] * N + node_map[new_batch.dst]]
+    assert (edge_map >= 0).all()
+    out = {}
+    for k, v in st.items():
+        rows = pair_map if k == 'out.e' else edge_map if (k.endswith('.ef') or '.msg.' in k) else node_map
+        out[k] = v.detach().cpu()[rows]
+    return out
+
+
+def to_reference_edge_order(st, perm):
+    """Engine stages with the directed-edge rows brought from the engine's destination-major order into the reference's (perm = edge_perm())."""
+    out = {}
+    for k, v in st.items():
+        v = v.detach().cpu()
+        if k.endswith('.ef') or '.msg.' in k:
+            w = torch.empty_like(v)
+            w[perm] = v
+            v = w
+        out[k] = v
+    return out
+
+
+def stage_sensitivity(cfg, sd, inp, t_val):
+    """The oracle's own f32-vs-f64 discrepancy of every stage parity_stages() can name, of the outputs and of the displacement stages on ``inp``, and the
+    displacement gates of dx_gates() from the same two oracle runs -> ({stage: discrepancy}, {dx stage: gate})."""
+    lo, hi = _oracle_f32_f64(cfg, sd, None, t_val, None, inp=inp)
+    rel = lambda k: float((lo[k].double() - hi[k]).abs().max() / hi[k].abs().max().clamp(min=1e-30))
+    sens = {}
+    for k, tap in parity_stages(cfg, t_val, inp['prev'] is not None).items():
+        if tap in lo:
+            sens[k] = rel(tap)
+    for k in lo:
+        if k.startswith('out.') or k.endswith('.dx'):
+            sens[k] = rel(k)
+    return sens, _dx_gates_from(lo, hi)[0]
+
+
+def regime_tolerance(k, sens, dx_gate=None, stage_tol=STAGE_TOL, out_tol=OUT_TOL):
+    """Gate of one stage in the regime tests: the fixed tolerance of the parity tests or DX_SENS_FACTOR x the oracle's own rounding sensitivity of that
+    stage on the same inputs, whichever is larger; displacement stages keep the gate of dx_gates()."""
+    if k.endswith('.dx'):
+        return dx_gate[k]
+    return max(stage_tolerance(k, None, stage_tol, out_tol), DX_SENS_FACTOR * sens[k])
+
+
 def oracle_run(orc, cfg, inp, t_val, dtype=torch.float32):
     """One evaluation of the oracle on seeded_inputs() with every tap recorded -> (taps, outputs)."""
     batch, prev = inp['batch'], inp['prev']
@@ -186,17 +477,14 @@ def out_of_tolerance(errs, dx_gate=None, stage_tol=STAGE_TOL, out_tol=OUT_TOL):
     return {k: v for k, v in errs.items() if not v < stage_tolerance(k, dx_gate, stage_tol, out_tol)}
 
 
-def forward_compare(eng, orc, cfg, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4, taps=True, dtype=torch.float32, dx=False):
-    """Returns {stage: relative error (max abs diff / max abs ref)} for every tap and the outputs.  dtype = torch.float64 with an oracle whose
-    parameters are float64 (oracle_f64): the kernels' error against the EXACT result instead of against the f32 reference arithmetic.
-    dx: also the displacement stages (add_dx_stages), whose gate is dx_gates() -- meaningful under visible_weights()."""
+def engine_stages(eng, cfg, inp, t_val, taps=True):
+    """One instrumented evaluation of the engine on ``inp`` (seeded_inputs / regime_inputs; the engine is bound to inp's batch here) ->
+    ({stage: tensor} with every tap of parity_stages() and the outputs as 'out.x|a|c|e', the stages, the outputs)."""
     dev = eng.device
-    eng.bind(n_atoms)
-    inp = seeded_inputs(cfg, n_atoms, with_prev, seed, frac_masked)
     batch, x, a, c, eu, prev = inp['batch'], inp['x'], inp['a'], inp['c'], inp['eu'], inp['prev']
+    eng.bind(batch.n_atoms)
     N, U, E = eng.N, eng.U, eng.E
     assert (N, U) == (x.shape[0], eu.shape[0])
-    taps_o, ref = oracle_run(orc, cfg, inp, t_val, dtype)
     state = eng.make_state(x, a, c, eu)
     V = cfg.n_vec_channels
     bufs = {}
@@ -222,10 +510,21 @@ def forward_compare(eng, orc, cfg, n_atoms, t_val, with_prev, seed=3, frac_maske
     last_ef_tapped = f'upd{cfg.n_convs - 1}.ef' in bufs          # (recycled stacks tap every pass's rows: the tap un-fuses the last pass on purpose)
     assert (eng.profile_get('edge_update_head')[1] > 0) == (fused_head and not last_ef_tapped), 'the instrumented pass must run the kernels the plain pass runs'
     eng.profile(False)
-    perm = edge_perm(eng, batch) if taps else None
     got = dict(bufs)
     for k in 'xace':
         got['out.' + k] = out[k]
+    return got, stages, out
+
+
+def forward_compare(eng, orc, cfg, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4, taps=True, dtype=torch.float32, dx=False, inp=None):
+    """Returns {stage: relative error (max abs diff / max abs ref)} for every tap and the outputs.  dtype = torch.float64 with an oracle whose
+    parameters are float64 (oracle_f64): the kernels' error against the EXACT result instead of against the f32 reference arithmetic.
+    dx: also the displacement stages (add_dx_stages), whose gate is dx_gates() -- meaningful under visible_weights().
+    inp: these inputs (regime_inputs) instead of seeded_inputs(cfg, n_atoms, with_prev, seed, frac_masked)."""
+    inp = inp or seeded_inputs(cfg, n_atoms, with_prev, seed, frac_masked)
+    taps_o, ref = oracle_run(orc, cfg, inp, t_val, dtype)
+    got, stages, out = engine_stages(eng, cfg, inp, t_val, taps)
+    perm = edge_perm(eng, inp['batch']) if taps else None
     want = oracle_stage_tensors(taps_o, ref, stages, perm)
     if dx:
         add_dx_stages(got, cfg, inp)
@@ -251,11 +550,11 @@ def _oracle_f32_f64(cfg, sd, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4,
     return res[torch.float32], res[torch.float64]
 
 
-def oracle_rounding_sensitivity(cfg, sd, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4):
+def oracle_rounding_sensitivity(cfg, sd, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4, inp=None):
     """How far the reference arithmetic itself moves when only its rounding changes: the oracle in float32 against the oracle in float64 on
     the inputs forward_compare() uses (same generator order).  {stage: max |f32 - f64| / max |f64|} for every tap, output and displacement stage --
     the yardstick for kernel errors in ill-conditioned regimes (large weights), where a fixed tolerance says nothing."""
-    lo, hi = _oracle_f32_f64(cfg, sd, n_atoms, t_val, with_prev, seed, frac_masked)
+    lo, hi = _oracle_f32_f64(cfg, sd, n_atoms, t_val, with_prev, seed, frac_masked, inp)
     return {k: float((lo[k].double() - hi[k]).abs().max() / hi[k].abs().max().clamp(min=1e-30)) for k in hi if k in lo}
 
 
@@ -268,7 +567,10 @@ def dx_gates(cfg, sd, n_atoms, t_val, with_prev, seed=3, frac_masked=0.4, inp=No
     """Gate of every displacement stage, measured on the reference arithmetic alone: max(DX_SENS_FACTOR x the oracle's own f32-vs-f64 discrepancy of that
     stage, DX_FLOOR_ULPS x ulp(max|x|) / max|ref dx|) -- the second term is what subtracting two f32 coordinate taps can resolve at all.
     -> ({stage: gate}, {stage: {'f32_vs_f64', 'floor', 'dx_over_x'}})."""
-    lo, hi = _oracle_f32_f64(cfg, sd, n_atoms, t_val, with_prev, seed, frac_masked, inp)
+    return _dx_gates_from(*_oracle_f32_f64(cfg, sd, n_atoms, t_val, with_prev, seed, frac_masked, inp))
+
+
+def _dx_gates_from(lo, hi):
     gate, detail = {}, {}
     for k in lo:
         if not k.endswith('.dx'):
