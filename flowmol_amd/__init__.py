@@ -9,6 +9,7 @@ Drop-in surface of the reference package for that path (reference flowmol/__init
 from .config import VFConfig
 from .model import FlowMol, load_pretrained, pretrained_model_names, read_checkpoint
 from .molecule import SampledMolecule
+from .sampling_queue import SamplingQueue
 
-__all__ = ['FlowMol', 'SampledMolecule', 'VFConfig', 'load_pretrained', 'pretrained_model_names', 'read_checkpoint']
+__all__ = ['FlowMol', 'SampledMolecule', 'SamplingQueue', 'VFConfig', 'load_pretrained', 'pretrained_model_names', 'read_checkpoint']
 __version__ = '0.1.0'

@@ -11,11 +11,12 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 8
+FM_ABI_VERSION = 9
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
 FM_MAX_CONVS = 16
+FM_TAB_SLOTS = 32      # embedding tables per bound batch = the most time groups of a mixed-time call
 # fm_prior_kind, by the reference's prior names (flowmol/data_processing/priors.py)
 FM_PRIOR_KINDS = {'gaussian': 0, 'uniform-simplex': 1, 'barycenter': 2, 'biased-simplex': 3, 'marginal': 4, 'c-given-a': 5}
 
@@ -121,6 +122,12 @@ _EXPORTS = {
     'fm_integrate': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_int, C.POINTER(fm_step_scalars), C.c_void_p,
                                C.POINTER(fm_step_noise), C.POINTER(fm_dst), C.POINTER(fm_dst), C.POINTER(fm_dst), C.POINTER(fm_traj_sink),
                                C.POINTER(C.c_int)]),
+    # ABI 9: per-molecule time
+    'fm_forward_mixed': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fm_dst), C.c_int, C.c_int,
+                                   C.POINTER(fm_dst)]),
+    'fm_integrate_mixed': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_int, C.c_int, C.POINTER(fm_step_scalars), C.c_void_p,
+                                     C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_dst), C.POINTER(fm_dst), C.POINTER(fm_dst),
+                                     C.POINTER(fm_traj_sink), C.POINTER(C.c_int)]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

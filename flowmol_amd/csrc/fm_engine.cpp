@@ -290,6 +290,7 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
     } else if (prev) {
         FmMlpArgs a = ma;
         a.s_tab = c->s_tab; a.tok_a = state->a_t; a.tok_c = state->c_t; a.n_c1 = nc1;
+        a.tab_slot = c->tab_slot; a.node_mol = b.node_mol; a.slot_rows = (int)(c->tab_slot_floats / 256);
         a.prev_a = prev->a; a.prev_c = prev->c; a.prev_x = prev->x; a.x_t = state->x_t;
         a.out = c->s;
         FmMlpArgs e = ma;
@@ -303,7 +304,7 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
         }
         FmMlp4Args a4{};
         a4.N = N; a4.W1q = c->sc_node_W1q; a4.b1 = c->sc_node.b1; a4.W2q = c->sc_node_W2q; a4.b2 = c->sc_node.b2;
-        a4.s_tab = a.s_tab; a4.tok_a = a.tok_a; a4.tok_c = a.tok_c; a4.n_c1 = nc1; a4.prev_a = a.prev_a; a4.prev_c = a.prev_c; a4.prev_x = a.prev_x; a4.x_t = a.x_t;
+        a4.s_tab = a.s_tab; a4.tok_a = a.tok_a; a4.tok_c = a.tok_c; a4.n_c1 = nc1; a4.tab_slot = a.tab_slot; a4.node_mol = a.node_mol; a4.slot_rows = a.slot_rows; a4.prev_a = a.prev_a; a4.prev_c = a.prev_c; a4.prev_x = a.prev_x; a4.x_t = a.x_t;
         a4.na = c->na; a4.nc = c->nc; a4.rbf_mu_step = c->rbf_mu_step; a4.rbf_inv_sigma = c->rbf_inv_sigma; a4.out = c->s;
         // one row per unordered pair, written to both directed edges; with the pair slab the edge kernel is matrix-pipe work followed by 3 KB of row
         // stores per pair: 32-row tiles (38 KB of LDS) put four independent workgroups on a CU instead of two, so that one's stores overlap the others' GEMMs
@@ -312,9 +313,9 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
         tap("sc.ef", c->ef, (size_t)E * 128 * 4);
     } else {
         L("gather_s", fm_k_gather_rows, dim3(std::min(2048, (N * 64 + 255) / 256)), dim3(256), 0, c->s, (const float*)c->s_tab, 256, N,
-          (const int*)state->a_t, (const int*)state->c_t, nc1, (const int*)nullptr);
+          (const int*)state->a_t, (const int*)state->c_t, nc1, (const int*)nullptr, c->tab_slot, (const int*)b.node_mol, (int)(c->tab_slot_floats / 256));
         L("gather_ef", fm_k_gather_rows, dim3(std::min(4096, (int)(((size_t)E * 32 + 255) / 256))), dim3(256), 0, c->ef, c->ef_tab, 128, E,
-          (const int*)state->e_t, (const int*)nullptr, 0, (const int*)b.e_pair);
+          (const int*)state->e_t, (const int*)nullptr, 0, (const int*)b.e_pair, (const int*)nullptr, (const int*)nullptr, 0);
         tap("embed.s", c->s, (size_t)N * 256 * 4);
         tap("embed.ef", c->ef, (size_t)E * 128 * 4);
     }
@@ -455,13 +456,15 @@ int embed_table(fm_ctx* c, hipStream_t st, const float* temb, int n_tables = 1) 
     return L.rc;
 }
 
-// tables_ready: the caller (fm_integrate) has already built this step's table into slot `table_slot`
+// tables_ready: the caller (fm_integrate) has already built this step's table into slot `table_slot`.  tab_slot (per-molecule time): device (n_mols) slot of
+// every molecule's table, counted from `table_slot`; the n_tables tables built here are temb's rows
 int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap,
-                 int remove_com, const fm_dst* out, int table_slot = -1) {
+                 int remove_com, const fm_dst* out, int table_slot = -1, const int* tab_slot = nullptr, int n_tables = 1) {
     int rc = 0;
-    if (table_slot < 0) { table_slot = 0; rc = embed_table(c, st, temb); }
+    if (table_slot < 0) { table_slot = 0; rc = embed_table(c, st, temb, n_tables); }
     if (rc) return rc;
     c->s_tab = c->s_tab_base + (size_t)table_slot * c->tab_slot_floats;
+    c->tab_slot = tab_slot;
     const bool sc = c->cfg.self_conditioning != 0;
     if (sc && !prev && bootstrap) {
         rc = evaluate(c, st, state, nullptr, 0, &c->boot, false);
@@ -476,9 +479,13 @@ int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* 
 
 __global__ void fm_k_noop() {}
 
+// device arrays of one call-step of fm_integrate_mixed (FmCtmcMixedArgs)
+struct MixedStep { const fm_step_scalars* steps; const int* active; const int* mol_group; };
+
 // frame: this step's slice of the trajectory sink (x, a, c, e, x1 used; a1 / c1 / e1 travel in `smp`); campbell steps write it inside the fused kernel
 int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* dst, const fm_step_noise* nz,
-              const fm_step_scalars* sc, const fm_sampled* smp, const float* x_raw = nullptr, const fm_traj_sink* frame = nullptr) {
+              const fm_step_scalars* sc, const fm_sampled* smp, const float* x_raw = nullptr, const fm_traj_sink* frame = nullptr,
+              const MixedStep* mixed = nullptr) {
     Launch L{c, st};
     // profiling only: an event pair around an empty kernel, once per step.  Its elapsed time is what a pair adds to every profiled launch
     // (event signalling + the dispatch that cannot overlap the previous kernel's tail); fm_profile_get("event_overhead") lets the caller
@@ -539,6 +546,12 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
     if (frame) { f.sink_x = frame->x; f.sink_x1 = frame->x1; }
     if (sc->noise_mode == FM_NOISE_PHILOX) { f.philox = 1; f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->mol_gid; }
     else if (!nz->q_a || !nz->u1_a || !nz->q_e) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
+    if (mixed) {      // per-molecule time: the scalars of `f` are unused, every molecule reads its group's from the caller's device arrays
+        const FmCtmcMixedArgs mx{f, mixed->steps, mixed->active, mixed->mol_group};
+        if (c->plan.ctmc_threads == 1024) L("ctmc_mixed", fm_k_ctmc_fused_mixed<1024>, dim3(b.B, 4), dim3(1024), 0, mx);
+        else L("ctmc_mixed", fm_k_ctmc_fused_mixed<256>, dim3(b.B, 4), dim3(256), 0, mx);
+        return L.rc;
+    }
     if (c->plan.ctmc_threads == 1024) L("ctmc", fm_k_ctmc_fused<1024>, dim3(b.B, 4), dim3(1024), 0, f);
     else L("ctmc", fm_k_ctmc_fused<256>, dim3(b.B, 4), dim3(256), 0, f);
     return L.rc;
@@ -1241,6 +1254,65 @@ int fm_integrate(fm_ctx* c, void* stream, const fm_state* state, int n_steps, co
             L.copy(frame.x1, out->x, frame.x1 ? (size_t)b.N * 12 : 0);
             if (L.rc) return L.rc;
         }
+        prev = out;
+        cur ^= 1;
+    }
+    if (final_dst) *final_dst = cur ^ 1;
+    return FM_OK;
+}
+
+// what both per-molecule-time entry points refuse (the model families whose time does not enter through the embedding table alone)
+static int mixed_check(fm_ctx* c, const char* fn, int n_groups) {
+    if (!c->bound) return fail(c, FM_ERR_STATE, "%s: no batch bound", fn);
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) are not supported with per-molecule time", fn);
+    if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
+    return FM_OK;
+}
+
+int fm_forward_mixed(fm_ctx* c, void* stream, const fm_state* state, const float* temb, int n_groups, const int32_t* mol_group, const fm_dst* prev,
+                     int bootstrap, int remove_com, const fm_dst* out) {
+    if (!c || !state || !temb || !mol_group || !out) return fail(c, FM_ERR_INVALID, "fm_forward_mixed: null argument");
+    if (const int rc = mixed_check(c, "fm_forward_mixed", n_groups)) return rc;
+    return forward_impl(c, (hipStream_t)stream, state, temb, prev, bootstrap, remove_com ? 1 : 0, out, -1, mol_group, n_groups);
+}
+
+int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                       const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                       const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst) {
+    if (!c || !state || !steps || !steps_dev || !active || !active_dev || !mol_group || !temb || !dst_a || !dst_b) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: null argument");
+    if (const int rc = mixed_check(c, "fm_integrate_mixed", n_groups)) return rc;
+    if (sink) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: a trajectory sink is not supported with per-molecule time");
+    // the launch decisions are made from the host copy, before anything is enqueued
+    for (int i = 0; i < n_steps * n_groups; ++i) {
+        if (!active[i]) continue;
+        if (steps[i].dfm_type != FM_DFM_CAMPBELL) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: dfm_type gat is not supported with per-molecule time (step %d, group %d)", i / n_groups, i % n_groups);
+        if (steps[i].noise_mode != FM_NOISE_PHILOX) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: FM_NOISE_TENSORS is not supported with per-molecule time: the reference's draw order depends on last_step (step %d, group %d)", i / n_groups, i % n_groups);
+    }
+    int boot0 = 0;
+    if (!prev0 && n_steps > 0) {      // prev is None and (t == 0).all(), vector_field.py:269-272, over the groups that take the step
+        int at0 = 0, later = 0;
+        for (int g = 0; g < n_groups; ++g) if (active[g]) (steps[g].t == 0.0f ? at0 : later) += 1;
+        if (at0 && later) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: prev0 is NULL and only %d of %d active groups are at t = 0: start the groups at t = 0 in a call of their own", at0, at0 + later);
+        boot0 = at0 ? 1 : 0;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int tt = c->cfg.time_embedding_dim;
+    const int spc = FM_TAB_SLOTS / n_groups;      // steps per table launch: every (step, group) of a chunk owns a slot
+    const fm_dst* prev = prev0;
+    int cur = (prev0 && prev0->x == dst_a->x) ? 1 : 0;
+    static const fm_step_scalars philox_step = [] { fm_step_scalars s{}; s.dfm_type = FM_DFM_CAMPBELL; s.noise_mode = FM_NOISE_PHILOX; return s; }();
+    for (int i = 0; i < n_steps; ++i) {
+        const fm_dst* out = cur == 0 ? dst_a : dst_b;
+        if (i % spc == 0) {
+            const int nt = n_steps - i < spc ? n_steps - i : spc;
+            const int rc0 = embed_table(c, st, temb + (size_t)i * n_groups * tt, nt * n_groups);
+            if (rc0) return rc0;
+        }
+        int rc = forward_impl(c, st, state, nullptr, prev, i == 0 ? boot0 : 0, 2, out, (i % spc) * n_groups, mol_group);
+        if (rc) return rc;
+        const MixedStep ms{steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
+        rc = ctmc_impl(c, st, state, out, nullptr, &philox_step, nullptr, c->xw, nullptr, &ms);
+        if (rc) return rc;
         prev = out;
         cur ^= 1;
     }

@@ -116,6 +116,7 @@ struct fm_ctx {
     float *s = nullptr, *v = nullptr, *xw = nullptr, *ef = nullptr, *Ps = nullptr, *Asd = nullptr, *PV = nullptr;
     float *part_s = nullptr, *part_v = nullptr, *s_tab = nullptr, *Psd = nullptr, *PVd = nullptr;
     float* s_tab_base = nullptr; size_t tab_slot_floats = 0;      // FM_TAB_SLOTS embedding tables (one per step of a chunk); s_tab = the current step's
+    const int* tab_slot = nullptr;      // per-molecule time: the caller's device (n_mols) table slot of every molecule, counted from s_tab; null = one table (set with s_tab)
     float *tap_s = nullptr, *tap_v = nullptr;    // scratch of the aggregated-message taps (parity runs only)
     fm_dst boot{};
     int32_t *sa1 = nullptr, *sc1 = nullptr, *se1 = nullptr;

@@ -7,6 +7,7 @@
 #pragma once
 #include <type_traits>
 
+#include "../../include/flowmol_hip.h"      // fm_step_scalars: the mixed CTMC kernel reads the caller's per-(step, group) array as it is
 #include "fm_device.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -127,6 +128,9 @@ struct FmMlpArgs {
     // TABLE, several tables in one launch (the embedding tables of a whole chunk of integration steps): workgroup b builds tile
     // b % tab_tiles of table b / tab_tiles, whose time embedding is temb + table * tt and whose rows start at out + table * tab_stride
     int tab_tiles; int tab_stride;
+    // SC_NODE, per-molecule time (fm_forward_mixed / fm_integrate_mixed): node n reads table slot tab_slot[node_mol[n]], slot_rows table rows apart
+    // (s_tab = slot 0).  null = one table for the whole batch
+    const int* tab_slot; const int* node_mol; int slot_rows;
 };
 
 // TM = rows per tile: 64 (throughput: every weight fragment serves four row tiles) or 16 (small batches: a tile's two dependent GEMMs are
@@ -162,6 +166,7 @@ __device__ __forceinline__ void fm_mlp2_tile(const FmMlpArgs& a, int tile, float
             int tok = -1; float d = 0.f;
             if (n < a.rows) {
                 tok = a.tok_a[n] * a.n_c1 + a.tok_c[n];
+                if (a.tab_slot) tok += a.tab_slot[a.node_mol[n]] * a.slot_rows;
                 d = fm_norm3(a.x_t[n * 3 + 0] - a.prev_x[n * 3 + 0], a.x_t[n * 3 + 1] - a.prev_x[n * 3 + 1], a.x_t[n * 3 + 2] - a.prev_x[n * 3 + 2]);
             }
             meta[tid] = tok; dd[tid] = d;
@@ -420,6 +425,7 @@ struct FmMlp4Args {
     const void* W2q; const float* b2;          // SC_NODE: K = 256, N = 256 (G = 4); NODE_HEAD: K = 256, N = 64 (G = 1; na + nc real columns)
     // SC_NODE
     const float* s_tab; const int* tok_a; const int* tok_c; int n_c1;
+    const int* tab_slot; const int* node_mol; int slot_rows;      // per-molecule table slot (FmMlpArgs::tab_slot), null = one table
     const float* prev_a; const float* prev_c; const float* prev_x; const float* x_t;
     int na, nc; float rbf_mu_step, rbf_inv_sigma;
     float* out; float* out2;                   // SC_NODE: s (N,256); NODE_HEAD: atom-type / charge probabilities
@@ -446,6 +452,7 @@ __device__ __forceinline__ void fm_mlp4_tile(const FmMlp4Args& a, int tile, floa
             int tok = -1; float d = 0.f;
             if (n < a.N) {
                 tok = a.tok_a[n] * a.n_c1 + a.tok_c[n];
+                if (a.tab_slot) tok += a.tab_slot[a.node_mol[n]] * a.slot_rows;
                 d = fm_norm3(a.x_t[n * 3 + 0] - a.prev_x[n * 3 + 0], a.x_t[n * 3 + 1] - a.prev_x[n * 3 + 1], a.x_t[n * 3 + 2] - a.prev_x[n * 3 + 2]);
             }
             meta[tid] = tok; dd[tid] = d;
@@ -523,12 +530,14 @@ __global__ void __launch_bounds__(FM_THREADS) fm_k_mlp4_pair(FmMlp4Args a, FmMlp
 // gather-only initialisation when there is no self-conditioning input (bootstrap pass / non-SC models)
 static __global__ void __launch_bounds__(256) fm_k_gather_rows(float* __restrict__ out, const float* __restrict__ tab, int width,
                                                          int rows, const int* __restrict__ tok_a, const int* __restrict__ tok_c,
-                                                         int n_c1, const int* __restrict__ e_pair) {
-    // node rows: tok = tok_a*n_c1+tok_c ; edge rows (e_pair != null): tok = tok_a[e_pair[row]]
+                                                         int n_c1, const int* __restrict__ e_pair, const int* __restrict__ tab_slot,
+                                                         const int* __restrict__ node_mol, int slot_rows) {
+    // node rows: tok = tok_a*n_c1+tok_c (+ tab_slot[node_mol[row]] * slot_rows: per-molecule table slot, null = one table) ; edge rows (e_pair != null): tok = tok_a[e_pair[row]]
     const int w4 = width / 4;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (size_t)rows * w4; idx += (size_t)gridDim.x * blockDim.x) {
         const int row = (int)(idx / w4), c4 = (int)(idx % w4);
-        const int tok = e_pair ? tok_a[e_pair[row]] : tok_a[row] * n_c1 + tok_c[row];
+        int tok = e_pair ? tok_a[e_pair[row]] : tok_a[row] * n_c1 + tok_c[row];
+        if (tab_slot) tok += tab_slot[node_mol[row]] * slot_rows;
         reinterpret_cast<float4*>(out)[idx] = reinterpret_cast<const float4*>(tab)[(size_t)tok * w4 + c4];
     }
 }
@@ -1715,12 +1724,10 @@ __device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
 
 // NT threads per workgroup: 256, or 1024 for batches of a few molecules -- there one workgroup per (molecule, modality) is all the parallelism the kernel has,
 // and a 47-atom molecule's 1081 pair rows are five dependent load-compute rounds of 256 threads but two of 1024 (one molecule: 13.9 -> 8 us per step)
+// Jobs 0..2: modality `job` (descriptor md) of molecule `mol`; the step's scalars are a's and md's.  One body for the kernel whose scalars are launch
+// arguments (fm_k_ctmc_fused) and the one that reads them per molecule from memory (fm_k_ctmc_fused_mixed)
 template <int NT>
-__global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
-    __shared__ int red[2][NT / 64];
-    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
-    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
-    const FmCtmcMod md = a.mod[job];
+__device__ __forceinline__ void fm_ctmc_mod_job(const FmCtmcFusedArgs& a, const FmCtmcMod& md, int (&red)[2][NT / 64], int mol, int job, int tid) {
     const int r0 = md.off[mol], r1 = md.off[mol + 1], K = md.K;
     const unsigned gid = a.philox ? (unsigned)a.mol_gid[mol] : 0u, ctr2 = (unsigned)a.step * 4u + (unsigned)job;
     int cm = 0, ch = 0;
@@ -1788,6 +1795,42 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
         md.x1[i] = x1;
         if (md.sink_t) md.sink_t[i] = nt;
     }
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
+    __shared__ int red[2][NT / 64];
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
+    const FmCtmcMod md = a.mod[job];
+    fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid);
+}
+
+// Per-molecule time (fm_integrate_mixed): the campbell step of a batch whose molecules sit at different points of different schedules.  Molecule `mol`
+// takes this step's scalars of its group, steps[mol_group[mol]] -- the caller's fm_step_scalars array in device memory, read as it is -- and is skipped
+// altogether while active[group] == 0: no store, no draw.  The values are workgroup-uniform (scalar loads); rows and positions run the bodies above, so
+// a molecule's bits are those of fm_k_ctmc_fused launched with its group's scalars.  Philox noise only (f.philox == 1).
+struct FmCtmcMixedArgs {
+    FmCtmcFusedArgs f;                // pointers, K, offsets; its step scalars are unused
+    const fm_step_scalars* steps;     // [n_groups] this call-step's row of the caller's (n_steps, n_groups) array
+    const int* active;                // [n_groups]
+    const int* mol_group;             // [B]
+};
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_fused_mixed(FmCtmcMixedArgs m) {
+    __shared__ int red[2][NT / 64];
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    const int g = m.mol_group[mol];
+    if (!m.active[g]) return;
+    const fm_step_scalars& s = m.steps[g];
+    FmCtmcFusedArgs a = m.f;
+    a.temp = s.cat_temperature; a.hc_thresh = s.hc_thresh; a.last_step = s.last_step;
+    a.coef = s.x_coef; a.dt = s.dt; a.scale = s.x_scale;
+    a.seed_lo = s.philox_seed_lo; a.seed_hi = s.philox_seed_hi; a.step = s.step_index;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
+    FmCtmcMod md = m.f.mod[job];
+    md.unmask_prob = s.unmask_prob[job]; md.mask_prob = s.mask_prob[job];
+    fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -143,6 +143,26 @@ def make_step_plan(n_timesteps: int, eta: float, hc_thresh: float, cat_temperatu
     return StepPlan(t, out)
 
 
+def mixed_step_arrays(plans: Sequence[StepPlan], start: Sequence[int], n_steps: int, time_embedding_dim: int):
+    """Host arrays of one fm_integrate_mixed call: (n_steps * G) fm_step_scalars and int32 active flags, row k * G + g = step start[g] + k of
+    plans[g] (inactive, zeroed, once the plan has run out), and the (n_steps * G, time_embedding_dim) time embeddings of those steps."""
+    G = len(plans)
+    scal = (fm_step_scalars * (n_steps * G))()
+    act = (C.c_int32 * (n_steps * G))()
+    temb = torch.zeros(n_steps * G, time_embedding_dim)
+    rows = {}
+    for k in range(n_steps):
+        for g in range(G):
+            if start[g] + k < len(plans[g].scalars):
+                sc = plans[g].scalars[start[g] + k]
+                scal[k * G + g] = sc
+                act[k * G + g] = 1
+                if sc.t not in rows:
+                    rows[sc.t] = time_embedding_host(sc.t, time_embedding_dim)
+                temb[k * G + g] = rows[sc.t]
+    return scal, act, temb
+
+
 class StepNoise:
     """The nine noise tensors of one CTMC step, in the reference's draw order
     (per modality a, c, e: Exp(1) (rows,K) -> rand(rows) -> rand(rows) [not drawn on the last step])."""
@@ -498,11 +518,21 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ hot path
-    def forward(self, state, t: float, prev=None, bootstrap=False, remove_com=True, out=None, taps: Optional[Dict[str, torch.Tensor]] = None):
+    def forward(self, state, t, prev=None, bootstrap=False, remove_com=True, out=None, taps: Optional[Dict[str, torch.Tensor]] = None):
         """One network evaluation -> dst dict of probabilities (EndpointVectorField.forward with
-        apply_softmax=True)."""
+        apply_softmax=True).  ``t``: a number, or the reference's per-graph time, a (B,) tensor (vector_field.py:212: molecules with equal t share
+        an embedding table, fm_forward_mixed; at most 32 distinct values).  A molecule's result is the same bits either way."""
         out = out if out is not None else self.new_dst()
-        temb = time_embedding_host(float(t), self.cfg.time_embedding_dim).to(self.device)
+        mixed = torch.is_tensor(t) and t.dim() > 0
+        if mixed:
+            tv = t.detach().to('cpu', torch.float32).reshape(-1)
+            if tv.shape[0] != self.B:
+                raise ValueError(f't has {tv.shape[0]} entries, the bound batch {self.B} molecules')
+            vals, group = torch.unique(tv, return_inverse=True)
+            temb = torch.stack([time_embedding_host(float(v), self.cfg.time_embedding_dim) for v in vals]).to(self.device).contiguous()
+            group = group.to(torch.int32).to(self.device)
+        else:
+            temb = time_embedding_host(float(t), self.cfg.time_embedding_dim).to(self.device)
         st = self._state_struct(state)
         o = self._dst_struct(out)
         p = self._dst_struct(prev) if prev is not None else None
@@ -511,12 +541,16 @@ class Engine:
             for k, v in taps.items():
                 self._check(self.lib.fm_set_tap(self._ctx, k.encode(), _ptr(v)), 'fm_set_tap')
         with self._dev():
-            rc = self.lib.fm_forward(self._ctx, self._stream(), C.byref(st), _ptr(temb), C.byref(p) if p is not None else None,
-                                     int(bool(bootstrap)), int(bool(remove_com)), C.byref(o))
-        self._check(rc, 'fm_forward')
+            if mixed:
+                rc = self.lib.fm_forward_mixed(self._ctx, self._stream(), C.byref(st), _ptr(temb), int(vals.shape[0]), _ptr(group),
+                                               C.byref(p) if p is not None else None, int(bool(bootstrap)), int(bool(remove_com)), C.byref(o))
+            else:
+                rc = self.lib.fm_forward(self._ctx, self._stream(), C.byref(st), _ptr(temb), C.byref(p) if p is not None else None,
+                                         int(bool(bootstrap)), int(bool(remove_com)), C.byref(o))
+        self._check(rc, 'fm_forward_mixed' if mixed else 'fm_forward')
         if taps:
             self.lib.fm_clear_taps(self._ctx)
-        self._keep = [temb, state, out, prev]
+        self._keep = [temb, state, out, prev, group if mixed else None]
         return out
 
     # ------------------------------------------------------------------ endpoint parameterization (EndpointVectorField)
@@ -613,6 +647,42 @@ class Engine:
         run.run(0, len(plan.scalars), chunk=chunk)
         self.synchronize()
         return run.last_dst()
+
+    def integrate_mixed(self, state, plans: Sequence[StepPlan], mol_group, start: Optional[Sequence[int]] = None, n_steps: Optional[int] = None,
+                        prev=None):
+        """Advance a batch whose molecules follow different schedules (fm_integrate_mixed).  ``plans``: one Philox campbell ``StepPlan`` of the
+        unchanged ``make_step_plan`` per group (at most 32); ``mol_group`` (B,): the group of every molecule; ``start[g]``: the step of its plan group
+        ``g`` takes first (default 0; > 0 continues a trajectory and needs ``prev``, the endpoint dict the previous call returned).  Runs ``n_steps``
+        call-steps (default: until the longest group has finished); a group that runs out of steps waits inactive, its molecules' state untouched.
+        Returns the final endpoint prediction dict (None when nothing ran) and synchronises, like ``integrate``."""
+        G = len(plans)
+        start = [0] * G if start is None else [int(v) for v in start]
+        left = [len(pl.scalars) - s0 for pl, s0 in zip(plans, start)]
+        if len(start) != G or min(left, default=0) < 0:
+            raise ValueError('start must give one step index inside its plan per group')
+        n = max(left, default=0) if n_steps is None else int(n_steps)
+        group = torch.as_tensor(mol_group).detach().to('cpu', torch.int32).reshape(-1)
+        if group.shape[0] != self.B or (G and (int(group.min()) < 0 or int(group.max()) >= G)):
+            raise ValueError(f'mol_group must hold one group index in [0, {G}) per bound molecule')
+        if n <= 0:
+            return None
+        scal, act, temb = mixed_step_arrays(plans, start, n, self.cfg.time_embedding_dim)
+        d = self.device
+        scal_dev = torch.frombuffer(bytearray(bytes(scal)), dtype=torch.uint8).to(d)
+        act_dev = torch.tensor(list(act), dtype=torch.int32).to(d)
+        temb, group = temb.to(d).contiguous(), group.to(d)
+        dst = [self.new_dst(), self.new_dst()]
+        ds = [self._dst_struct(dst[0]), self._dst_struct(dst[1])]
+        st = self._state_struct(state)
+        p = self._dst_struct(prev) if prev is not None else None
+        final = C.c_int(0)
+        with self._dev():
+            rc = self.lib.fm_integrate_mixed(self._ctx, self._stream(), C.byref(st), n, G, scal, _ptr(scal_dev), act, _ptr(act_dev), _ptr(group), _ptr(temb),
+                                             C.byref(p) if p is not None else None, C.byref(ds[0]), C.byref(ds[1]), None, C.byref(final))
+        self._check(rc, 'fm_integrate_mixed')
+        self.synchronize()
+        self._keep = [state, prev, dst]
+        return dst[final.value]
 
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):

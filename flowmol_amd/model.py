@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import presets
+from . import _lib, presets
 from .config import VFConfig, from_reference_hparams
 from .engine import Engine, StepNoise, cat_temp_schedule, forward_weight_schedule, make_step_plan
 from .molecule import SampledMolecule
@@ -236,6 +236,8 @@ class FlowMol:
         are asked for) gives every rank the full batch's frames in the caller's order."""
         import torch.distributed as dist
         from . import shard
+        if _step_counts(n_timesteps) is not None:
+            raise NotImplementedError('sample_distributed with a sequence of n_timesteps: a mixed-time batch is not sharded across ranks')
         if noise not in ('per_rank', 'replicated', 'philox'):
             raise ValueError(f"noise must be 'per_rank', 'replicated' or 'philox', got {noise!r}")
         n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
@@ -298,9 +300,17 @@ class FlowMol:
         (campbell and gat steps, and the priors of endpoint-parameterised models): no noise tensors, and a molecule's result depends only on
         ``seed=`` (default: one draw from torch's CPU generator) and on its id in ``mol_ids=`` (default 0..B-1), not on its batch.  So
         ``model.sample(n_atoms[i:i+1], rng='philox', seed=s, mol_ids=[i])`` regenerates molecule *i* of an earlier
-        ``model.sample(n_atoms, rng='philox', seed=s)`` on its own, bit for bit with canonical arithmetic (the default)."""
+        ``model.sample(n_atoms, rng='philox', seed=s)`` on its own, bit for bit with canonical arithmetic (the default).
+
+        ``n_timesteps`` may be a sequence of B ints, one per molecule (``rng='philox'``, campbell CTMC models): molecules with equal counts form a
+        time group, the groups advance together in one batch and a finished molecule waits until the call ends; ``n_timesteps[i] == 1`` returns
+        molecule *i*'s prior.  Molecule *i* is, bit for bit, ``model.sample(n_atoms[i:i+1], n_timesteps=n_timesteps[i], rng='philox', seed=s, mol_ids=[i])``.
+        Raises NotImplementedError for more than 32 distinct counts, rng='torch', dfm_type 'gat', endpoint models, xt_traj / ep_traj and tspan."""
         if device is not None and torch.device(device) != self.device:
             self.to(device)
+        counts = _step_counts(n_timesteps)
+        if counts is not None:
+            return self._sample_mixed(n_atoms, counts, stochasticity, high_confidence_threshold, xt_traj, ep_traj, prior, return_tensors, kwargs)
         eng = self.engine
         dev = eng.device
         n_timesteps = self.default_n_timesteps if n_timesteps is None else n_timesteps
@@ -382,6 +392,67 @@ class FlowMol:
         mols = self._package(out, n_atoms, frames, xt_traj, ep_traj)
         self.last_timing['package'] = time.perf_counter() - t2
         return mols
+
+    def _mixed_plan_args(self, stochasticity, high_confidence_threshold, kwargs):
+        """What make_step_plan takes besides the step count and the seed, as sample() passes it (campbell)."""
+        cfg = self.cfg
+        eta = cfg.stochasticity if stochasticity is None else stochasticity
+        hc = cfg.high_confidence_threshold if high_confidence_threshold is None else high_confidence_threshold
+        return (eta, hc, kwargs.get('cat_temp_func') or cat_temp_schedule(cfg)), dict(
+            dfm_type='campbell', forward_weight_func=kwargs.get('forward_weight_func') or forward_weight_schedule(cfg), inv_temp_func=kwargs.get('inv_temp_func'),
+            schedule_type=cfg.schedule_type, cosine_params=cfg.cosine_params)
+
+    def _check_mixed(self, kwargs, xt_traj=False, ep_traj=False):
+        """The combinations per-molecule step counts do not cover, each refused by name."""
+        if self.cfg.parameterization == 'endpoint':
+            raise NotImplementedError('per-molecule n_timesteps: endpoint models are not supported (time enters their embedding MLP per node)')
+        if kwargs.get('rng', 'torch') != 'philox':
+            raise NotImplementedError("per-molecule n_timesteps needs rng='philox': with rng='torch' the reference's draw order depends on every molecule's last step")
+        if (kwargs.get('dfm_type') or self.cfg.dfm_type) != 'campbell':
+            raise NotImplementedError("per-molecule n_timesteps: dfm_type 'gat' is not supported")
+        if xt_traj or ep_traj:
+            raise NotImplementedError('per-molecule n_timesteps: xt_traj / ep_traj are not supported (no trajectory sink)')
+        if kwargs.get('tspan') is not None:
+            raise NotImplementedError('per-molecule n_timesteps: tspan is one schedule for the whole batch')
+
+    def _sample_mixed(self, n_atoms, counts, stochasticity, high_confidence_threshold, xt_traj, ep_traj, prior, return_tensors, kwargs):
+        """sample() with one step count per molecule: one bind, one fm_integrate_mixed call."""
+        self._check_mixed(kwargs, xt_traj, ep_traj)
+        unknown = set(kwargs) - {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids'}
+        if unknown:
+            raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
+        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
+        if len(counts) != n_atoms.numel():
+            raise ValueError(f'n_timesteps has {len(counts)} entries for {n_atoms.numel()} molecules')
+        if min(counts) < 1:
+            raise ValueError('n_timesteps must be >= 1')
+        distinct = sorted(set(counts))
+        if len(distinct) > _lib.FM_TAB_SLOTS:
+            raise NotImplementedError(f'more than {_lib.FM_TAB_SLOTS} distinct step counts in one batch ({len(distinct)}): split the call')
+        eng = self.engine
+        eng.bind(n_atoms)
+        seed = self._philox_setup(kwargs)
+        state = eng.prior_state(eng.prior_philox(seed)) if prior is None else self._state_from_prior(prior)
+        args, kw = self._mixed_plan_args(stochasticity, high_confidence_threshold, kwargs)
+        plans = [make_step_plan(T, *args, philox_seed=seed, **kw) for T in distinct]
+        import time
+        t0 = time.perf_counter()
+        eng.integrate_mixed(state, plans, [distinct.index(T) for T in counts])
+        eng.synchronize()
+        t1 = time.perf_counter()
+        out_dev = {k: state[f'{k}_t'] for k in 'xace'}
+        self.last_timing = {'integrate': t1 - t0, 'precision': eng.precision}
+        if return_tensors == 'device':
+            return out_dev, n_atoms
+        out = _to_host(out_dev)
+        if return_tensors:
+            return out, n_atoms
+        return self._package(out, n_atoms, None, False, False)
+
+    def sampling_queue(self, seed: int, stochasticity=None, high_confidence_threshold=None, **kwargs) -> "SamplingQueue":
+        """A queue that admits requests into a batch that is already running (flowmol_amd.sampling_queue.SamplingQueue)."""
+        from .sampling_queue import SamplingQueue
+        return SamplingQueue(self, seed, stochasticity=stochasticity, high_confidence_threshold=high_confidence_threshold, **kwargs)
 
     def _philox_setup(self, kwargs) -> int:
         """Seed and molecule ids of a Philox run: ``seed`` / ``mol_ids`` (``_philox`` / ``_mol_ids`` are their earlier, private spellings)."""
@@ -567,6 +638,17 @@ class FlowMol:
                                         ctmc_mol=self.cfg.has_mask, explicit_aromaticity=self.explicit_aromaticity, traj_frames=tf,
                                         build_xt_traj=xt_traj, build_ep_traj=ep_traj, n_charges=self.n_atom_charges))
         return mols
+
+
+def _step_counts(n_timesteps):
+    """A per-molecule sequence of step counts as a list of ints, or None for what sample() has always taken (None, an int, a 0-dim tensor)."""
+    if n_timesteps is None or isinstance(n_timesteps, int):
+        return None
+    if torch.is_tensor(n_timesteps):
+        return None if n_timesteps.dim() == 0 else [int(v) for v in n_timesteps.reshape(-1).tolist()]
+    if isinstance(n_timesteps, (list, tuple)) or (hasattr(n_timesteps, '__len__') and hasattr(n_timesteps, '__iter__')):
+        return [int(v) for v in n_timesteps]
+    return None
 
 
 def _frames_of(init: Dict[str, torch.Tensor], traj: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -1,0 +1,150 @@
+"""``SamplingQueue``: requests join a batch that is already integrating (no reference counterpart: the reference's ``sample`` starts and ends a
+batch together).  One molecule costs about as much per step as eight, so a stream of small requests is served by admitting each newcomer into the
+running batch instead of running them back to back.
+
+Built on per-molecule time (``Engine.integrate_mixed``) and the per-molecule Philox streams: every molecule is, bit for bit, the molecule
+``model.sample([n], n_timesteps=T, rng='philox', seed=seed, mol_ids=[id])`` run alone, whenever it was admitted and whoever it shared the batch with.
+Synchronous and single-stream: ``run`` returns when its steps have run; admission happens at the start of a ``run`` call."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional
+
+import torch
+
+from . import _lib
+from .engine import IntegrationRun, make_step_plan
+
+
+class _Request:
+    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev')
+
+    def __init__(self, ticket, n, T, mol_id):
+        self.ticket, self.n, self.T, self.mol_id = ticket, n, T, mol_id
+        self.pos = 0          # steps taken
+        self.state = None     # {'x_t', 'a_t', 'c_t', 'e_t'}: this molecule's rows, on the device
+        self.prev = None      # {'x', 'a', 'c', 'e'}: its previous endpoint prediction
+
+
+class SamplingQueue:
+    def __init__(self, model, seed: int, stochasticity=None, high_confidence_threshold=None, **kwargs):
+        """``model``: a CTMC ``FlowMol`` on its device; ``seed``: the Philox seed of every request.  ``kwargs``: cat_temp_func / forward_weight_func /
+        inv_temp_func of ``FlowMol.sample``."""
+        model._check_mixed({'rng': 'philox', **kwargs})
+        self.model, self.seed = model, int(seed)
+        self._plan_args, self._plan_kw = model._mixed_plan_args(stochasticity, high_confidence_threshold, kwargs)
+        self._plans: Dict[int, object] = {}
+        self._pending: List[_Request] = []
+        self._running: List[_Request] = []
+        self._finished: Dict[int, object] = {}
+        self._next_ticket = 0
+
+    # ------------------------------------------------------------------ requests
+    def submit(self, n_atoms, n_timesteps=None, mol_ids=None) -> List[int]:
+        """Queue molecules of the given sizes; returns one ticket per molecule.  ``n_timesteps``: an int for all of them (default: the model's) or one per
+        molecule; ``mol_ids``: their Philox stream ids (default: the ticket numbers).  They are admitted by the next ``run``."""
+        sizes = [int(v) for v in torch.as_tensor(n_atoms).reshape(-1).tolist()]
+        if n_timesteps is None:
+            n_timesteps = self.model.default_n_timesteps
+        Ts = [int(n_timesteps)] * len(sizes) if isinstance(n_timesteps, int) else [int(v) for v in n_timesteps]
+        ids = None if mol_ids is None else [int(v) for v in torch.as_tensor(mol_ids).reshape(-1).tolist()]
+        if len(Ts) != len(sizes) or (ids is not None and len(ids) != len(sizes)):
+            raise ValueError('n_timesteps / mol_ids must give one entry per molecule')
+        if any(n < 1 for n in sizes) or any(T < 1 for T in Ts):
+            raise ValueError('n_atoms and n_timesteps must be >= 1')
+        tickets = []
+        for i, (n, T) in enumerate(zip(sizes, Ts)):
+            t = self._next_ticket
+            self._next_ticket += 1
+            self._pending.append(_Request(t, n, T, t if ids is None else ids[i]))
+            tickets.append(t)
+        return tickets
+
+    @property
+    def idle(self) -> bool:
+        return not self._pending and not self._running
+
+    def pop_finished(self) -> Dict[int, object]:
+        """{ticket: SampledMolecule} of the molecules that have finished since the last call."""
+        out, self._finished = self._finished, {}
+        return out
+
+    # ------------------------------------------------------------------ the batch
+    def _plan(self, T: int):
+        if T not in self._plans:
+            self._plans[T] = make_step_plan(T, *self._plan_args, philox_seed=self.seed, **self._plan_kw)
+        return self._plans[T]
+
+    @staticmethod
+    def _split(d, sizes, pair_key):
+        pairs = [n * (n - 1) // 2 for n in sizes]
+        cols = {k: torch.split(v, pairs if k == pair_key else sizes) for k, v in d.items()}
+        return [{k: cols[k][i] for k in d} for i in range(len(sizes))]
+
+    def _admit(self):
+        """Newcomers, grouped by step count, take step 0 (prior, bootstrap evaluation, first step) through fm_integrate on a bind of their own; then
+        they join the running list, as long as the batch keeps to the 32 time groups a bind has embedding tables for."""
+        eng = self.model.engine
+        groups = {(r.T, r.pos) for r in self._running}         # a time group = same schedule, same step
+        by_T: Dict[int, List[_Request]] = {}
+        keep = []
+        for r in self._pending:
+            joins = r.T > 2                                    # T <= 2: step 0 is the whole trajectory
+            if joins and (r.T, 1) not in groups and len(groups) >= _lib.FM_TAB_SLOTS:
+                keep.append(r)                                 # waits for a group to finish
+                continue
+            if joins:
+                groups.add((r.T, 1))
+            by_T.setdefault(r.T, []).append(r)
+        self._pending = keep
+        for T, reqs in by_T.items():
+            sizes = [r.n for r in reqs]
+            eng.bind(torch.tensor(sizes))
+            eng.set_molecule_ids(torch.tensor([r.mol_id for r in reqs]))
+            state = eng.prior_state(eng.prior_philox(self.seed))
+            prev = None
+            if T > 1:
+                run = IntegrationRun(eng, state, self._plan(T), None)
+                run.run(0, 1)
+                eng.synchronize()
+                prev = run.last_dst()
+            st, pv = self._split(state, sizes, 'e_t'), (self._split(prev, sizes, 'e') if prev is not None else [None] * len(reqs))
+            for r, s_, p_ in zip(reqs, st, pv):
+                r.state, r.prev, r.pos = s_, p_, min(1, T - 1)
+                (self._running if r.pos < T - 1 else self._done).append(r)
+
+    def _retire(self, reqs):
+        for r in reqs:
+            out = {k: r.state[f'{k}_t'].cpu() for k in 'xace'}
+            self._finished[r.ticket] = self.model._package(out, torch.tensor([r.n]), None, False, False)[0]
+
+    def run(self, max_steps: Optional[int] = None) -> int:
+        """Admit the pending requests, then advance the running batch by up to ``max_steps`` steps (default: until every running molecule has
+        finished).  Returns the number of steps taken; molecules that finish inside the call wait, untouched, until it returns."""
+        self._done: List[_Request] = []
+        if self._pending:
+            self._admit()
+        k = self._advance(max_steps) if self._running else 0
+        self._retire(self._done)
+        return k
+
+    def _advance(self, max_steps) -> int:
+        run = self._running
+        left = max(r.T - 1 - r.pos for r in run)
+        k = left if max_steps is None else min(int(max_steps), left)
+        if k <= 0:
+            return 0
+        eng = self.model.engine
+        sizes = [r.n for r in run]
+        eng.bind(torch.tensor(sizes))
+        eng.set_molecule_ids(torch.tensor([r.mol_id for r in run]))
+        keys = sorted({(r.T, r.pos) for r in run})
+        state = {f: torch.cat([r.state[f] for r in run]).contiguous() for f in ('x_t', 'a_t', 'c_t', 'e_t')}
+        prev = {f: torch.cat([r.prev[f] for r in run]).contiguous() for f in 'xace'}
+        dst = eng.integrate_mixed(state, [self._plan(T) for T, _ in keys], [keys.index((r.T, r.pos)) for r in run],
+                                  start=[pos for _, pos in keys], n_steps=k, prev=prev)
+        still = []
+        for r, s_, p_ in zip(run, self._split(state, sizes, 'e_t'), self._split(dst, sizes, 'e')):
+            r.state, r.prev, r.pos = s_, p_, min(r.pos + k, r.T - 1)
+            (still if r.pos < r.T - 1 else self._done).append(r)
+        self._running = still
+        return k

@@ -14,6 +14,9 @@
  *   fm_ctmc_step        the part of CTMCVectorField.step after the network evaluation,
  *                       ctmc_vector_field.py:328-411 + campbell_step :414-461 + purity_sampling ctmc_utils.py:4-34
  *   fm_integrate        CTMCVectorField.integrate, ctmc_vector_field.py:145-285
+ *   fm_forward_mixed    the same forward with the reference's per-graph time: t of shape (B,), vector_field.py:212-243 (t[node_batch_idx])
+ *   fm_integrate_mixed  CTMCVectorField.integrate for a batch whose molecules follow different schedules (no reference counterpart: its integrate
+ *                       takes one tspan; what a molecule computes is its own integrate call)
  *   fm_prior_philox_dense   the categorical priors of flowmol/data_processing/priors.py:8-107 as FlowMol.sample_prior draws them
  *                       (flowmol/models/flowmol.py:417-448), from per-molecule counter-based streams instead of the CPU generator
  *   fm_philox_tape      the draws of CTMCVectorField.step's torch.multinomial / torch.rand calls (ctmc_vector_field.py:349-357,
@@ -50,7 +53,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 8
+#define FM_ABI_VERSION 9
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -301,6 +304,33 @@ int fm_philox_tape(fm_ctx* ctx, void* stream, const fm_step_scalars* sc, const f
 int fm_integrate(fm_ctx* ctx, void* stream, const fm_state* state, int n_steps, const fm_step_scalars* steps,
                  const float* temb, const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a,
                  const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst);
+
+/* --- ABI 9: per-molecule time.  The molecules of the bound batch belong to n_groups <= 32 groups (mol_group: DEVICE (n_mols) int32, values in
+ * [0, n_groups)); every group has its own time.  Time enters the network through the (atom type, charge) embedding table only, so group g's molecules
+ * read the table built from row g of temb, and everything else is the arithmetic of fm_forward / fm_integrate: with canonical arithmetic and Philox
+ * noise a molecule's bits are those of the molecule run alone on its own schedule.  CTMC models (has_mask) only: endpoint models return FM_ERR_INVALID,
+ * as does n_groups > 32.  Neither call synchronises the stream or allocates device memory; workspace sizes are those of the existing calls.
+ *
+ * fm_forward_mixed: one evaluation; temb: device (n_groups, time_embedding_dim); prev / bootstrap / remove_com / out as in fm_forward. */
+int fm_forward_mixed(fm_ctx* ctx, void* stream, const fm_state* state, const float* temb, int n_groups, const int32_t* mol_group,
+                     const fm_dst* prev, int bootstrap, int remove_com, const fm_dst* out);
+
+/* fm_integrate_mixed: n_steps steps; at call-step k group g takes the campbell step steps[k * n_groups + g] (its own t, dt, coefficients, last_step,
+ * Philox step_index and seed) when active[k * n_groups + g] != 0, and is skipped otherwise: the state rows of its molecules stay bit-unchanged and no
+ * draw of their streams is consumed.  A group that has finished its schedule waits inactive; its rows of steps / temb must still be readable (any
+ * finite values).  A molecule's previous endpoint is carried from step to step only while its group stays active: groups go active -> inactive, not back.
+ *   steps / active: HOST arrays (n_steps, n_groups), read for the launch decisions;  steps_dev / active_dev: the same arrays in DEVICE memory (the
+ *   caller's; the fused CTMC kernel reads every molecule's scalars from them), which must stay untouched until the enqueued work has run;
+ *   temb: device (n_steps, n_groups, time_embedding_dim); the embedding tables of floor(32 / n_groups) steps are built per launch;
+ *   prev0, dst_a, dst_b, final_dst: as in fm_integrate.  Bootstrap follows the reference's `prev is None and (t == 0).all()` over the groups active at
+ *   step 0: all of them at t == 0 -> the bootstrap evaluation runs; some at 0 and some later with prev0 == NULL -> FM_ERR_INVALID (start newcomers in a
+ *   call of their own and pass their endpoint in);
+ *   FM_ERR_INVALID also for: dfm_type FM_DFM_GAT or noise_mode FM_NOISE_TENSORS in an active step (the reference's tensor draw order depends on
+ *   last_step, which differs between groups), and a non-NULL sink (trajectory frames are not recorded). */
+int fm_integrate_mixed(fm_ctx* ctx, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                       const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group,
+                       const float* temb, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink,
+                       int* final_dst);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",

@@ -1,0 +1,150 @@
+"""Time the per-molecule-time path on the GPU: what a step of fm_integrate_mixed costs next to fm_integrate, and what the sampling queue buys.
+
+    python tools/time_mixed_step.py step  [--n_mols 1024] [--n_atoms 47] [--steps 16] [--reps 7] [--out file.json]
+    python tools/time_mixed_step.py queue [--n_atoms 47] [--T 250] [--requests 8] [--gap 25] [--reps 3] [--out file.json]
+
+step   ms per step of `steps` steps from the middle of a 250-point schedule, ALTERNATING in every repetition between
+         integrate   fm_integrate (IntegrationRun.run), the existing path
+         mixed       fm_integrate_mixed with ONE time group holding every molecule (Engine.integrate_mixed: builds and uploads the per-(step, group)
+                     arrays, allocates two endpoint buffers, and ends in a device synchronise -- all inside the timed window)
+       Device events around the call, then a synchronise; min / median / max over the repetitions.
+queue  `requests` one-molecule requests of T time points, admitted `gap` steps apart through SamplingQueue, against the same requests sampled alone
+       back to back (FlowMol.sample, rng='philox'); host clock around work that ends in a device synchronise; wall time and ms per molecule-step
+       (wall / (requests x (T - 1))), alternating the two in every repetition.
+One JSON object on stdout (and in --out) with the digest of the library sources.  Needs a GPU: there is no CPU fallback for a timing."""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+from flowmol_amd import build          # noqa: E402
+from flowmol_amd.engine import IntegrationRun          # noqa: E402
+from flowmol_amd.model import FlowMol          # noqa: E402
+
+SEED = 11
+
+
+def summary(v):
+    return {'min': min(v), 'median': statistics.median(v), 'max': max(v)}
+
+
+def step_mode(args, model):
+    eng = model.engine
+    sizes = torch.full((args.n_mols,), args.n_atoms)
+    eng.bind(sizes)
+    T, lo = 250, 100
+    p_args, p_kw = model._mixed_plan_args(None, None, {})
+    from flowmol_amd.engine import make_step_plan
+    plan = make_step_plan(T, *p_args, philox_seed=SEED, **p_kw)
+    state0 = eng.prior_state(eng.prior_philox(SEED))
+    run = IntegrationRun(eng, state0, plan, None)
+    run.run(0, 2)                                    # an endpoint prediction to continue from (the bootstrap evaluation is not what is timed)
+    torch.cuda.synchronize()
+    prev0 = {k: v.clone() for k, v in run.last_dst().items()}
+    start = {k: v.clone() for k, v in state0.items()}
+    group = torch.zeros(args.n_mols, dtype=torch.int32)
+
+    def timed(kind):
+        state = {k: v.clone() for k, v in start.items()}
+        if kind == 'integrate':
+            r = IntegrationRun(eng, state, plan, None)
+            for k in 'xace':
+                r.dst[0][k].copy_(prev0[k])
+            r.prev_idx = 0
+            fn = lambda: r.run(lo, lo + args.steps)
+        else:
+            fn = lambda: eng.integrate_mixed(state, [plan], group, start=[lo], n_steps=args.steps, prev=prev0)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / args.steps, state
+
+    finals = {}
+    for kind in ('integrate', 'mixed'):
+        for _ in range(args.warmup):
+            finals[kind] = timed(kind)[1]
+    same = all(torch.equal(finals['integrate'][k], finals['mixed'][k]) for k in finals['mixed'])
+    samples = {'integrate': [], 'mixed': []}
+    for _ in range(args.reps):
+        for kind in samples:                         # alternate inside every repetition
+            samples[kind].append(timed(kind)[0])
+    return {'mode': 'step', 'n_mols': args.n_mols, 'n_atoms': args.n_atoms, 'steps': args.steps, 'unit': 'ms per step', 'clock': 'device events',
+            'same_bits': same, 'timings': {k: summary(v) for k, v in samples.items()},
+            'mixed_over_integrate_median': statistics.median(samples['mixed']) / statistics.median(samples['integrate'])}
+
+
+def queue_mode(args, model):
+    n, T, R = args.n_atoms, args.T, args.requests
+
+    def queued():
+        q = model.sampling_queue(seed=SEED)
+        for i in range(R):
+            q.submit([n], n_timesteps=T, mol_ids=[i])
+            q.run(max_steps=args.gap if i < R - 1 else None)
+        while not q.idle:
+            q.run()
+        return q.pop_finished()
+
+    def alone():
+        return [model.sample(torch.tensor([n]), n_timesteps=T, rng='philox', seed=SEED, mol_ids=[i], return_tensors=True)[0] for i in range(R)]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    got, want = timed(queued)[1], timed(alone)[1]          # warm-up of both, and the results must agree
+    same = all(torch.equal(got[i].x_1, want[i]['x']) and torch.equal(got[i].e_1, want[i]['e'].long()) for i in range(R))
+    samples = {'queue': [], 'alone': []}
+    for _ in range(args.reps):
+        samples['queue'].append(timed(queued)[0])
+        samples['alone'].append(timed(alone)[0])
+    per = R * (T - 1)
+    return {'mode': 'queue', 'n_atoms': n, 'T': T, 'requests': R, 'gap': args.gap, 'clock': 'host clock around a device synchronise', 'same_bits': same,
+            'wall_ms': {k: summary(v) for k, v in samples.items()}, 'ms_per_molecule_step': {k: statistics.median(v) / per for k, v in samples.items()},
+            'includes': 'queue: admission (bind, prior, step 0), re-binds, result copies and packaging; alone: bind, prior, result copy'}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('mode', choices=['step', 'queue'])
+    ap.add_argument('--n_mols', type=int, default=1024)
+    ap.add_argument('--n_atoms', type=int, default=47)
+    ap.add_argument('--steps', type=int, default=16)
+    ap.add_argument('--T', type=int, default=250)
+    ap.add_argument('--requests', type=int, default=8)
+    ap.add_argument('--gap', type=int, default=25)
+    ap.add_argument('--reps', type=int, default=None)
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--out', type=Path, default=None)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit('time_mixed_step.py measures on the GPU; none is visible')
+    args.reps = args.reps or (7 if args.mode == 'step' else 3)
+    model = FlowMol.from_preset('flowmol3').to('cuda:0')
+    res = {'tool': 'time_mixed_step', 'device': torch.cuda.get_device_name(0), 'library_digest': build._digest(), 'reps': args.reps}
+    res.update(step_mode(args, model) if args.mode == 'step' else queue_mode(args, model))
+    line = json.dumps(res)
+    print(line)
+    if args.out is not None:
+        args.out.parent.mkdir(parents=True, exist_ok=True)
+        args.out.write_text(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
