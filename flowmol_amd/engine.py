@@ -7,6 +7,7 @@ arithmetic of the hot path happens in libflowmol_hip.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -100,21 +101,25 @@ def alpha_tables(t: torch.Tensor, schedule_type=None, cosine_params=None):
     return alpha, torch.cat(cols, dim=1)
 
 
+def euler_steps(n_timesteps: int, tspan: Optional[torch.Tensor] = None, schedule_type=None, cosine_params=None):
+    """The time points of an integration (``tspan``, or n_timesteps points on [0, 1]) and, per Euler step, (t_i, dt, alpha(t_i), alpha'(t_i)) with
+    the columns of ``alpha_tables``: what the CTMC plan and the endpoint integrator both walk (ctmc_vector_field.py:169-178, vector_field.py:430-434)."""
+    t = torch.linspace(0, 1, n_timesteps) if tspan is None else tspan.detach().to('cpu', torch.float32).clone()
+    alpha, alpha_p = alpha_tables(t, schedule_type, cosine_params)      # (T,4) each; may clamp t[0] in place (cosine)
+    return t, [(t[i - 1], t[i] - t[i - 1], alpha[i - 1], alpha_p[i - 1]) for i in range(1, t.shape[0])]
+
+
 def make_step_plan(n_timesteps: int, eta: float, hc_thresh: float, cat_temperature,
                    tspan: Optional[torch.Tensor] = None, dfm_type: str = 'campbell', forward_weight_func: Optional[Callable] = None,
                    inv_temp_func: Optional[Callable] = None, philox_seed: Optional[int] = None,
                    schedule_type=None, cosine_params=None) -> StepPlan:
     """Per-step scalars of CTMCVectorField.integrate/step (ctmc_vector_field.py:169-178, 287-340), computed with the
     reference's own float32 tensor arithmetic.  ``cat_temperature`` is a number or a callable of the 0-dim tensor t_i."""
-    t = torch.linspace(0, 1, n_timesteps) if tspan is None else tspan.detach().to('cpu', torch.float32).clone()
-    alpha, alpha_p = alpha_tables(t, schedule_type, cosine_params)      # (T,4) each; may clamp t[0] in place (cosine)
+    t, steps = euler_steps(n_timesteps, tspan, schedule_type, cosine_params)
     if dfm_type not in ('campbell', 'gat'):
         raise ValueError(f"Invalid dfm_type: {dfm_type}")
     out = []
-    for s_idx in range(1, t.shape[0]):
-        s_i, t_i = t[s_idx], t[s_idx - 1]
-        a_i, ap_i = alpha[s_idx - 1], alpha_p[s_idx - 1]      # columns x, a, c, e
-        dt = s_i - t_i
+    for s_idx, (t_i, dt, a_i, ap_i) in enumerate(steps, 1):      # a_i, ap_i: columns x, a, c, e
         sc = fm_step_scalars()
         sc.t = float(t_i)
         sc.dt = float(dt)
@@ -163,9 +168,20 @@ def mixed_step_arrays(plans: Sequence[StepPlan], start: Sequence[int], n_steps: 
     return scal, act, temb
 
 
+def noise_layout(last_step: bool, dfm_type: str = 'campbell', N: int = 0, U: int = 0, na: int = 0, nc: int = 0, ne: int = 0):
+    """(field, rows, width) of the noise tensors of one CTMC step in the reference's draw order -- per modality a, c, e: q Exp(1) (rows, K), u1 and
+    u2 uniform (rows,) [width None; u2 not drawn on the last step]; 'gat': q (rows, K + 1) only.  The one description every producer iterates."""
+    gat = dfm_type == 'gat'
+    for tag, rows, k in (('a', N, na), ('c', N, nc), ('e', U, ne)):
+        yield f'q_{tag}', rows, k + 1 if gat else k
+        if not gat:
+            yield f'u1_{tag}', rows, None
+            if not last_step:
+                yield f'u2_{tag}', rows, None
+
+
 class StepNoise:
-    """The nine noise tensors of one CTMC step, in the reference's draw order
-    (per modality a, c, e: Exp(1) (rows,K) -> rand(rows) -> rand(rows) [not drawn on the last step])."""
+    """The nine noise tensors of one CTMC step, in the reference's draw order (``noise_layout``); a tensor that is not drawn is None."""
     __slots__ = ('q_a', 'u1_a', 'u2_a', 'q_c', 'u1_c', 'u2_c', 'q_e', 'u1_e', 'u2_e')
 
     def __init__(self, **kw):
@@ -177,31 +193,18 @@ class StepNoise:
         """Draw with torch's generator on ``device`` exactly as the reference's ops would
         (torch.multinomial's Exp(1) draw, then the two torch.rand calls; 'gat': one Exp(1) draw over K+1 classes)."""
         out = {}
-        if dfm_type == 'gat':
-            for tag, rows, k in (('a', N, na), ('c', N, nc), ('e', U, ne)):
-                out[f'q_{tag}'] = torch.empty(rows, k + 1, device=device, dtype=torch.float32).exponential_(1, generator=generator)
-            return StepNoise(**out)
-        for tag, rows, k in (('a', N, na), ('c', N, nc), ('e', U, ne)):
-            out[f'q_{tag}'] = torch.empty(rows, k, device=device, dtype=torch.float32).exponential_(1, generator=generator)
-            out[f'u1_{tag}'] = torch.rand(rows, device=device, generator=generator)
-            out[f'u2_{tag}'] = None if last_step else torch.rand(rows, device=device, generator=generator)
+        for field, rows, width in noise_layout(last_step, dfm_type, N, U, na, nc, ne):
+            if width is None:
+                out[field] = torch.rand(rows, device=device, generator=generator)
+            else:
+                out[field] = torch.empty(rows, width, device=device, dtype=torch.float32).exponential_(1, generator=generator)
         return StepNoise(**out)
 
     @staticmethod
     def from_tape(tape: Sequence[torch.Tensor], pos: int, last_step: bool, device, dfm_type: str = 'campbell') -> "tuple[StepNoise, int]":
-        out = {}
-        if dfm_type == 'gat':
-            for tag in 'ace':
-                out[f'q_{tag}'] = tape[pos].to(device, torch.float32).contiguous(); pos += 1
-            return StepNoise(**out), pos
-        for tag in 'ace':
-            out[f'q_{tag}'] = tape[pos].to(device, torch.float32).contiguous(); pos += 1
-            out[f'u1_{tag}'] = tape[pos].to(device, torch.float32).contiguous(); pos += 1
-            if last_step:
-                out[f'u2_{tag}'] = None
-            else:
-                out[f'u2_{tag}'] = tape[pos].to(device, torch.float32).contiguous(); pos += 1
-        return StepNoise(**out), pos
+        fields = [f for f, _, _ in noise_layout(last_step, dfm_type)]
+        out = {f: tape[pos + i].to(device, torch.float32).contiguous() for i, f in enumerate(fields)}
+        return StepNoise(**out), pos + len(fields)
 
     def take_rows(self, node_rows: torch.Tensor, pair_rows: torch.Tensor) -> "StepNoise":
         """The draws of a subset of the batch's nodes / unordered pairs (sharded runs that replicate the full-batch noise)."""
@@ -293,10 +296,17 @@ class Engine:
 
     # ------------------------------------------------------------------ plumbing
     def _dev(self):
-        if self.device.type == 'cuda':
-            return torch.cuda.device(self.device)
-        import contextlib
-        return contextlib.nullcontext()
+        return torch.cuda.device(self.device) if self.device.type == 'cuda' else contextlib.nullcontext()
+
+    @contextlib.contextmanager
+    def _taps(self, taps: Optional[Dict[str, torch.Tensor]]):
+        """Taps set for the evaluation inside the block (stale ones cleared first), cleared again behind it."""
+        self.lib.fm_clear_taps(self._ctx)
+        for k, v in (taps or {}).items():
+            self._check(self.lib.fm_set_tap(self._ctx, k.encode(), _ptr(v)), 'fm_set_tap')
+        yield
+        if taps:
+            self.lib.fm_clear_taps(self._ctx)
 
     def _stream(self):
         if self.device.type == 'cuda':
@@ -396,10 +406,22 @@ class Engine:
         return s
 
     @staticmethod
-    def _state_struct(st) -> fm_state:
-        s = fm_state()
+    def _state_struct(st, struct=fm_state):
+        s = struct()
         s.x_t, s.a_t, s.c_t, s.e_t = _ptr(st['x_t']), _ptr(st['a_t']), _ptr(st['c_t']), _ptr(st['e_t'])
         return s
+
+    @staticmethod
+    def _dense_struct(st) -> fm_dense_state:
+        return Engine._state_struct(st, fm_dense_state)
+
+    def new_traj(self, n_steps: int) -> Dict[str, torch.Tensor]:
+        """The eight per-step frame buffers of a visualised run (fm_traj_sink): state 'x', 'a', 'c', 'e' after every step, endpoint predictions '*1'."""
+        f32, i32 = dict(device=self.device), dict(dtype=torch.int32, device=self.device)
+        return {'x': torch.empty(n_steps, self.N, 3, **f32), 'a': torch.empty(n_steps, self.N, **i32),
+                'c': torch.empty(n_steps, self.N, **i32), 'e': torch.empty(n_steps, self.U, **i32),
+                'x1': torch.empty(n_steps, self.N, 3, **f32), 'a1': torch.empty(n_steps, self.N, **i32),
+                'c1': torch.empty(n_steps, self.N, **i32), 'e1': torch.empty(n_steps, self.U, **i32)}
 
     def make_state(self, x_t, a_t, c_t, e_t) -> Dict[str, torch.Tensor]:
         """x_t (N,3) float; a_t, c_t (N) and e_t (U, per unordered pair in reference upper-edge order) int tokens."""
@@ -413,7 +435,6 @@ class Engine:
 
     def prior_state(self, x_0: torch.Tensor) -> Dict[str, torch.Tensor]:
         """CTMC masked prior for a, c, e (priors.py:101-107,305-316) around given positions."""
-        d = self.device
         return self.make_state(x_0, torch.full((self.N,), self.cfg.n_atom_types, dtype=torch.int32),
                                torch.full((self.N,), self.cfg.n_charges, dtype=torch.int32),
                                torch.full((self.U,), self.cfg.n_bond_types, dtype=torch.int32))
@@ -490,15 +511,9 @@ class Engine:
         sc = plan.scalars[step]
         if sc.noise_mode != FM_NOISE_PHILOX:
             raise ValueError('philox_tape needs a plan made with philox_seed')
-        cfg, d = self.cfg, self.device
-        gat = sc.dfm_type == FM_DFM_GAT
-        out = {}
-        for tag, rows, k in (('a', self.N, cfg.n_atom_types), ('c', self.N, cfg.n_charges), ('e', self.U, cfg.n_bond_types)):
-            out[f'q_{tag}'] = torch.empty(rows, k + 1 if gat else k, device=d)
-            if not gat:
-                out[f'u1_{tag}'] = torch.empty(rows, device=d)
-                out[f'u2_{tag}'] = None if sc.last_step else torch.empty(rows, device=d)
-        nz = StepNoise(**out)
+        cfg = self.cfg
+        layout = noise_layout(bool(sc.last_step), 'gat' if sc.dfm_type == FM_DFM_GAT else 'campbell', self.N, self.U, cfg.n_atom_types, cfg.n_charges, cfg.n_bond_types)
+        nz = StepNoise(**{f: torch.empty(*((rows,) if width is None else (rows, width)), device=self.device) for f, rows, width in layout})
         cs = nz.c_struct()
         with self._dev():
             self._check(self.lib.fm_philox_tape(self._ctx, self._stream(), C.byref(sc), C.byref(cs)), 'fm_philox_tape')
@@ -536,30 +551,18 @@ class Engine:
         st = self._state_struct(state)
         o = self._dst_struct(out)
         p = self._dst_struct(prev) if prev is not None else None
-        self.lib.fm_clear_taps(self._ctx)
-        if taps:
-            for k, v in taps.items():
-                self._check(self.lib.fm_set_tap(self._ctx, k.encode(), _ptr(v)), 'fm_set_tap')
-        with self._dev():
+        with self._taps(taps), self._dev():
             if mixed:
                 rc = self.lib.fm_forward_mixed(self._ctx, self._stream(), C.byref(st), _ptr(temb), int(vals.shape[0]), _ptr(group),
                                                C.byref(p) if p is not None else None, int(bool(bootstrap)), int(bool(remove_com)), C.byref(o))
             else:
                 rc = self.lib.fm_forward(self._ctx, self._stream(), C.byref(st), _ptr(temb), C.byref(p) if p is not None else None,
                                          int(bool(bootstrap)), int(bool(remove_com)), C.byref(o))
-        self._check(rc, 'fm_forward_mixed' if mixed else 'fm_forward')
-        if taps:
-            self.lib.fm_clear_taps(self._ctx)
+            self._check(rc, 'fm_forward_mixed' if mixed else 'fm_forward')
         self._keep = [temb, state, out, prev, group if mixed else None]
         return out
 
     # ------------------------------------------------------------------ endpoint parameterization (EndpointVectorField)
-    @staticmethod
-    def _dense_struct(st) -> fm_dense_state:
-        s = fm_dense_state()
-        s.x_t, s.a_t, s.c_t, s.e_t = _ptr(st['x_t']), _ptr(st['a_t']), _ptr(st['c_t']), _ptr(st['e_t'])
-        return s
-
     def make_dense_state(self, x_t, a_t, c_t, e_t) -> Dict[str, torch.Tensor]:
         """x_t (N,3), a_t (N,na), c_t (N,nc), e_t (U,ne): continuous features of an endpoint-parameterised model (copies)."""
         d = self.device
@@ -573,15 +576,8 @@ class Engine:
         out = out if out is not None else self.new_dst()
         temb = time_embedding_host(float(t), self.cfg.time_embedding_dim).to(self.device)
         st, o = self._dense_struct(state), self._dst_struct(out)
-        self.lib.fm_clear_taps(self._ctx)
-        if taps:
-            for k, v in taps.items():
-                self._check(self.lib.fm_set_tap(self._ctx, k.encode(), _ptr(v)), 'fm_set_tap')
-        with self._dev():
-            rc = self.lib.fm_forward_dense(self._ctx, self._stream(), C.byref(st), _ptr(temb), int(bool(remove_com)), C.byref(o))
-        self._check(rc, 'fm_forward_dense')
-        if taps:
-            self.lib.fm_clear_taps(self._ctx)
+        with self._taps(taps), self._dev():
+            self._check(self.lib.fm_forward_dense(self._ctx, self._stream(), C.byref(st), _ptr(temb), int(bool(remove_com)), C.byref(o)), 'fm_forward_dense')
         self._keep = [temb, state, out]
         return out
 
@@ -603,8 +599,7 @@ class Engine:
         ``traj`` (optional, vector_field.py:412-466 `visualize`): preallocated per-step frames -- 'x' (steps,N,3) and the argmax categories
         'a','c' (steps,N), 'e' (steps,U) of the state after each step, 'x1','a1','c1','e1' of the step's endpoint prediction."""
         cfg = self.cfg
-        t = torch.linspace(0, 1, n_timesteps) if tspan is None else tspan.detach().to('cpu', torch.float32).clone()
-        alpha, alpha_p = alpha_tables(t, cfg.schedule_type, cfg.cosine_params)
+        t, steps = euler_steps(n_timesteps, tspan, cfg.schedule_type, cfg.cosine_params)
         if inv_temp_func is None:
             if cfg.continuous_inv_temp_schedule == 'linear':
                 mx = cfg.continuous_inv_temp_max
@@ -612,12 +607,10 @@ class Engine:
             else:
                 inv_temp_func = lambda tt: 1.0
         dst = [self.new_dst(), self.new_dst()]
-        for s_idx in range(1, t.shape[0]):
-            s_i, t_i = t[s_idx], t[s_idx - 1]
-            a_i, ap_i = alpha[s_idx - 1], alpha_p[s_idx - 1]
+        for s_idx, (t_i, dt, a_i, ap_i) in enumerate(steps, 1):
             out = dst[s_idx & 1]
             self.forward_dense(state, float(t_i), remove_com=True, out=out)
-            self.endpoint_step(state, out, float(s_i - t_i), [float(ap_i[k] / (1 - a_i[k])) for k in range(4)], _f32(inv_temp_func(t_i)))
+            self.endpoint_step(state, out, float(dt), [float(ap_i[k] / (1 - a_i[k])) for k in range(4)], _f32(inv_temp_func(t_i)))
             if traj is not None:
                 f = s_idx - 1
                 traj['x'][f].copy_(state['x_t']); traj['x1'][f].copy_(out['x'])

@@ -13,15 +13,20 @@ from __future__ import annotations
 import json
 import os
 import pickle
+import time
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, List, Optional
 
 import torch
+import torch.distributed as dist
 
-from . import _lib, presets
+from . import _lib, presets, shard
 from .config import VFConfig, from_reference_hparams
 from .engine import Engine, StepNoise, cat_temp_schedule, forward_weight_schedule, make_step_plan
 from .molecule import SampledMolecule
+from .priors import (adapt_prior, categorical_prior, default_marginals, draw_categorical_priors,          # noqa: F401  (re-exported)
+                     load_marginal_dists, simplex_projection)
 from .weights import synth_state_dict
 
 PKG = Path(__file__).resolve().parent
@@ -32,27 +37,6 @@ def load_n_atoms_hist(name: str):
     if name not in data:
         raise KeyError(f'no size histogram named {name!r}; have {sorted(data)}')
     return torch.tensor(data[name]['n_atoms'], dtype=torch.int64), torch.tensor(data[name]['counts'], dtype=torch.int64)
-
-
-def load_marginal_dists(name: str):
-    """(p_a, p_c, p_e, p_c_given_a) of a dataset: the reference's data/<set>/train_data_marginal_dists.pt as shipped JSON."""
-    data = json.loads((PKG / 'data' / 'marginal_dists.json').read_text())
-    if name not in data:
-        raise KeyError(f'no marginal distributions named {name!r}; have {sorted(data)}')
-    d = data[name]
-    return tuple(torch.tensor(d[k], dtype=torch.float32) for k in ('p_a', 'p_c', 'p_e', 'p_c_given_a'))
-
-
-def simplex_projection(x: torch.Tensor) -> torch.Tensor:
-    """Euclidean projection of every row onto the probability simplex (Wang & Carreira-Perpinan, arXiv:1309.1541), the operation the
-    reference's blurred barycenter prior applies (priors.py:36-44 -> flowmol/utils/dirflow.py:35-49): with the row sorted descending,
-    u, and c_j = (sum_{i<=j} u_i - 1) / j, the threshold is c_rho for rho = #{j : u_j > c_j}; the result is max(x - c_rho, 0)."""
-    y = x.reshape(-1, x.shape[-1])
-    u, _ = torch.sort(y, dim=-1, descending=True)
-    c = (torch.cumsum(u, dim=-1) - 1) / torch.arange(1, y.shape[1] + 1, dtype=y.dtype, device=y.device).unsqueeze(0)
-    rho = (u > c).sum(dim=1, keepdim=True)
-    tau = torch.gather(c, 1, rho - 1)
-    return torch.max(y - tau, torch.zeros_like(y)).view(x.shape)
 
 
 class _Lenient(pickle.Unpickler):
@@ -148,6 +132,7 @@ class FlowMol:
         self.parameterization = cfg.parameterization
         self.device = torch.device('cpu')
         self._engine: Optional[Engine] = None
+        self.last_timing: Dict[str, object] = {}
         self.build_n_atoms_dist(n_atoms_hist or cfg.n_atoms_hist)
 
     # ------------------------------------------------------------------ construction
@@ -206,7 +191,11 @@ class FlowMol:
         """flowmol.py:468-471 (draws on the CPU generator like the reference)."""
         return self.n_atoms_map[self.n_atoms_dist.sample((n_molecules,), **kwargs)]
 
+    _categorical_prior = staticmethod(categorical_prior)
+
     # ------------------------------------------------------------------ sampling
+    # One call runs five stages, each one function: _request (arguments) -> bind -> _initial_state (prior) -> _plan_args + the engine's
+    # integrator -> _finish (to host, package).  sample_distributed and SamplingQueue enter the same stages.
     def sample_random_sizes(self, n_molecules: int, device=None, stochasticity=None, high_confidence_threshold=None,
                             xt_traj=False, ep_traj=False, **kwargs) -> List[SampledMolecule]:
         atoms_per_molecule = self.sample_n_atoms(n_molecules)
@@ -234,13 +223,8 @@ class FlowMol:
         batch: every rank keeps its molecules' rows, flowmol.py:534-545) and ``xt_traj`` / ``ep_traj`` (flowmol.py:564-589, test.py:212-257): each rank
         records its shard's frames in HBM in the compact token format and a SECOND all-gather (``shard.gather_frames``; only when trajectories
         are asked for) gives every rank the full batch's frames in the caller's order."""
-        import torch.distributed as dist
-        from . import shard
-        if _step_counts(n_timesteps) is not None:
-            raise NotImplementedError('sample_distributed with a sequence of n_timesteps: a mixed-time batch is not sharded across ranks')
-        if noise not in ('per_rank', 'replicated', 'philox'):
-            raise ValueError(f"noise must be 'per_rank', 'replicated' or 'philox', got {noise!r}")
-        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
+        req = self._request(n_atoms, n_timesteps, kwargs, noise=noise)       # every refusal before the first collective
+        n_atoms = req.n_atoms
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         parts = shard.partition_lpt(n_atoms, world)
         dev = self.engine.device
@@ -273,18 +257,8 @@ class FlowMol:
             i32 = dict(dtype=torch.int32, device=dev)
             local = {'x': torch.zeros(0, 3, device=dev), 'a': torch.zeros(0, **i32), 'c': torch.zeros(0, **i32), 'e': torch.zeros(0, **i32)}
         full_dev = shard.gather_results(local, n_atoms, parts, group=group)
-        frames_dev = None
-        if visualize:
-            ts = kwargs.get('tspan')
-            n_frames = (self.default_n_timesteps if n_timesteps is None else n_timesteps) if ts is None else int(ts.shape[0])
-            frames_dev = shard.gather_frames(local_frames, n_atoms, parts, n_frames, dev, group=group)
-        if return_tensors == 'device':
-            return (full_dev, n_atoms, frames_dev) if visualize else (full_dev, n_atoms)
-        full = _to_host(full_dev)            # one packed device->host copy of the whole gathered batch (1.7 KB/molecule)
-        frames = {k: v.cpu() for k, v in frames_dev.items()} if visualize else None
-        if return_tensors:
-            return (full, n_atoms, frames) if visualize else (full, n_atoms)
-        return self._package(full, n_atoms, frames, xt_traj, ep_traj)
+        frames_dev = shard.gather_frames(local_frames, n_atoms, parts, req.n_points, dev, group=group) if visualize else None
+        return self._finish({f'{k}_t': v for k, v in full_dev.items()}, n_atoms, frames_dev, return_tensors, visualize, xt_traj, ep_traj)
 
     @torch.no_grad()
     def sample(self, n_atoms: torch.Tensor, n_timesteps: int = None, device=None, stochasticity=None,
@@ -294,7 +268,9 @@ class FlowMol:
 
         RNG use mirrors the reference: ``randn(N,3)`` on the device for the position prior, then per step
         and per modality (a, c, e) ``Exp(1)`` of shape (rows, K), ``rand(rows)``, ``rand(rows)`` (the last
-        one skipped on the final step).
+        one skipped on the final step).  Endpoint-parameterised models (EndpointVectorField.integrate, vector_field.py:388-499: the categorical
+        modalities are continuous vectors integrated with the same Euler step as the positions; the sampled molecule takes their argmax) draw
+        ``randn(N,3)`` on the device, then the a, c, e priors on the CPU generator, and nothing per step.
 
         ``rng='philox'`` instead draws the prior and every step's noise inside the kernels from per-molecule counter-based streams
         (campbell and gat steps, and the priors of endpoint-parameterised models): no noise tensors, and a molecule's result depends only on
@@ -303,104 +279,91 @@ class FlowMol:
         ``model.sample(n_atoms, rng='philox', seed=s)`` on its own, bit for bit with canonical arithmetic (the default).
 
         ``n_timesteps`` may be a sequence of B ints, one per molecule (``rng='philox'``, campbell CTMC models): molecules with equal counts form a
-        time group, the groups advance together in one batch and a finished molecule waits until the call ends; ``n_timesteps[i] == 1`` returns
-        molecule *i*'s prior.  Molecule *i* is, bit for bit, ``model.sample(n_atoms[i:i+1], n_timesteps=n_timesteps[i], rng='philox', seed=s, mol_ids=[i])``.
-        Raises NotImplementedError for more than 32 distinct counts, rng='torch', dfm_type 'gat', endpoint models, xt_traj / ep_traj and tspan."""
+        time group, the groups advance together in one batch (one bind, one fm_integrate_mixed call) and a finished molecule waits until the call
+        ends; ``n_timesteps[i] == 1`` returns molecule *i*'s prior.  Molecule *i* is, bit for bit,
+        ``model.sample(n_atoms[i:i+1], n_timesteps=n_timesteps[i], rng='philox', seed=s, mol_ids=[i])``.
+        Raises NotImplementedError for more than 32 distinct counts, rng='torch', dfm_type 'gat', endpoint models, xt_traj / ep_traj and tspan.
+
+        ``return_tensors``: False -> a list of SampledMolecule; True -> (host tensors {'x','a','c','e'}, n_atoms); 'device' -> the same on the
+        device, unsynchronised with the host copy left out; 'dense' (endpoint models) -> the continuous final state instead of its argmax."""
         if device is not None and torch.device(device) != self.device:
             self.to(device)
-        counts = _step_counts(n_timesteps)
-        if counts is not None:
-            return self._sample_mixed(n_atoms, counts, stochasticity, high_confidence_threshold, xt_traj, ep_traj, prior, return_tensors, kwargs)
-        eng = self.engine
-        dev = eng.device
-        n_timesteps = self.default_n_timesteps if n_timesteps is None else n_timesteps
-        if self.cfg.parameterization == 'endpoint':
-            return self._sample_endpoint(n_atoms, n_timesteps, xt_traj, ep_traj, prior, return_tensors, kwargs)
-        # integrator variants of CTMCVectorField.integrate/step (ctmc_vector_field.py:145-156,287-315): all optional
-        dfm_type = kwargs.get('dfm_type') or self.cfg.dfm_type
-        if dfm_type not in ('campbell', 'gat'):
-            raise ValueError(f"Invalid dfm_type: {dfm_type}")
-        unknown = set(kwargs) - {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', '_rows', '_noise_for_step', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids', '_frames'}
-        if unknown:
-            raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
+        req = self._request(n_atoms, n_timesteps, kwargs, xt_traj, ep_traj)
+        eng, cfg, kw = self.engine, self.cfg, req.kw
+        eng.bind(req.n_atoms)
+        state, seed = self._initial_state(req, prior)
         visualize = bool(xt_traj or ep_traj)
-        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
-        eng.bind(n_atoms)
-        N, U = eng.N, eng.U
-        cfg = self.cfg
-        # ---- prior (flowmol.py:417-448 / 534-545)
-        rows = kwargs.get('_rows')     # sample_distributed(noise='replicated'): (N_full, U_full, node rows, pair rows) of this shard
-        # rng='philox': position prior and CTMC noise come from per-molecule counter-based streams inside the kernels (no noise
-        # tensors; results independent of batch composition / sharding).  rng='torch' (default): the reference's draws from torch's generator.
+        traj = init = None
+        if visualize:        # frames as tokens (the molecule of an endpoint model's frame is its argmax, molecule_builder.py:231-247) + fp32 coordinates
+            traj, init = eng.new_traj(req.n_points - 1), _tokens(state, copy=True)
+        if req.path == 'endpoint':
+            integrate = lambda: eng.integrate_endpoint(state, req.n_timesteps, inv_temp_func=kw.get('inv_temp_func'), tspan=kw.get('tspan'), traj=traj)
+        else:
+            args, plan_kw = self._plan_args(stochasticity, high_confidence_threshold, kw, req.dfm_type)
+            if req.path == 'mixed':
+                distinct = sorted(set(req.counts))
+                plans = [make_step_plan(T, *args, philox_seed=seed, **plan_kw) for T in distinct]
+                integrate = lambda: eng.integrate_mixed(state, plans, [distinct.index(T) for T in req.counts])
+            else:
+                plan = make_step_plan(req.n_timesteps, *args, philox_seed=seed, **plan_kw)
+                rows = kw.get('_rows')     # sample_distributed(noise='replicated'): (N_full, U_full, node rows, pair rows): draw the full batch's noise, keep this shard's
+                nN, nU = (eng.N, eng.U) if rows is None else rows[:2]
+
+                def noise_for_step(i, last):
+                    nz = StepNoise.draw(nN, nU, cfg.n_atom_types, cfg.n_charges, cfg.n_bond_types, last, eng.device, dfm_type=req.dfm_type)
+                    return nz if rows is None else nz.take_rows(rows[2], rows[3])
+                # _noise_for_step(i, last) -> StepNoise: recorded draws instead of torch's generator (parity tests drive the public API with
+                # the oracle's RNG tape); never set by the product itself.  A Philox plan draws inside the kernels: no callback
+                noise = None if seed is not None else (kw.get('_noise_for_step') or noise_for_step)
+                integrate = lambda: eng.integrate(state, plan, noise, traj=traj)
+        t0 = time.perf_counter()
+        integrate()          # every integrator synchronises at its end
+        t_integrate = time.perf_counter() - t0
+        frames_in_tuple = bool(kw.get('_frames')) and return_tensors == 'device'      # sample_distributed: this shard's frames stay in HBM for the second gather
+        frames = _frames_of(init, traj) if visualize and (frames_in_tuple or not return_tensors) else None
+        return self._finish(state, req.n_atoms, frames, return_tensors, frames_in_tuple, xt_traj, ep_traj, t_integrate)
+
+    # ---- stage 1: arguments
+    def _request(self, n_atoms, n_timesteps, kwargs, xt_traj=False, ep_traj=False, noise=None) -> "_Request":
+        """What every entry point does first: name the path, refuse what it does not take -- before the bind and before any draw from a generator --
+        and normalise the rest (``n_atoms`` a CPU int64 tensor, the default step count, ``seed`` / ``mol_ids`` and their earlier spellings ``_philox``
+        / ``_mol_ids``).  ``noise``: the noise mode of a ``sample_distributed`` call, whose ``kwargs`` still hold sample()'s named arguments."""
+        counts = _step_counts(n_timesteps)
+        if noise is not None:
+            if counts is not None:
+                raise NotImplementedError('sample_distributed with a sequence of n_timesteps: a mixed-time batch is not sharded across ranks')
+            if noise not in ('per_rank', 'replicated', 'philox'):
+                raise ValueError(f"noise must be 'per_rank', 'replicated' or 'philox', got {noise!r}")
+            kwargs = {k: v for k, v in kwargs.items() if k not in SAMPLE_NAMED_ARGS}         # as the shard's sample() call will see them
+            kwargs.update({'philox': {'rng': 'philox'}, 'replicated': {'_rows': ()}}.get(noise, {}))
+        path = 'mixed' if counts is not None else ('endpoint' if self.cfg.parameterization == 'endpoint' else 'ctmc')
+        if path == 'mixed':
+            self._check_mixed(kwargs, xt_traj, ep_traj)
         rng = kwargs.get('rng', 'torch')
         if rng not in ('torch', 'philox'):
             raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
-        philox_seed = None
-        if rng == 'philox':
-            if rows is not None or kwargs.get('_noise_for_step') is not None:
-                raise NotImplementedError("rng='philox' draws inside the kernels: it does not combine with replicated row slicing (_rows) or a noise callback (_noise_for_step)")
-            philox_seed = self._philox_setup(kwargs)
-        if prior is None and philox_seed is not None:
-            state = eng.prior_state(eng.prior_philox(philox_seed))
-        elif prior is None:
-            x0 = torch.randn(N, 3, device=dev) if rows is None else torch.randn(rows[0], 3, device=dev)[rows[2]].contiguous()
-            eng.remove_com(x0)
-            state = eng.prior_state(x0)
+        # integrator variants of CTMCVectorField.integrate/step (ctmc_vector_field.py:145-156,287-315): all optional
+        dfm_type = kwargs.get('dfm_type') or self.cfg.dfm_type
+        if path != 'endpoint' and dfm_type not in ('campbell', 'gat'):
+            raise ValueError(f"Invalid dfm_type: {dfm_type}")
+        unknown = set(kwargs) - ALLOWED_KWARGS[path]
+        if unknown:
+            raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
+        if rng == 'philox' and (kwargs.get('_rows') is not None or kwargs.get('_noise_for_step') is not None):
+            raise NotImplementedError("rng='philox' draws inside the kernels: it does not combine with replicated row slicing (_rows) or a noise callback (_noise_for_step)")
+        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
+        if counts is None:
+            n_timesteps = self.default_n_timesteps if n_timesteps is None else n_timesteps
         else:
-            state = self._state_from_prior(prior)
-        eta = cfg.stochasticity if stochasticity is None else stochasticity
-        hc = cfg.high_confidence_threshold if high_confidence_threshold is None else high_confidence_threshold
-        ctf = kwargs.get('cat_temp_func') or cat_temp_schedule(cfg)
-        fwf = kwargs.get('forward_weight_func') or forward_weight_schedule(cfg)
-        plan = make_step_plan(n_timesteps, eta, hc, ctf, tspan=kwargs.get('tspan'), dfm_type=dfm_type,
-                              forward_weight_func=fwf, inv_temp_func=kwargs.get('inv_temp_func'), philox_seed=philox_seed,
-                              schedule_type=cfg.schedule_type, cosine_params=cfg.cosine_params)
-        n_steps = len(plan.scalars)
-        traj = None
-        if visualize:
-            i32 = dict(dtype=torch.int32, device=dev)
-            traj = {'x': torch.empty(n_steps, N, 3, device=dev), 'a': torch.empty(n_steps, N, **i32),
-                    'c': torch.empty(n_steps, N, **i32), 'e': torch.empty(n_steps, U, **i32),
-                    'x1': torch.empty(n_steps, N, 3, device=dev), 'a1': torch.empty(n_steps, N, **i32),
-                    'c1': torch.empty(n_steps, N, **i32), 'e1': torch.empty(n_steps, U, **i32)}
-            init = {k: state[f'{k}_t'].clone() for k in 'xace'}
-
-        def noise_for_step(i, last):
-            if rows is None:
-                return StepNoise.draw(N, U, cfg.n_atom_types, cfg.n_charges, cfg.n_bond_types, last, dev, dfm_type=dfm_type)
-            full = StepNoise.draw(rows[0], rows[1], cfg.n_atom_types, cfg.n_charges, cfg.n_bond_types, last, dev, dfm_type=dfm_type)
-            return full.take_rows(rows[2], rows[3])
-
-        import time
-        t0 = time.perf_counter()
-        # _noise_for_step(i, last) -> StepNoise: recorded draws instead of torch's generator (parity tests drive the public API with
-        # the oracle's RNG tape); never set by the product itself
-        eng.integrate(state, plan, None if philox_seed is not None else (kwargs.get('_noise_for_step') or noise_for_step), traj=traj)          # synchronises at the end
-        t1 = time.perf_counter()
-        out_dev = {k: state[f'{k}_t'] for k in 'xace'}
-        if return_tensors == 'device':
-            self.last_timing = {'integrate': t1 - t0, 'precision': eng.precision}
-            if kwargs.get('_frames'):          # sample_distributed: this shard's frames stay in HBM for the second gather
-                return out_dev, n_atoms, (_frames_of(init, traj) if visualize else None)
-            return out_dev, n_atoms
-        out = _to_host(out_dev)
-        t2 = time.perf_counter()
-        self.last_timing = {'integrate': t1 - t0, 'to_host': t2 - t1, 'precision': eng.precision}
-        if return_tensors:
-            return out, n_atoms
-        frames = {k: v.cpu() for k, v in _frames_of(init, traj).items()} if visualize else None
-        mols = self._package(out, n_atoms, frames, xt_traj, ep_traj)
-        self.last_timing['package'] = time.perf_counter() - t2
-        return mols
-
-    def _mixed_plan_args(self, stochasticity, high_confidence_threshold, kwargs):
-        """What make_step_plan takes besides the step count and the seed, as sample() passes it (campbell)."""
-        cfg = self.cfg
-        eta = cfg.stochasticity if stochasticity is None else stochasticity
-        hc = cfg.high_confidence_threshold if high_confidence_threshold is None else high_confidence_threshold
-        return (eta, hc, kwargs.get('cat_temp_func') or cat_temp_schedule(cfg)), dict(
-            dfm_type='campbell', forward_weight_func=kwargs.get('forward_weight_func') or forward_weight_schedule(cfg), inv_temp_func=kwargs.get('inv_temp_func'),
-            schedule_type=cfg.schedule_type, cosine_params=cfg.cosine_params)
+            if len(counts) != n_atoms.numel():
+                raise ValueError(f'n_timesteps has {len(counts)} entries for {n_atoms.numel()} molecules')
+            if min(counts) < 1:
+                raise ValueError('n_timesteps must be >= 1')
+            if len(set(counts)) > _lib.FM_TAB_SLOTS:
+                raise NotImplementedError(f'more than {_lib.FM_TAB_SLOTS} distinct step counts in one batch ({len(set(counts))}): split the call')
+        seed = kwargs.get('seed') if kwargs.get('seed') is not None else kwargs.get('_philox')
+        ids = kwargs.get('mol_ids') if kwargs.get('mol_ids') is not None else kwargs.get('_mol_ids')
+        return _Request(path, n_atoms, n_timesteps, counts, rng, dfm_type, None if seed is None else int(seed), ids, kwargs)
 
     def _check_mixed(self, kwargs, xt_traj=False, ep_traj=False):
         """The combinations per-molecule step counts do not cover, each refused by name."""
@@ -415,212 +378,81 @@ class FlowMol:
         if kwargs.get('tspan') is not None:
             raise NotImplementedError('per-molecule n_timesteps: tspan is one schedule for the whole batch')
 
-    def _sample_mixed(self, n_atoms, counts, stochasticity, high_confidence_threshold, xt_traj, ep_traj, prior, return_tensors, kwargs):
-        """sample() with one step count per molecule: one bind, one fm_integrate_mixed call."""
-        self._check_mixed(kwargs, xt_traj, ep_traj)
-        unknown = set(kwargs) - {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids'}
-        if unknown:
-            raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
-        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
-        if len(counts) != n_atoms.numel():
-            raise ValueError(f'n_timesteps has {len(counts)} entries for {n_atoms.numel()} molecules')
-        if min(counts) < 1:
-            raise ValueError('n_timesteps must be >= 1')
-        distinct = sorted(set(counts))
-        if len(distinct) > _lib.FM_TAB_SLOTS:
-            raise NotImplementedError(f'more than {_lib.FM_TAB_SLOTS} distinct step counts in one batch ({len(distinct)}): split the call')
-        eng = self.engine
-        eng.bind(n_atoms)
-        seed = self._philox_setup(kwargs)
-        state = eng.prior_state(eng.prior_philox(seed)) if prior is None else self._state_from_prior(prior)
-        args, kw = self._mixed_plan_args(stochasticity, high_confidence_threshold, kwargs)
-        plans = [make_step_plan(T, *args, philox_seed=seed, **kw) for T in distinct]
-        import time
-        t0 = time.perf_counter()
-        eng.integrate_mixed(state, plans, [distinct.index(T) for T in counts])
-        eng.synchronize()
-        t1 = time.perf_counter()
-        out_dev = {k: state[f'{k}_t'] for k in 'xace'}
-        self.last_timing = {'integrate': t1 - t0, 'precision': eng.precision}
-        if return_tensors == 'device':
-            return out_dev, n_atoms
-        out = _to_host(out_dev)
-        if return_tensors:
-            return out, n_atoms
-        return self._package(out, n_atoms, None, False, False)
+    # ---- stage 2: what make_step_plan takes
+    def _plan_args(self, stochasticity, high_confidence_threshold, kwargs, dfm_type='campbell'):
+        """(args, kwargs) of ``make_step_plan`` besides the step count and the Philox seed: stochasticity and confidence threshold (default: the
+        model's), the temperature and forward-weight schedules (default: the configured ones) and the caller's tspan / inv_temp_func."""
+        cfg = self.cfg
+        eta = cfg.stochasticity if stochasticity is None else stochasticity
+        hc = cfg.high_confidence_threshold if high_confidence_threshold is None else high_confidence_threshold
+        return (eta, hc, kwargs.get('cat_temp_func') or cat_temp_schedule(cfg)), dict(
+            tspan=kwargs.get('tspan'), dfm_type=dfm_type, forward_weight_func=kwargs.get('forward_weight_func') or forward_weight_schedule(cfg),
+            inv_temp_func=kwargs.get('inv_temp_func'), schedule_type=cfg.schedule_type, cosine_params=cfg.cosine_params)
 
-    def sampling_queue(self, seed: int, stochasticity=None, high_confidence_threshold=None, **kwargs) -> "SamplingQueue":
-        """A queue that admits requests into a batch that is already running (flowmol_amd.sampling_queue.SamplingQueue)."""
-        from .sampling_queue import SamplingQueue
-        return SamplingQueue(self, seed, stochasticity=stochasticity, high_confidence_threshold=high_confidence_threshold, **kwargs)
+    def _mixed_plan_args(self, stochasticity, high_confidence_threshold, kwargs):
+        return self._plan_args(stochasticity, high_confidence_threshold, kwargs)
 
-    def _philox_setup(self, kwargs) -> int:
-        """Seed and molecule ids of a Philox run: ``seed`` / ``mol_ids`` (``_philox`` / ``_mol_ids`` are their earlier, private spellings)."""
-        seed = kwargs.get('seed') if kwargs.get('seed') is not None else kwargs.get('_philox')
-        if seed is None:                              # one 62-bit seed per call from torch's CPU generator: torch.manual_seed controls it
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        ids = kwargs.get('mol_ids') if kwargs.get('mol_ids') is not None else kwargs.get('_mol_ids')
-        self.engine.set_molecule_ids(None if ids is None else torch.as_tensor(ids))
-        return int(seed)
-
-    # ------------------------------------------------------------------ endpoint-parameterised models
-    @staticmethod
-    def _categorical_prior(kind: str, n: int, d: int, kw: dict, a_0: Optional[torch.Tensor] = None, default_p=None) -> torch.Tensor:
-        """The reference's categorical prior functions on the CPU generator, as FlowMol.sample_prior calls them (priors.py:8-107;
-        flowmol.py:426-441) -- same draws in the same order.  'marginal' / 'c-given-a' take their distribution from the prior kwargs
-        (`p` / `p_c_given_a`, as the reference would) or, when absent, from the shipped marginals of the model's dataset (`default_p`)."""
-        F = torch.nn.functional
-        if kind == 'gaussian':
-            p = torch.randn(n, d) * kw.get('std', 1.0)
-            return p + 1 / d if kw.get('simplex_center', False) else p
-        if kind == 'uniform-simplex':
-            sample = torch.distributions.Exponential(torch.tensor(1.0)).sample((n, d))
-            return sample / sample.sum(dim=1, keepdim=True)
-        if kind == 'barycenter':
-            p = torch.ones(n, d) / d
-            blur = kw.get('blur', 0.0)
-            if blur != 0.0:
-                p = simplex_projection(p + torch.randn_like(p) * blur)
-            return p
-        if kind == 'biased-simplex':          # priors.py:47-56
-            vp, std, vi = kw.get('vertex_prob', 0.75), kw.get('std', 0.2), kw.get('vertex_idx', 0)
-            mu = torch.ones(d) * ((1 - vp) / (d - 1))
-            mu[vi] = vp
-            return F.softmax((mu.unsqueeze(0) + torch.randn(n, d) * std) / (1 / d), dim=1)
-        if kind in ('marginal', 'c-given-a'):
-            key = 'p' if kind == 'marginal' else 'p_c_given_a'
-            p = kw.get(key, default_p)
-            if p is None:
-                raise ValueError(f"prior {kind!r} needs kwargs[{key!r}] (or a dataset whose shipped marginals have {d} categories)")
-            p = torch.as_tensor(p, dtype=torch.float32)
-            if p.shape[-1] != d:
-                raise ValueError(f"prior {kind!r}: distribution has {p.shape[-1]} categories, the model {d}")
-            if kind == 'marginal':            # priors.py:67-79
-                idx = torch.multinomial(p, n, replacement=True)
-            else:                             # priors.py:81-98: charges conditioned on the sampled atom-type prior
-                if a_0 is None:
-                    raise ValueError("the 'c-given-a' prior needs the atom-type prior")
-                idx = torch.multinomial(p[a_0.argmax(dim=1)], 1, replacement=True).squeeze(-1)
-            one = F.one_hot(idx, num_classes=d).float()
-            blur = kw.get('blur')
-            if blur is not None:
-                one = F.softmax((one + torch.randn_like(one) * blur) / (1 / d), dim=1)
-            return one
-        raise NotImplementedError(f'prior type {kind!r}')
-
-    def _default_marginal(self, feat: str, d: int):
-        """Shipped marginals of the model's dataset for the 'marginal' / 'c-given-a' priors, when their category count fits."""
-        try:
-            p_a, p_c, p_e, p_ca = load_marginal_dists(self.cfg.n_atoms_hist)
-        except KeyError:
-            return None
-        p = {'a': p_a, 'c': p_c, 'e': p_e, 'c|a': p_ca}[feat]
-        return p if p.shape[-1] == d else None
-
-    def _sample_endpoint(self, n_atoms, n_timesteps, xt_traj, ep_traj, prior, return_tensors, kwargs):
-        """FlowMol.sample for parameterization='endpoint' (flowmol.py:489-589 with EndpointVectorField.integrate, vector_field.py:388-499):
-        the categorical modalities are continuous vectors integrated with the same Euler step as the positions; the sampled
-        molecule takes their argmax.  RNG order = the reference's: randn(N,3) on the device, then a, c, e priors on the CPU generator."""
-        rng = kwargs.get('rng', 'torch')
-        if rng not in ('torch', 'philox'):
-            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
-        unknown = set(kwargs) - {'inv_temp_func', 'tspan', '_rows', 'rng', 'seed', 'mol_ids', '_philox', '_mol_ids', '_frames'}
-        if unknown:
-            raise TypeError(f'sample() got unexpected keyword arguments {sorted(unknown)}')
-        if rng == 'philox' and kwargs.get('_rows') is not None:
-            raise NotImplementedError("rng='philox' draws inside the kernels: it does not combine with replicated row slicing (_rows)")
+    # ---- stage 3: prior
+    def _initial_state(self, req: "_Request", prior):
+        """The initial state of the bound batch, and the Philox seed of the run (None with rng='torch').  A caller's ``prior`` dict is adapted to the
+        model; without one the prior is drawn: inside the kernels from the per-molecule Philox streams, or with torch's generators in the reference's
+        order (flowmol.py:417-448 / 534-545).  An endpoint model's own ``x_0`` is centred here; a caller's is taken as it is."""
         eng, cfg = self.engine, self.cfg
-        dev = eng.device
-        n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64)
-        eng.bind(n_atoms)
-        N, U = eng.N, eng.U
-        rows = kwargs.get('_rows')      # sample_distributed(noise='replicated'): (N_full, U_full, node rows, pair rows) -- draw the full batch's priors, keep this shard's
-        if prior is None and rng == 'philox':
-            # the whole prior in one launch from the per-molecule streams (fm_prior_philox_dense); the integration itself is deterministic
-            seed = self._philox_setup(kwargs)
-            ck = cfg.prior_types['c']
-            p0 = eng.prior_philox_dense(seed, default_p={'a': self._default_marginal('a', cfg.n_atom_types), 'e': self._default_marginal('e', cfg.n_bond_types),
-                                                         'c': self._default_marginal('c|a' if ck == 'c-given-a' else 'c', cfg.n_charges)})
-            x0, a0, c0, e0 = p0['x_t'], p0['a_t'], p0['c_t'], p0['e_t']
-        elif prior is None:
-            nN, nU = (rows[0], rows[1]) if rows is not None else (N, U)
-            x0 = torch.randn(nN, 3, device=dev)
-            pk = cfg.prior_kwargs
-            a0 = self._categorical_prior(cfg.prior_types['a'], nN, cfg.n_atom_types, pk.get('a', {}), default_p=self._default_marginal('a', cfg.n_atom_types))
-            c_kind = cfg.prior_types['c']
-            c0 = self._categorical_prior(c_kind, nN, cfg.n_charges, pk.get('c', {}), a_0=a0,
-                                         default_p=self._default_marginal('c|a' if c_kind == 'c-given-a' else 'c', cfg.n_charges))
-            e0 = self._categorical_prior(cfg.prior_types['e'], nU, cfg.n_bond_types, pk.get('e', {}), default_p=self._default_marginal('e', cfg.n_bond_types))
-            if rows is not None:
-                x0 = x0[rows[2]].contiguous()
-                a0, c0, e0 = a0[rows[2].cpu()], c0[rows[2].cpu()], e0[rows[3].cpu()]
-            eng.remove_com(x0)          # per molecule, so centring after the row selection equals centring the full batch
-        else:
-            x0, a0, c0 = prior['x_0'], prior['a_0'], prior['c_0']
-            # the reference adapts a prior drawn with / without the fake-atom column to the model (flowmol.py:540-545)
-            if prior.get('fake_atoms', False) and not self.fake_atoms:
-                a0 = a0[:, 1:]
-            elif not prior.get('fake_atoms', False) and self.fake_atoms and a0.shape[-1] == cfg.n_atom_types - 1:
-                a0 = torch.cat([torch.zeros(a0.shape[0], 1, device=a0.device, dtype=a0.dtype), a0], dim=-1)
+        endpoint, rows = req.path == 'endpoint', req.kw.get('_rows')
+        seed = None
+        if req.rng == 'philox' and not (endpoint and prior is not None):      # an endpoint run is deterministic behind its prior: a given prior needs no seed
+            # one 62-bit seed per call from torch's CPU generator (torch.manual_seed controls it), drawn behind the bind
+            seed = req.seed if req.seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+            eng.set_molecule_ids(None if req.mol_ids is None else torch.as_tensor(req.mol_ids))
+        if prior is not None:
+            x0, a0, c0, e0 = adapt_prior(prior, req.n_atoms, cfg, eng.E, only_missing_column=endpoint)
+            if not endpoint:
+                return eng.make_state(x0, a0.argmax(-1), c0.argmax(-1), e0.argmax(-1)), seed
+            N = eng.N
             if a0.shape != (N, cfg.n_atom_types) or c0.shape != (N, cfg.n_charges) or tuple(x0.shape) != (N, 3):
                 raise ValueError(f"prior shapes x_0 {tuple(x0.shape)}, a_0 {tuple(a0.shape)}, c_0 {tuple(c0.shape)} do not fit the batch "
                                  f"({N} atoms, {cfg.n_atom_types} atom types, {cfg.n_charges} charges)")
-            e0 = prior['e_0']
-            if e0.shape[0] == eng.E:          # directed edges, upper block first per molecule -> keep the upper halves
-                idx, off = [], 0
-                for k in n_atoms.tolist():
-                    u = k * (k - 1) // 2
-                    idx.append(torch.arange(off, off + u))
-                    off += 2 * u
-                e0 = e0[torch.cat(idx)]
-        state = eng.make_dense_state(x0, a0, c0, e0)
-        visualize = bool(xt_traj or ep_traj)
-        traj = None
-        if visualize:        # frames as category indices (the molecule of a frame is its argmax, molecule_builder.py:231-247) + fp32 coordinates
-            ts = kwargs.get('tspan')
-            n_steps = (n_timesteps if ts is None else int(ts.shape[0])) - 1
-            i32 = dict(dtype=torch.int32, device=dev)
-            traj = {'x': torch.empty(n_steps, N, 3, device=dev), 'a': torch.empty(n_steps, N, **i32),
-                    'c': torch.empty(n_steps, N, **i32), 'e': torch.empty(n_steps, U, **i32),
-                    'x1': torch.empty(n_steps, N, 3, device=dev), 'a1': torch.empty(n_steps, N, **i32),
-                    'c1': torch.empty(n_steps, N, **i32), 'e1': torch.empty(n_steps, U, **i32)}
-            init = {'x': state['x_t'].clone(), 'a': state['a_t'].argmax(-1).int(), 'c': state['c_t'].argmax(-1).int(), 'e': state['e_t'].argmax(-1).int()}
-        import time
-        t0 = time.perf_counter()
-        eng.integrate_endpoint(state, n_timesteps, inv_temp_func=kwargs.get('inv_temp_func'), tspan=kwargs.get('tspan'), traj=traj)
-        self.last_timing = {'integrate': time.perf_counter() - t0, 'precision': eng.precision}
-        if return_tensors == 'dense':
-            return {k: state[f'{k}_t'] for k in 'xace'}, n_atoms
-        out_dev = {'x': state['x_t'], 'a': state['a_t'].argmax(-1).int(), 'c': state['c_t'].argmax(-1).int(), 'e': state['e_t'].argmax(-1).int()}
-        if return_tensors == 'device':
-            if kwargs.get('_frames'):
-                return out_dev, n_atoms, (_frames_of(init, traj) if visualize else None)
-            return out_dev, n_atoms
-        out = _to_host(out_dev)
-        if return_tensors:
-            return out, n_atoms
-        frames = {k: v.cpu() for k, v in _frames_of(init, traj).items()} if visualize else None
-        return self._package(out, n_atoms, frames, xt_traj, ep_traj)
+        elif seed is not None and not endpoint:
+            return eng.prior_state(eng.prior_philox(seed)), seed
+        elif seed is not None:          # the whole prior in one launch (fm_prior_philox_dense)
+            p0 = eng.prior_philox_dense(seed, default_p=default_marginals(cfg))
+            x0, a0, c0, e0 = p0['x_t'], p0['a_t'], p0['c_t'], p0['e_t']
+        else:                           # rows: draw the full batch's prior, keep this shard's
+            nN, nU = (eng.N, eng.U) if rows is None else rows[:2]
+            x0 = torch.randn(nN, 3, device=eng.device)
+            if endpoint:
+                a0, c0, e0 = draw_categorical_priors(cfg, nN, nU, default_p=default_marginals(cfg))
+            if rows is not None:
+                x0 = x0[rows[2]].contiguous()
+                if endpoint:
+                    a0, c0, e0 = a0[rows[2].cpu()], c0[rows[2].cpu()], e0[rows[3].cpu()]
+            eng.remove_com(x0)          # per molecule, so centring after the row selection equals centring the full batch
+            if not endpoint:
+                return eng.prior_state(x0), seed
+        return eng.make_dense_state(x0, a0, c0, e0), seed
 
-    # ------------------------------------------------------------------ helpers
-    def _state_from_prior(self, prior):
-        """Reference-format prior dict: x_0 (N,3), a_0/c_0 one-hot (N,*), e_0 one-hot (E,*) in reference edge order."""
-        eng = self.engine
-        a0 = prior['a_0']
-        if prior.get('fake_atoms', False) and not self.fake_atoms:
-            a0 = a0[:, 1:]
-        elif not prior.get('fake_atoms', False) and self.fake_atoms:
-            a0 = torch.cat([torch.zeros(a0.shape[0], 1, device=a0.device), a0], dim=-1)
-        e0 = prior['e_0']
-        n = eng.n_atoms
-        if e0.shape[0] == eng.E:      # directed edges, upper block first per molecule -> keep the upper halves
-            idx, off = [], 0
-            for k in n.tolist():
-                u = k * (k - 1) // 2
-                idx.append(torch.arange(off, off + u))
-                off += 2 * u
-            e0 = e0[torch.cat(idx)]
-        return eng.make_state(prior['x_0'], a0.argmax(-1), prior['c_0'].argmax(-1), e0.argmax(-1))
+    # ---- stage 4: epilogue
+    def _finish(self, state, n_atoms, frames, return_tensors, frames_in_tuple, xt_traj, ep_traj, t_integrate=None):
+        """The final state on the device (tokens, or an endpoint model's continuous features) -> what the caller asked for with ``return_tensors``
+        ('dense' | 'device' | True | False, see ``sample``); ``frames``: the run's frames on the device, where they stay for 'device'; ``frames_in_tuple``:
+        the tensor forms return (out, n_atoms, frames).  ``last_timing``: 'integrate' and 'precision' (as set by the shard's sample() when
+        ``t_integrate`` is None), 'to_host' when the result was copied and 'package' when molecules were built."""
+        if t_integrate is not None:
+            self.last_timing = {'integrate': t_integrate, 'precision': self.engine.precision}
+        if return_tensors == 'dense' and state['a_t'].dim() == 2:
+            return {k: state[f'{k}_t'] for k in 'xace'}, n_atoms
+        out, t1 = _tokens(state), time.perf_counter()
+        if return_tensors != 'device':
+            out = _to_host(out)            # one packed device->host copy of the whole batch (1.7 KB/molecule)
+            self.last_timing['to_host'] = time.perf_counter() - t1
+            t2 = time.perf_counter()
+            if frames is not None and (frames_in_tuple or not return_tensors):
+                frames = {k: v.cpu() for k, v in frames.items()}
+        if return_tensors:
+            return (out, n_atoms, frames) if frames_in_tuple else (out, n_atoms)
+        mols = self._package(out, n_atoms, frames, xt_traj, ep_traj)
+        self.last_timing['package'] = time.perf_counter() - t2
+        return mols
 
     def _package(self, out, n_atoms, frames, xt_traj, ep_traj) -> List[SampledMolecule]:
         """Host tensors of the whole batch -> one SampledMolecule per molecule, in batch order (flowmol.py:564-589)."""
@@ -639,6 +471,41 @@ class FlowMol:
                                         build_xt_traj=xt_traj, build_ep_traj=ep_traj, n_charges=self.n_atom_charges))
         return mols
 
+    def sampling_queue(self, seed: int, stochasticity=None, high_confidence_threshold=None, **kwargs) -> "SamplingQueue":
+        """A queue that admits requests into a batch that is already running (flowmol_amd.sampling_queue.SamplingQueue)."""
+        from .sampling_queue import SamplingQueue
+        return SamplingQueue(self, seed, stochasticity=stochasticity, high_confidence_threshold=high_confidence_threshold, **kwargs)
+
+
+# what sample() names itself; everything else arrives in **kwargs and is checked against the path's table
+SAMPLE_NAMED_ARGS = ('device', 'stochasticity', 'high_confidence_threshold', 'xt_traj', 'ep_traj', 'prior')
+_PHILOX_KWARGS = {'rng', 'seed', 'mol_ids', '_philox', '_mol_ids'}
+ALLOWED_KWARGS = {
+    'ctmc': {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func', '_rows', '_noise_for_step', '_frames'} | _PHILOX_KWARGS,
+    'endpoint': {'inv_temp_func', 'tspan', '_rows', '_frames'} | _PHILOX_KWARGS,
+    'mixed': {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'} | _PHILOX_KWARGS,
+}
+
+
+@dataclass
+class _Request:
+    """One sample() call behind the argument stage (``FlowMol._request``)."""
+    path: str                       # 'ctmc' | 'endpoint' | 'mixed'
+    n_atoms: torch.Tensor           # (B,) int64 on the CPU
+    n_timesteps: object             # one count for the batch, as given or the model's default ('ctmc', 'endpoint')
+    counts: Optional[List[int]]     # one count per molecule ('mixed')
+    rng: str                        # 'torch' | 'philox'
+    dfm_type: str
+    seed: Optional[int]             # the caller's Philox seed; None: one draw from the CPU generator behind the bind
+    mol_ids: object                 # the caller's Philox stream ids; None: 0..B-1
+    kw: dict                        # the checked keyword arguments: schedules, tspan, _rows, _noise_for_step, _frames
+
+    @property
+    def n_points(self) -> int:
+        """Time points of the run = frames of a visualised one."""
+        ts = self.kw.get('tspan')
+        return int(self.n_timesteps) if ts is None else int(ts.shape[0])
+
 
 def _step_counts(n_timesteps):
     """A per-molecule sequence of step counts as a list of ints, or None for what sample() has always taken (None, an int, a 0-dim tensor)."""
@@ -651,6 +518,16 @@ def _step_counts(n_timesteps):
     return None
 
 
+def _tokens(state: Dict[str, torch.Tensor], copy: bool = False) -> Dict[str, torch.Tensor]:
+    """{'x', 'a', 'c', 'e'} of a state on its device: coordinates and int32 tokens -- a CTMC state's own tensors (clones with ``copy``), the argmax
+    of an endpoint model's continuous (rows, K) features."""
+    out = {}
+    for k in 'xace':
+        v = state[f'{k}_t']
+        out[k] = v.argmax(-1).int() if k != 'x' and v.dim() == 2 else (v.clone() if copy else v)
+    return out
+
+
 def _frames_of(init: Dict[str, torch.Tensor], traj: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """Compact frames of a visualised run on the device: 'x', 'a', 'c', 'e' = the prior + the state after every step (T frames), '*_1_pred' = every step's
     endpoint prediction (T - 1 frames) -- the frame set of the reference (ctmc_vector_field.py:188-202,235-283), tokens instead of one-hots."""
@@ -661,11 +538,10 @@ def _frames_of(init: Dict[str, torch.Tensor], traj: Dict[str, torch.Tensor]) -> 
 
 def _to_host(dev_out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """Final state of a batch, device -> host, as ONE packed copy (x fp32 | a, c, e as bytes: 14 B/atom + 1 B/pair)."""
-    from .shard import pack_results, unpack_results
     if dev_out['x'].device.type == 'cpu':
         return {k: v for k, v in dev_out.items()}
     N, U = int(dev_out['x'].shape[0]), int(dev_out['e'].shape[0])
-    return unpack_results(pack_results(dev_out['x'], dev_out['a'], dev_out['c'], dev_out['e']).cpu(), N, U)
+    return shard.unpack_results(shard.pack_results(dev_out['x'], dev_out['a'], dev_out['c'], dev_out['e']).cpu(), N, U)
 
 
 # names accepted by the reference's load_pretrained (flowmol/__init__.py:5-28)
@@ -698,3 +574,4 @@ def load_pretrained(model_name: str = 'flowmol3', precision: Optional[str] = Non
     if precision is not None:
         kw['precision'] = precision
     return FlowMol.load_from_checkpoint(ckpt, **kw)
+

@@ -31,7 +31,7 @@ class SamplingQueue:
         inv_temp_func of ``FlowMol.sample``."""
         model._check_mixed({'rng': 'philox', **kwargs})
         self.model, self.seed = model, int(seed)
-        self._plan_args, self._plan_kw = model._mixed_plan_args(stochasticity, high_confidence_threshold, kwargs)
+        self._plan_args, self._plan_kw = model._plan_args(stochasticity, high_confidence_threshold, kwargs)
         self._plans: Dict[int, object] = {}
         self._pending: List[_Request] = []
         self._running: List[_Request] = []

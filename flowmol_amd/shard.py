@@ -145,6 +145,12 @@ def gather_frames(local, n_atoms_all: torch.Tensor, parts: List[torch.Tensor], n
     return out
 
 
+def upper_half_rows(n_atoms: torch.Tensor) -> torch.Tensor:
+    """Rows of a directed-edge tensor (every molecule's n (n - 1) / 2 upper-block rows first, then its lower block) that hold the upper blocks."""
+    pairs = n_atoms * (n_atoms - 1) // 2
+    return _ranges(torch.cumsum(2 * pairs, 0) - 2 * pairs, pairs)
+
+
 def _ranges(starts: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
     """Concatenation of arange(starts[i], starts[i] + lens[i]) for all i."""
     total = int(lens.sum())

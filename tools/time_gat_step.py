@@ -28,7 +28,7 @@ if str(ROOT) not in sys.path:
 
 from flowmol_amd import build, presets, weights          # noqa: E402
 from flowmol_amd.engine import Engine, StepNoise, cat_temp_schedule, make_step_plan          # noqa: E402
-from flowmol_amd.model import FlowMol          # noqa: E402
+from flowmol_amd.priors import draw_categorical_priors          # noqa: E402
 
 
 def main(argv=None):
@@ -83,9 +83,7 @@ def main(argv=None):
 
             def host(types=types, kws=kws):
                 x0 = torch.randn(eeng.N, 3, device=dev)
-                a0 = FlowMol._categorical_prior(types['a'], eeng.N, ecfg.n_atom_types, kws.get('a', {}))
-                c0 = FlowMol._categorical_prior(types['c'], eeng.N, ecfg.n_charges, kws.get('c', {}), a_0=a0)
-                e0 = FlowMol._categorical_prior(types['e'], eeng.U, ecfg.n_bond_types, kws.get('e', {}))
+                a0, c0, e0 = draw_categorical_priors(ecfg, eeng.N, eeng.U, types, kws)
                 eeng.remove_com(x0)
                 return a0.to(dev), c0.to(dev), e0.to(dev)
             if 'p_host' in prior_variants:

@@ -28,7 +28,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 from flowmol_amd import build          # noqa: E402
-from flowmol_amd.engine import IntegrationRun          # noqa: E402
+from flowmol_amd.engine import IntegrationRun, make_step_plan          # noqa: E402
 from flowmol_amd.model import FlowMol          # noqa: E402
 
 SEED = 11
@@ -43,8 +43,7 @@ def step_mode(args, model):
     sizes = torch.full((args.n_mols,), args.n_atoms)
     eng.bind(sizes)
     T, lo = 250, 100
-    p_args, p_kw = model._mixed_plan_args(None, None, {})
-    from flowmol_amd.engine import make_step_plan
+    p_args, p_kw = model._plan_args(None, None, {})
     plan = make_step_plan(T, *p_args, philox_seed=SEED, **p_kw)
     state0 = eng.prior_state(eng.prior_philox(SEED))
     run = IntegrationRun(eng, state0, plan, None)
