@@ -212,6 +212,10 @@ const InstList<Mlp4PairFn> mlp4_pair_instances{"mode_a, mode_b", {mlp4_pair_inst
 const InstList<ProjFn> node_proj_instances{"V, tile_rows", {proj_inst<32>(), proj_inst<16>(), proj_inst<32, 16>(), proj_inst<16, 16>()}};
 const InstList<EdgeUpdFn> edge_update_instances{"tile_rows, narrow, head", {eupd_inst<32, false>(), eupd_inst<64, false>(), eupd_inst<32, true>(), eupd_inst<32, false, true>()}};
 const InstList<EdgeUpdSpFn> edge_update_sp_instances{"tile_rows, half_planes", {eupd_sp_inst<32, 0>(), eupd_sp_inst<32, 1>()}};
+// fused campbell step, keyed like its gat sibling (ctmc_gat_instances, fm_host.h); per-molecule time (`mixed`) is a kernel with an argument struct of its own,
+// hence a list of its own.  No dynamic LDS; the workgroup size is BatchPlan::ctmc_threads
+const InstList<decltype(&fm_k_ctmc_fused_mixed<256>)> ctmc_mixed_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused_mixed<1024>, 0}, {{256}, fm_k_ctmc_fused_mixed<256>, 0}}};
+const InstList<decltype(&fm_k_ctmc_fused<256>)> ctmc_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused<1024>, 0}, {{256}, fm_k_ctmc_fused<256>, 0}}};
 
 // fm_k_mlp2<mode, tm> over `rows` rows
 void launch_mlp(Launch& L, int mode, const char* name, FmMlpArgs a, const MlpW& w, int rows, int tm = FM_TM) {
@@ -252,189 +256,200 @@ void launch_node_proj(Launch& L, const char* name, int V, bool small, int N, con
     launch_inst(L, node_proj_instances, {V, tm}, name, dim3((N + tm - 1) / tm), dim3(FM_THREADS), lds_proj(V, tm), pa);
 }
 
-// One network evaluation of the bound batch.  The kernel instances are selected from the model (vector channels V, destination-feature vectors HX), the batch
-// plan (tile heights, fusions, MLP tiles: plan_batch) and this call (prev given, dense inputs, taps); the heavy families live in translation units of their own (fm_host.h).
+// One network evaluation of the bound batch is a short sequence of stages (evaluate, below); every stage takes the Launch, the context and what varies.  The
+// kernel instances are selected from the model (vector channels V, destination-feature vectors HX), the batch plan (tile heights, fusions, MLP tiles:
+// plan_batch) and the call (prev given, dense inputs, taps); the heavy families live in translation units of their own (fm_host.h).
+// the 4-row-tile arguments (fm_k_mlp4) of a stage's node side from its regular ones: same sources and destinations, the quad-row weight copies (the heads'
+// copy so also carries the rbf constants, which the parent left 0 there and NODE_HEAD never reads)
+FmMlp4Args mlp4_args(const FmMlpArgs& a, int N, const MlpW& w, const void* W1q, const void* W2q) {
+    FmMlp4Args q{};
+    q.N = N; q.W1q = W1q; q.b1 = w.b1; q.W2q = W2q; q.b2 = w.b2;
+    q.s_tab = a.s_tab; q.tok_a = a.tok_a; q.tok_c = a.tok_c; q.n_c1 = a.n_c1; q.tab_slot = a.tab_slot; q.node_mol = a.node_mol; q.slot_rows = a.slot_rows;
+    q.prev_a = a.prev_a; q.prev_c = a.prev_c; q.prev_x = a.prev_x; q.x_t = a.x_t;
+    q.na = a.na; q.nc = a.nc; q.rbf_mu_step = a.rbf_mu_step; q.rbf_inv_sigma = a.rbf_inv_sigma;
+    q.in = a.in; q.out = a.out; q.out2 = a.out2;
+    return q;
+}
+
+// Input stage: s and ef from dense inputs (endpoint-parameterised models), from the tokens and a previous endpoint prediction (the self-conditioning
+// layer; n_pq > 0: and the first convolutions' pair slab), or from the tokens alone (rows of the embedding tables)
+void input_stage(Launch& L, fm_ctx* c, const FmMlpArgs& base, const fm_state* state, const fm_dst* prev, const fm_dense_state* dense, const float* temb,
+                 bool mlp4, int n_pq) {
+    const Workspace& w = c->ws;
+    const FmBatch& b = w.b;
+    if (dense) {
+        // the categorical inputs are continuous vectors, so the embeddings are real MLPs over the N node rows [a_t | c_t | temb] and the U pair rows e_t
+        // (vector_field.py:226-261) -- the same two-layer kernel the token tables use, fed with dense rows; pair rows are written to both directed
+        // edges.  Ps is free scratch until the first node_proj.
+        const int kp = c->node_embed.K1p;
+        L("dense_in", fm_k_dense_node_in, dim3(std::min(2048, (int)(((size_t)b.N * kp + 255) / 256))), dim3(256), 0, w.Ps, kp, b.N,
+          (const float*)dense->a_t, c->na, (const float*)dense->c_t, c->nc, temb, c->cfg.time_embedding_dim);
+        FmMlpArgs a{};
+        a.in = w.Ps; a.in_ld = kp; a.out = w.s; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
+        launch_mlp(L, FM_MLP_TABLE, "embed_nodes", a, c->node_embed, b.N);
+        FmMlpArgs e{};
+        e.in = dense->e_t; e.in_ld = c->ne; e.in_w = c->ne; e.out = w.ef; e.out_ld = 128; e.ln_g = c->edge_ln_g; e.ln_b = c->edge_ln_b; e.ln_n = c->F;
+        e.p_e0 = b.p_e0; e.p_e1 = b.p_e1;
+        launch_mlp(L, FM_MLP_TABLE, "embed_pairs", e, c->edge_embed, b.U);
+    } else if (prev) {
+        FmMlpArgs a = base, e = base;
+        a.s_tab = c->s_tab; a.tok_a = state->a_t; a.tok_c = state->c_t; a.n_c1 = c->nc + 1;
+        a.tab_slot = c->tab_slot; a.node_mol = b.node_mol; a.slot_rows = (int)(c->tab_slot_floats / 256);
+        a.prev_a = prev->a; a.prev_c = prev->c; a.prev_x = prev->x; a.x_t = state->x_t;
+        a.out = w.s;
+        e.e_src = b.e_src; e.e_dst = b.e_dst; e.e_pair = b.e_pair; e.tok_e = state->e_t;
+        e.prev_e = prev->e; e.prev_x = prev->x; e.x_t = state->x_t; e.T1 = c->T1; e.ef_tab = c->ef_tab;
+        e.out = w.ef; e.p_e0 = b.p_e0; e.p_e1 = b.p_e1;
+        if (n_pq > 0) {      // the self-conditioning layer produces the edge features the first convolutions see: their pair slab in the same kernel
+            e.slabW0 = c->conv[0].Ws_slab; e.slabQ0 = w.Q[0];
+            if (n_pq > 1) { e.slabW1 = c->conv[1].Ws_slab; e.slabQ1 = w.Q[1]; }
+        }
+        // one row per unordered pair, written to both directed edges; with the pair slab the edge kernel is matrix-pipe work followed by 3 KB of row
+        // stores per pair: 32-row tiles (38 KB of LDS) put four independent workgroups on a CU instead of two, so that one's stores overlap the others' GEMMs
+        launch_mlp_stage(L, c->plan, mlp4, FM_MLP4_SC_NODE, FM_MLP_SC_NODE, FM_MLP_SC_EDGE, "sc", "sc_node", "sc_edge",
+                         mlp4_args(a, b.N, c->sc_node, c->sc_node_W1q, c->sc_node_W2q), a, c->sc_node, e, c->sc_edge, n_pq > 0);
+    } else {
+        L("gather_s", fm_k_gather_rows, dim3(std::min(2048, (b.N * 64 + 255) / 256)), dim3(256), 0, w.s, (const float*)c->s_tab, 256, b.N,
+          (const int*)state->a_t, (const int*)state->c_t, c->nc + 1, (const int*)nullptr, c->tab_slot, (const int*)b.node_mol, (int)(c->tab_slot_floats / 256));
+        L("gather_ef", fm_k_gather_rows, dim3(std::min(4096, (int)(((size_t)b.E * 32 + 255) / 256))), dim3(256), 0, w.ef, c->ef_tab, 128, b.E,
+          (const int*)state->e_t, (const int*)nullptr, 0, (const int*)b.e_pair, (const int*)nullptr, (const int*)nullptr, 0);
+    }
+}
+
+// Pass `it` of n_pass: node projections (pass 0, or every pass of the unfused sequence), edge messages, node update.  x_t: copied into the working
+// positions by pass 0; pq: a pair-slab convolution of this evaluation (FmMlpArgs::slabQ0)
+void conv_pass(Launch& L, fm_ctx* c, const Taps& tap, int it, int n_pass, const float* x_t, bool mlp4, bool pq) {
+    const BatchPlan& p = c->plan;
+    const Workspace& w = c->ws;
+    const fm_config& cf = c->cfg;
+    const int V = c->V, TN = p.tm_node, HX = c->HX, N = w.b.N;
+    const int i = it % cf.n_convs, u = cf.update_after[i];
+    const ConvW& cw = c->conv[i];
+    const ConvW* nx = it + 1 < n_pass ? &c->conv[(i + 1) % cf.n_convs] : nullptr;      // the next pass's convolution
+    const dim3 blk(FM_THREADS), gnt((N + TN - 1) / TN);
+    if (it == 0 || !p.fuse_node) {      // later convs: projected in the previous conv's node_update
+        if (it == 0 && mlp4) {
+            FmMlp4Args p4{};
+            p4.N = N; p4.in = w.s; p4.Wps4 = cw.Wps4; p4.Ps = w.Ps; p4.PV = w.PV; p4.pv_w = c->PVW; p4.v_init = w.v; p4.V = V; p4.x_src = x_t; p4.x_dst = w.xw;
+            launch_inst(L, mlp4_instances, {FM_MLP4_PROJ0}, "node_proj", dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, p4);
+        } else {
+            FmProjArgs pa{};
+            pa.N = N; pa.s = w.s; pa.v = w.v; pa.Wps = cw.Wps; pa.Ps = w.Ps; pa.Wpv = cw.Wpv; pa.PV = w.PV; pa.pv_w = c->PVW;
+            if (it == 0) { pa.v_init = w.v; pa.x_src = x_t; pa.x_dst = w.xw; }     // v = 0, working copy of x (no memset / memcpy nodes)
+            launch_node_proj(L, "node_proj", V, p.small_node, N, pa);
+        }
+    }
+    FmMsgArgs m{};
+    m.b = w.b; m.x = w.xw; m.ef = w.ef; m.Ps = w.Ps; m.PV = w.PV; m.w0 = cw.w0;
+    if (HX > 0) {       // use_dst_feats: projection GVP of the conv's input features + its per-node hoists
+        FmDstProjArgs dp{};
+        dp.N = N; dp.s = w.s; dp.v = w.v; dp.g = cw.dproj; dp.Wsd = cw.Wsd; dp.Psd = w.Psd; dp.Wpvd = cw.Wpvd; dp.PVd = w.PVd; dp.pv_w = c->PVW;
+        fm_launch_dst_proj(L, V, TN, HX, gnt, dp);
+        m.Psd = w.Psd; m.PVd = w.PVd;
+    }
+    m.g0 = cw.msg[0]; m.g1 = cw.msg[1]; m.g2 = cw.msg[2]; m.part_s = w.part_s; m.part_v = w.part_v;
+    m.rbf_mu_step = c->rbf_mu_step; m.rbf_inv_sigma = c->rbf_inv_sigma;
+    // per-edge message taps are written straight into the caller's buffers (both must be registered)
+    m.dbg_s = it == 0 && tap.find("conv0.msg.v") ? (float*)tap.find("conv0.msg.s") : nullptr;
+    m.dbg_v = m.dbg_s ? (float*)tap.find("conv0.msg.v") : nullptr;
+    dim3 gmsg(p.n_tiles_msg);      // edge tiles: molecule-aligned, FmBatch::tile_desc
+    if (p.xcd_swizzle) { m.xcd_chunk = (p.n_tiles_msg + 7) / 8; gmsg = dim3(8 * m.xcd_chunk); }
+    if (pq) { m.Q = w.Q[it]; m.g0.Ws = cw.Ws_sh; }          // GVP0's scalar GEMM: K = KU0 (hidden-vector norms); the rest arrives through Q
+    fm_launch_edge_message(L, V, p.tm_edge, HX, cf.precision, pq, gmsg, m);
+    FmNodeUpdArgs nu{};
+    nu.b = w.b; nu.s = w.s; nu.v = w.v; nu.part_s = w.part_s; nu.part_v = w.part_v; nu.inv_z = cf.msg_z < 0.f ? -1.0f : 1.0f / cf.msg_z;
+    nu.g0 = cw.upd[0]; nu.g1 = cw.upd[1]; nu.g2 = cw.upd[2];
+    nu.ln1_g = cw.ln1_g; nu.ln1_b = cw.ln1_b; nu.ln2_g = cw.ln2_g; nu.ln2_b = cw.ln2_b;
+    // aggregated-message taps go through scratch of their own (Ps / PV, which served in round 1, are outputs of the fused kernel)
+    const bool tagg = tap.find("conv", i, ".agg.s") || tap.find("conv", i, ".agg.v");
+    nu.agg_s = tagg ? w.tap_s : nullptr; nu.agg_v = tagg ? w.tap_v : nullptr;
+    if (p.fuse_node) {
+        if (nx) { nu.Wps = nx->Wps; nu.Wps4 = nx->Wps4; nu.Ps = w.Ps; nu.Wpv = nx->Wpv; nu.PV = w.PV; }
+        if (u >= 0) {
+            const UpdW& uw = c->upd[u];
+            nu.Wasd = uw.Wasd; nu.Wasd4 = uw.Wasd4; nu.Asd = w.Asd; nu.p0 = uw.pos[0]; nu.p1 = uw.pos[1]; nu.p2 = uw.pos[2]; nu.x = w.xw;
+        }
+    }
+    nu.s_real = c->S;
+    // instance of the node kernel: split precision, 4 rg nodes per workgroup (one tile per CU), narrow, or the regular one
+    if (p.node_sp) {
+        if (nx) nu.Wps_sp = nx->Wps_sp;
+        if (u >= 0) nu.Wasd_sp = c->upd[u].Wasd_sp;
+    }
+    const int rg = p.node_rg;
+    const size_t lds = p.node_sp ? lds_gvp_sp(V, TN) - (size_t)TN * 9 * 4 : lds_gvp(V, TN, false);
+    fm_launch_node_update(L, V, TN, p.node_sp || c->mp.narrow_s, p.node_sp, rg, rg ? dim3((N + 4 * rg - 1) / (4 * rg)) : gnt, lds, nu);
+    if (tagg) { tap(w.tap_s, (size_t)N * 256 * 4, "conv", i, ".agg.s"); tap(w.tap_v, (size_t)N * 3 * V * 4, "conv", i, ".agg.v"); }
+    tap(w.s, (size_t)N * 256 * 4, "conv", i, ".s"); tap(w.v, (size_t)N * 3 * V * 4, "conv", i, ".v");
+}
+
+// The molecule update after convolution i: positions and EdgeUpdate's node terms (kernels of their own in the unfused sequence, else done by node_update),
+// then EdgeUpdate.  last: the evaluation's last pass, whose EdgeUpdate may run the edge head as its epilogue -- returns whether it did
+bool mol_update(Launch& L, fm_ctx* c, const Taps& tap, int i, bool last, const fm_dst* out) {
+    const BatchPlan& p = c->plan;
+    const Workspace& w = c->ws;
+    const int V = c->V, TN = p.tm_node, N = w.b.N, E = w.b.E;
+    const UpdW& uw = c->upd[c->cfg.update_after[i]];
+    const dim3 blk(FM_THREADS);
+    const bool head_done = !c->mp.node_sp && last && p.fuse_head && !tap.find("upd", i, ".ef");      // a registered upd<i>.ef tap keeps the head unfused
+    if (!p.fuse_node) {
+        FmPosArgs pp{};
+        pp.N = N; pp.s = w.s; pp.v = w.v; pp.x = w.xw; pp.g0 = uw.pos[0]; pp.g1 = uw.pos[1]; pp.g2 = uw.pos[2];
+        fm_launch_pos_update(L, V, TN, dim3((N + TN - 1) / TN), pp);
+        FmProjArgs pa2{};
+        pa2.N = N; pa2.s = w.s; pa2.v = w.v; pa2.Wasd = uw.Wasd; pa2.Asd = w.Asd;
+        launch_node_proj(L, "node_proj_asd", V, p.small_node, N, pa2);
+    }
+    FmEdgeUpdArgs eu{};
+    eu.b = w.b; eu.x = w.xw; eu.Asd = w.Asd; eu.ef = w.ef; eu.W1 = uw.W1; eu.b1 = uw.b1; eu.W2 = uw.W2; eu.b2 = uw.b2;
+    eu.ln_g = uw.ln_g; eu.ln_b = uw.ln_b; eu.rbf_mu_step = c->rbf_mu_step; eu.rbf_inv_sigma = c->rbf_inv_sigma; eu.f_real = c->F;
+    if (c->mp.node_sp) {
+        const FmEdgeUpdSpW sw{uw.W1_sp, uw.W2_sp};
+        launch_inst(L, edge_update_sp_instances, {32, c->mp.half_planes}, "edge_update", dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
+    } else if (head_done) {
+        // the evaluation's last EdgeUpdate: its rows feed the edge head and nothing else -- tiles of 16 pairs, the head as the epilogue, no ef store
+        eu.hW1 = c->edge_head.W1; eu.hb1 = c->edge_head.b1; eu.hW2 = c->edge_head.W2; eu.hb2 = c->edge_head.b2; eu.out_e = out->e; eu.ne = c->ne;
+        launch_inst(L, edge_update_instances, {32, false, true}, "edge_update_head", dim3((w.b.U + 15) / 16), blk, lds_edge_upd(32), eu);
+    } else {
+        const int tm = p.tm_eupd;
+        launch_inst(L, edge_update_instances, {tm, c->mp.narrow_f, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
+    }
+    tap(w.xw, (size_t)N * 3 * 4, "upd", i, ".x");
+    if (!head_done) tap(w.ef, (size_t)E * 128 * 4, "upd", i, ".ef");
+    return head_done;
+}
+
+// The output heads.  head_done: the edge head ran as the epilogue of the last EdgeUpdate, only the node head is left
+void heads(Launch& L, fm_ctx* c, const FmMlpArgs& base, bool mlp4, bool head_done, const fm_dst* out) {
+    FmMlpArgs a = base, e = base;
+    a.in = c->ws.s; a.out = out->a; a.out2 = out->c;
+    e.ef = c->ws.ef; e.p_e0 = c->ws.b.p_e0; e.p_e1 = c->ws.b.p_e1; e.out = out->e;
+    launch_mlp_stage(L, c->plan, mlp4, FM_MLP4_NODE_HEAD, FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, "heads", "node_head", head_done ? nullptr : "edge_head",
+                     mlp4_args(a, c->ws.b.N, c->node_head, c->node_head_W1q, c->node_head_W2q), a, c->node_head, e, c->edge_head, c->plan.edge_head32);
+}
+
 int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* prev, int remove_com, const fm_dst* out,
              bool taps_on, const fm_dense_state* dense = nullptr, const float* temb = nullptr) {
     Launch L{c, st};
-    const BatchPlan& p = c->plan;
-    const int V = c->V, TE = p.tm_edge, TN = p.tm_node, HX = c->HX;
-    const FmBatch& b = c->b;
-    const int N = b.N, E = b.E, U = b.U;
+    const Taps tap{L, taps_on && !c->taps.empty()};
     const fm_config& cf = c->cfg;
-    const int nc1 = c->nc + 1;
-    auto tap = [&](const std::string& n, const void* src, size_t bytes) { if (taps_on) L.tap(n, src, bytes); };
-
-    const bool mlp4 = p.mlp4 && !dense;
-    const int n_pq = (prev && !dense) ? p.n_pq : 0;      // pair-slab convolutions of this evaluation (first pass only; FmMlpArgs::slabQ0)
-    FmMlpArgs ma{};
-    ma.na = c->na; ma.nc = c->nc; ma.ne = c->ne;
-    ma.rbf_mu_step = c->rbf_mu_step; ma.rbf_inv_sigma = c->rbf_inv_sigma;
-    const float* x_t = dense ? dense->x_t : state->x_t;
-    if (dense) {
-        // endpoint-parameterised model: the categorical inputs are continuous vectors, so the embeddings are real MLPs over the N
-        // node rows [a_t | c_t | temb] and the U pair rows e_t (vector_field.py:226-261) -- the same two-layer kernel the token
-        // tables use, fed with dense rows; pair rows are written to both directed edges.  Ps is free scratch until the first node_proj.
-        const int kp = c->node_embed.K1p;
-        L("dense_in", fm_k_dense_node_in, dim3(std::min(2048, (int)(((size_t)N * kp + 255) / 256))), dim3(256), 0, c->Ps, kp, N,
-          (const float*)dense->a_t, c->na, (const float*)dense->c_t, c->nc, temb, cf.time_embedding_dim);
-        FmMlpArgs a{};
-        a.in = c->Ps; a.in_ld = kp; a.out = c->s; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
-        launch_mlp(L, FM_MLP_TABLE, "embed_nodes", a, c->node_embed, N);
-        FmMlpArgs e{};
-        e.in = dense->e_t; e.in_ld = c->ne; e.in_w = c->ne; e.out = c->ef; e.out_ld = 128; e.ln_g = c->edge_ln_g; e.ln_b = c->edge_ln_b; e.ln_n = c->F;
-        e.p_e0 = b.p_e0; e.p_e1 = b.p_e1;
-        launch_mlp(L, FM_MLP_TABLE, "embed_pairs", e, c->edge_embed, U);
-        tap("embed.s", c->s, (size_t)N * 256 * 4);
-        tap("embed.ef", c->ef, (size_t)E * 128 * 4);
-    } else if (prev) {
-        FmMlpArgs a = ma;
-        a.s_tab = c->s_tab; a.tok_a = state->a_t; a.tok_c = state->c_t; a.n_c1 = nc1;
-        a.tab_slot = c->tab_slot; a.node_mol = b.node_mol; a.slot_rows = (int)(c->tab_slot_floats / 256);
-        a.prev_a = prev->a; a.prev_c = prev->c; a.prev_x = prev->x; a.x_t = state->x_t;
-        a.out = c->s;
-        FmMlpArgs e = ma;
-        e.e_src = b.e_src; e.e_dst = b.e_dst; e.e_pair = b.e_pair; e.tok_e = state->e_t;
-        e.prev_e = prev->e; e.prev_x = prev->x; e.x_t = state->x_t; e.T1 = c->T1; e.ef_tab = c->ef_tab;
-        e.out = c->ef;
-        e.p_e0 = b.p_e0; e.p_e1 = b.p_e1;
-        if (n_pq > 0) {      // the self-conditioning layer produces the edge features the first convolutions see: their pair slab in the same kernel
-            e.slabW0 = c->conv[0].Ws_slab; e.slabQ0 = c->Q[0];
-            if (n_pq > 1) { e.slabW1 = c->conv[1].Ws_slab; e.slabQ1 = c->Q[1]; }
-        }
-        FmMlp4Args a4{};
-        a4.N = N; a4.W1q = c->sc_node_W1q; a4.b1 = c->sc_node.b1; a4.W2q = c->sc_node_W2q; a4.b2 = c->sc_node.b2;
-        a4.s_tab = a.s_tab; a4.tok_a = a.tok_a; a4.tok_c = a.tok_c; a4.n_c1 = nc1; a4.tab_slot = a.tab_slot; a4.node_mol = a.node_mol; a4.slot_rows = a.slot_rows; a4.prev_a = a.prev_a; a4.prev_c = a.prev_c; a4.prev_x = a.prev_x; a4.x_t = a.x_t;
-        a4.na = c->na; a4.nc = c->nc; a4.rbf_mu_step = c->rbf_mu_step; a4.rbf_inv_sigma = c->rbf_inv_sigma; a4.out = c->s;
-        // one row per unordered pair, written to both directed edges; with the pair slab the edge kernel is matrix-pipe work followed by 3 KB of row
-        // stores per pair: 32-row tiles (38 KB of LDS) put four independent workgroups on a CU instead of two, so that one's stores overlap the others' GEMMs
-        launch_mlp_stage(L, p, mlp4, FM_MLP4_SC_NODE, FM_MLP_SC_NODE, FM_MLP_SC_EDGE, "sc", "sc_node", "sc_edge", a4, a, c->sc_node, e, c->sc_edge, n_pq > 0);
-        tap("sc.s", c->s, (size_t)N * 256 * 4);
-        tap("sc.ef", c->ef, (size_t)E * 128 * 4);
-    } else {
-        L("gather_s", fm_k_gather_rows, dim3(std::min(2048, (N * 64 + 255) / 256)), dim3(256), 0, c->s, (const float*)c->s_tab, 256, N,
-          (const int*)state->a_t, (const int*)state->c_t, nc1, (const int*)nullptr, c->tab_slot, (const int*)b.node_mol, (int)(c->tab_slot_floats / 256));
-        L("gather_ef", fm_k_gather_rows, dim3(std::min(4096, (int)(((size_t)E * 32 + 255) / 256))), dim3(256), 0, c->ef, c->ef_tab, 128, E,
-          (const int*)state->e_t, (const int*)nullptr, 0, (const int*)b.e_pair, (const int*)nullptr, (const int*)nullptr, 0);
-        tap("embed.s", c->s, (size_t)N * 256 * 4);
-        tap("embed.ef", c->ef, (size_t)E * 128 * 4);
-    }
-
-    const dim3 blk(FM_THREADS);
-    const dim3 gn((N + FM_TM - 1) / FM_TM), ge((E + FM_TM - 1) / FM_TM);     // 64-row kernels
-    const dim3 gnt((N + TN - 1) / TN), get(p.n_tiles_msg);                 // GVP kernels (edge tiles: molecule-aligned, FmBatch::tile_desc)
-    const bool fuse = p.fuse_node;
+    const bool mlp4 = c->plan.mlp4 && !dense, sc = prev && !dense;
+    const int n_pq = sc ? c->plan.n_pq : 0;      // pair-slab convolutions of this evaluation (first passes only)
+    FmMlpArgs base{};      // the fields every MLP stage shares
+    base.na = c->na; base.nc = c->nc; base.ne = c->ne; base.rbf_mu_step = c->rbf_mu_step; base.rbf_inv_sigma = c->rbf_inv_sigma;
+    input_stage(L, c, base, state, prev, dense, temb, mlp4, n_pq);
+    tap(c->ws.s, (size_t)c->ws.b.N * 256 * 4, sc ? "sc.s" : "embed.s");
+    tap(c->ws.ef, (size_t)c->ws.b.E * 128 * 4, sc ? "sc.ef" : "embed.ef");
     const int n_pass = cf.n_convs * (cf.n_recycles > 1 ? cf.n_recycles : 1);       // vector_field.py:307: the whole stack again, same weights
-    bool head_done = false;      // the edge head ran as the epilogue of the last EdgeUpdate
+    bool head_done = false;
     for (int it = 0; it < n_pass; ++it) {
-        const int i = it % cf.n_convs;
-        const ConvW& cw = c->conv[i];
-        if (it == 0 || !fuse) {      // later convs: projected in the previous conv's node_update
-            FmProjArgs pa{};
-            pa.N = N; pa.s = c->s; pa.v = c->v; pa.Wps = cw.Wps; pa.Ps = c->Ps; pa.Wpv = cw.Wpv; pa.PV = c->PV; pa.pv_w = c->PVW;
-            if (it == 0) { pa.v_init = c->v; pa.x_src = x_t; pa.x_dst = c->xw; }     // v = 0, working copy of x (no memset / memcpy nodes)
-            if (it == 0 && mlp4) {
-                FmMlp4Args p4{};
-                p4.N = N; p4.in = c->s; p4.Wps4 = cw.Wps4; p4.Ps = c->Ps; p4.PV = c->PV; p4.pv_w = c->PVW; p4.v_init = c->v; p4.V = V; p4.x_src = x_t; p4.x_dst = c->xw;
-                launch_inst(L, mlp4_instances, {FM_MLP4_PROJ0}, "node_proj", dim3((N + 3) / 4), blk, (size_t)FM_MLP4_LDS_BYTES, p4);
-            }
-            else launch_node_proj(L, "node_proj", V, p.small_node, N, pa);
-        }
-        FmMsgArgs m{};
-        m.b = b; m.x = c->xw; m.ef = c->ef; m.Ps = c->Ps; m.PV = c->PV; m.w0 = cw.w0;
-        if (HX > 0) {       // use_dst_feats: projection GVP of the conv's input features + its per-node hoists
-            FmDstProjArgs dp{};
-            dp.N = N; dp.s = c->s; dp.v = c->v; dp.g = cw.dproj; dp.Wsd = cw.Wsd; dp.Psd = c->Psd; dp.Wpvd = cw.Wpvd; dp.PVd = c->PVd; dp.pv_w = c->PVW;
-            fm_launch_dst_proj(L, V, TN, HX, gnt, dp);
-            m.Psd = c->Psd; m.PVd = c->PVd;
-        }
-        m.g0 = cw.msg[0]; m.g1 = cw.msg[1]; m.g2 = cw.msg[2];
-        m.part_s = c->part_s; m.part_v = c->part_v;
-        m.rbf_mu_step = c->rbf_mu_step; m.rbf_inv_sigma = c->rbf_inv_sigma;
-        // per-edge message taps are written straight into the caller's buffers (both must be registered)
-        const bool dbg = taps_on && it == 0 && c->taps.count("conv0.msg.s") && c->taps.count("conv0.msg.v");
-        m.dbg_s = dbg ? (float*)c->taps["conv0.msg.s"] : nullptr; m.dbg_v = dbg ? (float*)c->taps["conv0.msg.v"] : nullptr;
-        dim3 gmsg = get;
-        if (p.xcd_swizzle) { m.xcd_chunk = ((int)get.x + 7) / 8; gmsg = dim3(8 * m.xcd_chunk); }
-        const bool pq = it < n_pq;
-        if (pq) { m.Q = c->Q[it]; m.g0.Ws = cw.Ws_sh; }          // GVP0's scalar GEMM: K = KU0 (hidden-vector norms); the rest arrives through Q
-        fm_launch_edge_message(L, V, TE, HX, cf.precision, pq, gmsg, m);
-        const int u = cf.update_after[i];
-        FmNodeUpdArgs nu{};
-        nu.b = b; nu.s = c->s; nu.v = c->v; nu.part_s = c->part_s; nu.part_v = c->part_v; nu.inv_z = cf.msg_z < 0.f ? -1.0f : 1.0f / cf.msg_z;
-        nu.g0 = cw.upd[0]; nu.g1 = cw.upd[1]; nu.g2 = cw.upd[2];
-        nu.ln1_g = cw.ln1_g; nu.ln1_b = cw.ln1_b; nu.ln2_g = cw.ln2_g; nu.ln2_b = cw.ln2_b;
-        const std::string ci = "conv" + std::to_string(i);
-        const bool tagg = taps_on && (c->taps.count(ci + ".agg.s") || c->taps.count(ci + ".agg.v"));
-        // aggregated-message taps go through scratch of their own (Ps / PV, which served in round 1, are outputs of the fused kernel)
-        nu.agg_s = tagg ? c->tap_s : nullptr;
-        nu.agg_v = tagg ? c->tap_v : nullptr;
-        if (fuse) {
-            if (it + 1 < n_pass) { const ConvW& nx = c->conv[(i + 1) % cf.n_convs]; nu.Wps = nx.Wps; nu.Wps4 = nx.Wps4; nu.Ps = c->Ps; nu.Wpv = nx.Wpv; nu.PV = c->PV; }
-            if (u >= 0) {
-                const UpdW& uw = c->upd[u];
-                nu.Wasd = uw.Wasd; nu.Wasd4 = uw.Wasd4; nu.Asd = c->Asd; nu.p0 = uw.pos[0]; nu.p1 = uw.pos[1]; nu.p2 = uw.pos[2]; nu.x = c->xw;
-            }
-        }
-        nu.s_real = c->S;
-        {   // instance of the node kernel: split precision, 4 rg nodes per workgroup (one tile per CU), narrow, or the regular one
-            if (p.node_sp) {
-                if (it + 1 < n_pass) nu.Wps_sp = c->conv[(i + 1) % cf.n_convs].Wps_sp;
-                if (u >= 0) nu.Wasd_sp = c->upd[u].Wasd_sp;
-            }
-            const int rg = p.node_rg;
-            const size_t lds = p.node_sp ? lds_gvp_sp(V, TN) - (size_t)TN * 9 * 4 : lds_gvp(V, TN, false);
-            fm_launch_node_update(L, V, TN, p.node_sp || c->mp.narrow_s, p.node_sp, rg, rg ? dim3((N + 4 * rg - 1) / (4 * rg)) : gnt, lds, nu);
-        }
-        if (tagg) { tap(ci + ".agg.s", c->tap_s, (size_t)N * 256 * 4); tap(ci + ".agg.v", c->tap_v, (size_t)N * 3 * V * 4); }
-        tap(ci + ".s", c->s, (size_t)N * 256 * 4);
-        tap(ci + ".v", c->v, (size_t)N * 3 * V * 4);
-        if (u >= 0) {
-            const UpdW& uw = c->upd[u];
-            if (!fuse) {
-                FmPosArgs pp{};
-                pp.N = N; pp.s = c->s; pp.v = c->v; pp.x = c->xw; pp.g0 = uw.pos[0]; pp.g1 = uw.pos[1]; pp.g2 = uw.pos[2];
-                fm_launch_pos_update(L, V, TN, gnt, pp);
-                FmProjArgs pa2{};
-                pa2.N = N; pa2.s = c->s; pa2.v = c->v; pa2.Wasd = uw.Wasd; pa2.Asd = c->Asd;
-                launch_node_proj(L, "node_proj_asd", V, p.small_node, N, pa2);
-            }
-            FmEdgeUpdArgs eu{};
-            eu.b = b; eu.x = c->xw; eu.Asd = c->Asd; eu.ef = c->ef; eu.W1 = uw.W1; eu.b1 = uw.b1; eu.W2 = uw.W2; eu.b2 = uw.b2;
-            eu.ln_g = uw.ln_g; eu.ln_b = uw.ln_b; eu.rbf_mu_step = c->rbf_mu_step; eu.rbf_inv_sigma = c->rbf_inv_sigma;
-            eu.f_real = c->F;
-            if (c->mp.node_sp) {
-                const FmEdgeUpdSpW sw{uw.W1_sp, uw.W2_sp};
-                launch_inst(L, edge_update_sp_instances, {32, c->mp.half_planes}, "edge_update", dim3((E + 31) / 32), blk, lds_edge_upd_sp(32), eu, sw);
-            } else if (it == n_pass - 1 && p.fuse_head && !(taps_on && c->taps.count("upd" + std::to_string(i) + ".ef"))) {
-                // the evaluation's last EdgeUpdate: its rows feed the edge head and nothing else -- tiles of 16 pairs, the head as the epilogue, no ef store
-                eu.hW1 = c->edge_head.W1; eu.hb1 = c->edge_head.b1; eu.hW2 = c->edge_head.W2; eu.hb2 = c->edge_head.b2; eu.out_e = out->e; eu.ne = c->ne;
-                launch_inst(L, edge_update_instances, {32, false, true}, "edge_update_head", dim3((U + 15) / 16), blk, lds_edge_upd(32), eu);
-                head_done = true;
-            } else {
-                const int tm = p.tm_eupd;
-                launch_inst(L, edge_update_instances, {tm, c->mp.narrow_f, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
-            }
-            const std::string ui = "upd" + std::to_string(i);
-            tap(ui + ".x", c->xw, (size_t)N * 3 * 4);
-            if (!head_done) tap(ui + ".ef", c->ef, (size_t)E * 128 * 4);
-        }
+        conv_pass(L, c, tap, it, n_pass, dense ? dense->x_t : state->x_t, mlp4, it < n_pq);
+        if (cf.update_after[it % cf.n_convs] >= 0) head_done = mol_update(L, c, tap, it % cf.n_convs, it == n_pass - 1, out);
     }
-    {
-        FmMlpArgs a = ma;
-        a.in = c->s; a.out = out->a; a.out2 = out->c;
-        FmMlpArgs e = ma;
-        e.ef = c->ef; e.p_e0 = b.p_e0; e.p_e1 = b.p_e1; e.out = out->e;
-        FmMlp4Args a4{};
-        a4.N = N; a4.W1q = c->node_head_W1q; a4.b1 = c->node_head.b1; a4.W2q = c->node_head_W2q; a4.b2 = c->node_head.b2;
-        a4.na = c->na; a4.nc = c->nc; a4.in = c->s; a4.out = out->a; a4.out2 = out->c;
-        // head_done: only the node head is left
-        launch_mlp_stage(L, p, mlp4, FM_MLP4_NODE_HEAD, FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, "heads", "node_head", head_done ? nullptr : "edge_head", a4, a, c->node_head,
-                         e, c->edge_head, p.edge_head32);
-    }
-    if (remove_com != 2) {       // 2: the caller's fused CTMC kernel centres the raw positions (c->xw) and writes out->x itself
-        L.copy(out->x, c->xw, (size_t)N * 3 * 4);
-        if (remove_com) L("remove_com", fm_k_remove_com, dim3(b.B), dim3(64), 0, out->x, (const int*)b.mol_node_off);
+    heads(L, c, base, mlp4, head_done, out);
+    if (remove_com != 2) {       // 2: the caller's fused CTMC kernel centres the raw positions (ws.xw) and writes out->x itself
+        L.copy(out->x, c->ws.xw, (size_t)c->ws.b.N * 3 * 4);
+        if (remove_com) L("remove_com", fm_k_remove_com, dim3(c->ws.b.B), dim3(64), 0, out->x, (const int*)c->ws.b.mol_node_off);
     }
     return L.rc;
 }
@@ -449,29 +464,35 @@ int embed_table(fm_ctx* c, hipStream_t st, const float* temb, int n_tables = 1) 
     a.in = nullptr; a.n_c1 = c->nc + 1;          // rows = (a,c) token pairs; the input row is built in the kernel's prologue
     a.emb_a = c->emb_a; a.emb_c = c->emb_c; a.temb = temb;
     a.ta = cf.a_token_dim ? cf.a_token_dim : c->na + 1; a.tc = cf.c_token_dim ? cf.c_token_dim : c->nc + 1; a.tt = cf.time_embedding_dim;
-    a.out = c->s_tab_base; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
+    a.out = c->ws.s_tab_base; a.out_ld = 256; a.ln_g = c->node_ln_g; a.ln_b = c->node_ln_b; a.ln_n = c->S;
     fill_mlp(a, c->node_embed, c->tab_rows);
     a.tab_tiles = (c->tab_rows + FM_TM - 1) / FM_TM; a.tab_stride = a.tab_tiles * FM_TM * 256;
     launch_inst(L, mlp_instances, {FM_MLP_TABLE, FM_TM}, "embed_table", dim3(a.tab_tiles * n_tables), dim3(FM_THREADS), lds_mlp(a.ldx, a.ldh), a);
     return L.rc;
 }
 
-// tables_ready: the caller (fm_integrate) has already built this step's table into slot `table_slot`.  tab_slot (per-molecule time): device (n_mols) slot of
-// every molecule's table, counted from `table_slot`; the n_tables tables built here are temb's rows
+// table_slot >= 0: the caller (step_driver) has already built this step's table into that slot, and temb is not read (it may be null); else the n_tables
+// tables are built here from temb's rows.  tab_slot (per-molecule time): device (n_mols) slot of every molecule's table, counted from `table_slot`
 int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap,
                  int remove_com, const fm_dst* out, int table_slot = -1, const int* tab_slot = nullptr, int n_tables = 1) {
     int rc = 0;
     if (table_slot < 0) { table_slot = 0; rc = embed_table(c, st, temb, n_tables); }
     if (rc) return rc;
-    c->s_tab = c->s_tab_base + (size_t)table_slot * c->tab_slot_floats;
+    c->s_tab = c->ws.s_tab_base + (size_t)table_slot * c->tab_slot_floats;
     c->tab_slot = tab_slot;
     const bool sc = c->cfg.self_conditioning != 0;
     if (sc && !prev && bootstrap) {
-        rc = evaluate(c, st, state, nullptr, 0, &c->boot, false);
+        const fm_dst& boot = c->ws.boot;
+        rc = evaluate(c, st, state, nullptr, 0, &boot, false);
         if (rc) return rc;
-        if (c->taps.count("boot.x")) { Launch L{c, st}; L.tap("boot.x", c->boot.x, (size_t)c->b.N * 12); L.tap("boot.a", c->boot.a, (size_t)c->b.N * c->na * 4);
-            L.tap("boot.c", c->boot.c, (size_t)c->b.N * c->nc * 4); L.tap("boot.e", c->boot.e, (size_t)c->b.U * c->ne * 4); if (L.rc) return L.rc; }
-        prev = &c->boot;
+        if (!c->taps.empty() && c->taps.count("boot.x")) {      // the bootstrap prediction's taps: asked for by registering boot.x
+            Launch L{c, st};
+            const Taps tap{L, true};
+            const size_t N = c->ws.b.N, U = c->ws.b.U;
+            tap(boot.x, N * 12, "boot.x"); tap(boot.a, N * c->na * 4, "boot.a"); tap(boot.c, N * c->nc * 4, "boot.c"); tap(boot.e, U * c->ne * 4, "boot.e");
+            if (L.rc) return L.rc;
+        }
+        prev = &boot;
     }
     if (!sc) prev = nullptr;
     return evaluate(c, st, state, prev, remove_com, out, true);
@@ -483,7 +504,7 @@ __global__ void fm_k_noop() {}
 struct MixedStep { const fm_step_scalars* steps; const int* active; const int* mol_group; };
 
 // frame: this step's slice of the trajectory sink (x, a, c, e, x1 used; a1 / c1 / e1 travel in `smp`); campbell steps write it inside the fused kernel
-int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* dst, const fm_step_noise* nz,
+int ctmc_impl(fm_ctx* c, hipStream_t st, const Modality (&md)[3], const fm_state* state, const fm_dst* dst, const fm_step_noise* nz,
               const fm_step_scalars* sc, const fm_sampled* smp, const float* x_raw = nullptr, const fm_traj_sink* frame = nullptr,
               const MixedStep* mixed = nullptr) {
     Launch L{c, st};
@@ -491,41 +512,45 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
     // (event signalling + the dispatch that cannot overlap the previous kernel's tail); fm_profile_get("event_overhead") lets the caller
     // subtract it, which matters for the sub-millisecond kernels of small batches (HIP events vs rocprofv3: +12 % on a 350 us kernel).
     if (c->prof) L("event_overhead", fm_k_noop, dim3(1), dim3(64), 0);
-    const FmBatch& b = c->b;
-    struct Mod { int rows, K; const float* p; const int* mol; int* xt; int* x1; const float *q, *u1, *u2; };
+    const FmBatch& b = c->ws.b;
     static const fm_step_noise no_noise{};
-    if (!nz) {                    // Philox steps draw inside the kernel
-        if (sc->noise_mode != FM_NOISE_PHILOX) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
-        nz = &no_noise;
-    }
-    Mod mods[3] = {
-        {b.N, c->na, dst->a, b.node_mol, state->a_t, (smp && smp->a1) ? smp->a1 : c->sa1, nz->q_a, nz->u1_a, nz->u2_a},
-        {b.N, c->nc, dst->c, b.node_mol, state->c_t, (smp && smp->c1) ? smp->c1 : c->sc1, nz->q_c, nz->u1_c, nz->u2_c},
-        {b.U, c->ne, dst->e, b.pair_mol, state->e_t, (smp && smp->e1) ? smp->e1 : c->se1, nz->q_e, nz->u1_e, nz->u2_e},
+    const char* const missing = "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)";
+    const bool philox = sc->noise_mode == FM_NOISE_PHILOX;
+    if (!nz && !philox) return fail(c, FM_ERR_INVALID, "%s", missing);
+    if (!nz) nz = &no_noise;      // Philox steps draw inside the kernel
+    // what the per-modality structs of the three kernels share: K, p, xt, x1 (the caller's buffer or the workspace's), and for the fused ones off, sink_t
+    auto fill_mod = [&](auto& d, int m) {
+        int32_t* const x1 = smp ? pick3(m, smp->a1, smp->c1, smp->e1) : nullptr;
+        d.K = md[m].K; d.p = pick3(m, dst->a, dst->c, dst->e); d.xt = md[m].tok; d.x1 = x1 ? x1 : md[m].x1;
     };
-    if (sc->dfm_type == FM_DFM_GAT && sc->noise_mode == FM_NOISE_PHILOX) {      // in-kernel noise: the whole step in one launch (fm_k_ctmc_gat_fused)
-        FmGatFusedArgs f{};
-        const int* offs[3] = {b.mol_node_off, b.mol_node_off, b.mol_pair_off};
+    auto fill_fused = [&](auto& f) {      // + the position job and the Philox stream of a fused kernel (fm_ctmc_x_job)
         for (int m = 0; m < 3; ++m) {
-            FmGatMod& d = f.mod[m];
-            d.K = mods[m].K; d.p = mods[m].p; d.xt = mods[m].xt; d.x1 = mods[m].x1; d.off = offs[m]; d.cf = sc->gat_cf[m]; d.cb = sc->gat_cb[m];
-            d.sink_t = frame ? (m == 0 ? frame->a : m == 1 ? frame->c : frame->e) : nullptr;
+            fill_mod(f.mod[m], m);
+            f.mod[m].off = md[m].off; f.mod[m].sink_t = frame ? pick3(m, frame->a, frame->c, frame->e) : nullptr;
         }
-        f.temp = sc->cat_temperature; f.fw = sc->gat_fw; f.bw = sc->gat_bw; f.dt_cat = sc->dt;
         f.x_t = state->x_t; f.x1 = dst->x; f.node_off = b.mol_node_off; f.coef = sc->x_coef; f.dt = sc->dt; f.scale = sc->x_scale;
         f.x_raw = x_raw; f.x1_out = dst->x;
         if (frame) { f.sink_x = frame->x; f.sink_x1 = frame->x1; }
-        f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->mol_gid;
-        launch_inst(L, ctmc_gat_instances(), {c->plan.ctmc_threads}, "ctmc", dim3(b.B, 4), dim3(c->plan.ctmc_threads), 0, f);
+        if (philox) { f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->ws.mol_gid; }
+    };
+    const int nt = c->plan.ctmc_threads;
+    const dim3 grid(b.B, 4), blk(nt);
+    if (sc->dfm_type == FM_DFM_GAT && philox) {      // in-kernel noise: the whole step in one launch (fm_k_ctmc_gat_fused)
+        FmGatFusedArgs f{};
+        fill_fused(f);
+        for (int m = 0; m < 3; ++m) { f.mod[m].cf = sc->gat_cf[m]; f.mod[m].cb = sc->gat_cb[m]; }
+        f.temp = sc->cat_temperature; f.fw = sc->gat_fw; f.bw = sc->gat_bw; f.dt_cat = sc->dt;
+        launch_inst(L, ctmc_gat_instances(), {nt}, "ctmc", grid, blk, 0, f);
         return L.rc;
     }
-    if (sc->dfm_type == FM_DFM_GAT && !nz->q_a) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
-    if (sc->dfm_type == FM_DFM_GAT) {
+    if (sc->dfm_type == FM_DFM_GAT) {      // tensor noise: the Euler step and one flat kernel per modality
+        if (!nz->q_a) return fail(c, FM_ERR_INVALID, "%s", missing);
         L("x_step", fm_k_x_step, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3);
         for (int m = 0; m < 3; ++m) {
-            if (mods[m].rows == 0) continue;
+            if (md[m].rows == 0) continue;
             FmGatArgs a{};
-            a.rows = mods[m].rows; a.K = mods[m].K; a.p = mods[m].p; a.xt = mods[m].xt; a.x1 = mods[m].x1; a.q = mods[m].q;
+            fill_mod(a, m);
+            a.rows = md[m].rows; a.q = pick3(m, nz->q_a, nz->q_c, nz->q_e);
             a.temp = sc->cat_temperature; a.cf = sc->gat_cf[m]; a.cb = sc->gat_cb[m]; a.fw = sc->gat_fw; a.bw = sc->gat_bw; a.dt = sc->dt;
             L("ctmc_gat", fm_k_ctmc_gat, dim3((a.rows + 255) / 256), dim3(256), 0, a);
         }
@@ -533,28 +558,69 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* ds
     }
     if (sc->dfm_type != FM_DFM_CAMPBELL) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: unknown dfm_type %d", sc->dfm_type);
     FmCtmcFusedArgs f{};
-    const int* offs[3] = {b.mol_node_off, b.mol_node_off, b.mol_pair_off};
+    fill_fused(f);
     for (int m = 0; m < 3; ++m) {
         FmCtmcMod& d = f.mod[m];
-        d.K = mods[m].K; d.p = mods[m].p; d.xt = mods[m].xt; d.x1 = mods[m].x1; d.q = mods[m].q; d.u1 = mods[m].u1; d.u2 = mods[m].u2;
-        d.off = offs[m]; d.unmask_prob = sc->unmask_prob[m]; d.mask_prob = sc->mask_prob[m];
-        d.sink_t = frame ? (m == 0 ? frame->a : m == 1 ? frame->c : frame->e) : nullptr;
+        d.q = pick3(m, nz->q_a, nz->q_c, nz->q_e); d.u1 = pick3(m, nz->u1_a, nz->u1_c, nz->u1_e); d.u2 = pick3(m, nz->u2_a, nz->u2_c, nz->u2_e);
+        d.unmask_prob = sc->unmask_prob[m]; d.mask_prob = sc->mask_prob[m];
     }
-    f.temp = sc->cat_temperature; f.hc_thresh = sc->hc_thresh; f.last_step = sc->last_step;
-    f.x_t = state->x_t; f.x1 = dst->x; f.node_off = b.mol_node_off; f.coef = sc->x_coef; f.dt = sc->dt; f.scale = sc->x_scale;
-    f.x_raw = x_raw; f.x1_out = dst->x;
-    if (frame) { f.sink_x = frame->x; f.sink_x1 = frame->x1; }
-    if (sc->noise_mode == FM_NOISE_PHILOX) { f.philox = 1; f.seed_lo = sc->philox_seed_lo; f.seed_hi = sc->philox_seed_hi; f.step = sc->step_index; f.mol_gid = c->mol_gid; }
-    else if (!nz->q_a || !nz->u1_a || !nz->q_e) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: noise tensors missing (noise_mode FM_NOISE_TENSORS)");
-    if (mixed) {      // per-molecule time: the scalars of `f` are unused, every molecule reads its group's from the caller's device arrays
-        const FmCtmcMixedArgs mx{f, mixed->steps, mixed->active, mixed->mol_group};
-        if (c->plan.ctmc_threads == 1024) L("ctmc_mixed", fm_k_ctmc_fused_mixed<1024>, dim3(b.B, 4), dim3(1024), 0, mx);
-        else L("ctmc_mixed", fm_k_ctmc_fused_mixed<256>, dim3(b.B, 4), dim3(256), 0, mx);
-        return L.rc;
-    }
-    if (c->plan.ctmc_threads == 1024) L("ctmc", fm_k_ctmc_fused<1024>, dim3(b.B, 4), dim3(1024), 0, f);
-    else L("ctmc", fm_k_ctmc_fused<256>, dim3(b.B, 4), dim3(256), 0, f);
+    f.temp = sc->cat_temperature; f.hc_thresh = sc->hc_thresh; f.last_step = sc->last_step; f.philox = philox;
+    if (!philox && (!nz->q_a || !nz->u1_a || !nz->q_e)) return fail(c, FM_ERR_INVALID, "%s", missing);
+    // per-molecule time: the scalars of `f` are unused, every molecule reads its group's from the caller's device arrays
+    if (mixed) launch_inst(L, ctmc_mixed_instances, {nt}, "ctmc_mixed", grid, blk, 0, FmCtmcMixedArgs{f, mixed->steps, mixed->active, mixed->mol_group});
+    else launch_inst(L, ctmc_instances, {nt}, "ctmc", grid, blk, 0, f);
     return L.rc;
+}
+
+// The step loop of fm_integrate and fm_integrate_mixed: the endpoint predictions ping-pong between dst_a and dst_b from prev0 on, the embedding tables of a
+// chunk of steps are built in one launch (`tabs` tables per step, temb: n_steps x tabs rows; tab_slot: forward_impl), every step is one evaluation and one CTMC
+// step with its frame of the sink.  step(i, prev, sc, nz, mixed) sets what differs per step (mixed.mol_group stays null for a batch at one time) and returns
+// the bootstrap flag (no previous prediction and t = 0, vector_field.py:269-272); the entry points check their arguments first: a refused call enqueues nothing.
+template <class StepFn>
+int step_driver(fm_ctx* c, hipStream_t st, const fm_state* state, int n_steps, int tabs, const int* tab_slot, const float* temb, const fm_dst* prev0,
+                const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst, StepFn step) {
+    const int tt = c->cfg.time_embedding_dim, spc = FM_TAB_SLOTS / tabs;      // steps per table launch: every table of a chunk owns a slot
+    const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
+    const fm_dst* prev = prev0;
+    int cur = (prev0 && prev0->x == dst_a->x) ? 1 : 0;
+    for (int i = 0; i < n_steps; ++i) {
+        const fm_dst* out = cur == 0 ? dst_a : dst_b;
+        const fm_step_scalars* sc = nullptr;
+        const fm_step_noise* nz = nullptr;
+        MixedStep mixed{};
+        const int boot = step(i, prev, sc, nz, mixed);
+        // campbell steps: the COM removal of the endpoint positions runs inside the fused CTMC kernel (one launch and one copy less)
+        // (so do gat steps with in-kernel noise: fm_k_ctmc_gat_fused shares the campbell kernel's position job)
+        const bool defer_com = sc->dfm_type == FM_DFM_CAMPBELL || (sc->dfm_type == FM_DFM_GAT && sc->noise_mode == FM_NOISE_PHILOX);
+        if (i % spc == 0) {
+            const int rc0 = embed_table(c, st, temb + (size_t)i * tabs * tt, std::min(n_steps - i, spc) * tabs);
+            if (rc0) return rc0;
+        }
+        int rc = forward_impl(c, st, state, nullptr, prev, boot, defer_com ? 2 : 1, out, (i % spc) * tabs, tab_slot);
+        if (rc) return rc;
+        fm_sampled smp{};
+        fm_traj_sink frame{};      // step i's frames: the fused CTMC kernel writes them next to the state (no copy nodes per step)
+        if (sink) {
+            auto tok = [&](int32_t* p, int m) { return p ? p + (size_t)i * md[m].rows : nullptr; };
+            auto pos = [&](float* p) { return p ? p + (size_t)i * md[0].rows * 3 : nullptr; };
+            smp = {tok(sink->a1, 0), tok(sink->c1, 1), tok(sink->e1, 2)};
+            frame.x = pos(sink->x); frame.a = tok(sink->a, 0); frame.c = tok(sink->c, 1); frame.e = tok(sink->e, 2); frame.x1 = pos(sink->x1);
+        }
+        const bool in_kernel = sink && defer_com;      // the fused kernels write the frames too
+        rc = ctmc_impl(c, st, md, state, out, nz, sc, &smp, defer_com ? c->ws.xw : nullptr, in_kernel ? &frame : nullptr, mixed.mol_group ? &mixed : nullptr);
+        if (rc) return rc;
+        if (sink && !in_kernel) {      // tensor-noise 'gat' steps (three small kernels): frames by copy
+            Launch L{c, st};
+            L.copy(frame.x, state->x_t, frame.x ? (size_t)md[0].rows * 12 : 0);
+            for (int m = 0; m < 3; ++m) { int32_t* f = pick3(m, frame.a, frame.c, frame.e); L.copy(f, md[m].tok, f ? (size_t)md[m].rows * 4 : 0); }
+            L.copy(frame.x1, out->x, frame.x1 ? (size_t)md[0].rows * 12 : 0);
+            if (L.rc) return L.rc;
+        }
+        prev = out;
+        cur ^= 1;
+    }
+    if (final_dst) *final_dst = cur ^ 1;
+    return FM_OK;
 }
 
 // ---------------------------------------------------------------------------------------- fm_create: validate, plan, pack by module, upload
@@ -973,36 +1039,33 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
 }
 
 // ---------------------------------------------------------------------------------------- workspace
-struct WsLayout {
-    size_t off_mol_tile, off_tile_desc, off_mol_node, off_mol_edge, off_mol_pair, off_node_mol, off_first_edge, off_esrc, off_edst, off_epair, off_pe0, off_pe1,
-        off_pair_mol, off_s, off_v, off_xw, off_ef, off_Ps, off_Asd, off_PV, off_part_s, off_part_v, off_Psd, off_PVd, off_stab, off_bx, off_ba,
-        off_bc, off_be, off_tap_s, off_tap_v, off_gid, off_sa1, off_sc1, off_se1, off_Q0, off_Q1, total;
-};
-
-static WsLayout ws_layout(const fm_ctx* c, const BatchPlan& p) {
-    const size_t B = p.B, N = p.N, E = p.E, U = p.U, V = c->V;
-    WsLayout w;
+// The ONE list of the workspace's regions, in layout order, every region on a 256-byte boundary: "this pointer gets so many bytes".  Sets the pointers of `w`
+// from `base` (all null from a null base: fm_workspace_bytes) and returns the bytes the workspace needs; INTEGRATION.md ("Workspace size") states the sum.
+static size_t ws_carve(const fm_ctx* c, const BatchPlan& p, char* base, Workspace& w) {
+    const size_t B = p.B, N = p.N, E = p.E, U = p.U, V = c->V, PVW = c->PVW;
     size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    w.off_mol_tile = take((B + 1) * 4); w.off_tile_desc = take((size_t)p.n_tiles_msg * 16);
-    w.off_mol_node = take((B + 1) * 4); w.off_mol_edge = take((B + 1) * 4); w.off_mol_pair = take((B + 1) * 4);
-    w.off_node_mol = take(N * 4); w.off_first_edge = take(N * 4);
-    w.off_esrc = take(E * 4); w.off_edst = take(E * 4); w.off_epair = take(E * 4);
-    w.off_pe0 = take(U * 4); w.off_pe1 = take(U * 4); w.off_pair_mol = take(U * 4);
-    w.off_s = take(N * 256 * 4); w.off_v = take(N * 3 * V * 4); w.off_xw = take(N * 3 * 4);
-    w.off_ef = take(E * 128 * 4);
-    w.off_Ps = take(N * 256 * 4); w.off_Asd = take(N * 256 * 4); w.off_PV = take(N * 3 * c->PVW * 4);
-    w.off_Psd = take(c->HX ? N * 256 * 4 : 0); w.off_PVd = take(c->HX ? N * 3 * c->PVW * 4 : 0);
-    w.off_part_s = take(N * p.P * 256 * 4); w.off_part_v = take(N * p.P * 3 * V * 4);
-    w.off_stab = take(align_up(c->tab_rows, FM_TM) * 256 * 4 * FM_TAB_SLOTS);
-    w.off_bx = take(N * 3 * 4); w.off_ba = take(N * c->na * 4); w.off_bc = take(N * c->nc * 4); w.off_be = take(U * c->ne * 4);
-    w.off_tap_s = take(N * 256 * 4); w.off_tap_v = take(N * 3 * V * 4);
-    w.off_gid = take(B * 4);
-    w.off_sa1 = take(N * 4); w.off_sc1 = take(N * 4); w.off_se1 = take(U * 4);
+    auto take = [&](auto*& ptr, size_t bytes) {
+        ptr = base ? reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + o) : nullptr;
+        o = align_up(o + bytes, 256);
+    };
+    take(w.b.mol_tile_off, (B + 1) * 4); take(w.b.tile_desc, (size_t)p.n_tiles_msg * 16);
+    take(w.b.mol_node_off, (B + 1) * 4); take(w.b.mol_edge_off, (B + 1) * 4); take(w.b.mol_pair_off, (B + 1) * 4);
+    take(w.b.node_mol, N * 4); take(w.b.node_first_edge, N * 4);
+    take(w.b.e_src, E * 4); take(w.b.e_dst, E * 4); take(w.b.e_pair, E * 4);
+    take(w.b.p_e0, U * 4); take(w.b.p_e1, U * 4); take(w.b.pair_mol, U * 4);
+    take(w.s, N * 256 * 4); take(w.v, N * 3 * V * 4); take(w.xw, N * 3 * 4);
+    take(w.ef, E * 128 * 4);
+    take(w.Ps, N * 256 * 4); take(w.Asd, N * 256 * 4); take(w.PV, N * 3 * PVW * 4);
+    take(w.Psd, c->HX ? N * 256 * 4 : 0); take(w.PVd, c->HX ? N * 3 * PVW * 4 : 0);
+    take(w.part_s, N * p.P * 256 * 4); take(w.part_v, N * p.P * 3 * V * 4);
+    take(w.s_tab_base, align_up(c->tab_rows, FM_TM) * 256 * 4 * FM_TAB_SLOTS);
+    take(w.boot.x, N * 3 * 4); take(w.boot.a, N * c->na * 4); take(w.boot.c, N * c->nc * 4); take(w.boot.e, U * c->ne * 4);
+    take(w.tap_s, N * 256 * 4); take(w.tap_v, N * 3 * V * 4);
+    take(w.mol_gid, B * 4);
+    take(w.x1[0], N * 4); take(w.x1[1], N * 4); take(w.x1[2], U * 4);
     // the pair-slab tables are as large as `ef` each: only batches that use them pay for them (8192 x 47 atoms: 13.3 GB without, 31.5 GB with)
-    w.off_Q0 = take(p.n_pq > 0 ? U * 256 * 4 : 0); w.off_Q1 = take(p.n_pq > 1 ? U * 256 * 4 : 0);
-    w.total = o;
-    return w;
+    take(w.Q[0], p.n_pq > 0 ? U * 256 * 4 : 0); take(w.Q[1], p.n_pq > 1 ? U * 256 * 4 : 0);
+    return o;
 }
 
 int fm_workspace_bytes(fm_ctx* c, const int32_t* n_atoms, int B, size_t* bytes) {
@@ -1010,7 +1073,8 @@ int fm_workspace_bytes(fm_ctx* c, const int32_t* n_atoms, int B, size_t* bytes) 
     BatchPlan p;
     const int rc = plan_batch(c, n_atoms, B, p);
     if (rc) return rc;
-    *bytes = ws_layout(c, p).total;
+    Workspace scratch;
+    *bytes = ws_carve(c, p, nullptr, scratch);
     return FM_OK;
 }
 
@@ -1044,14 +1108,18 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
     BatchPlan p;
     int rc = plan_batch(c, n_atoms, B, p);
     if (rc) return rc;
-    const WsLayout w = ws_layout(c, p);
-    if (bytes < w.total) return fail(c, FM_ERR_INVALID, "fm_batch_bind: workspace of %zu bytes < required %zu", bytes, w.total);
+    Workspace w;
+    const size_t need = ws_carve(c, p, (char*)workspace, w);
+    if (bytes < need) return fail(c, FM_ERR_INVALID, "fm_batch_bind: workspace of %zu bytes < required %zu", bytes, need);
     if ((uintptr_t)workspace % 256) return fail(c, FM_ERR_INVALID, "fm_batch_bind: workspace must be 256-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)workspace;
-    rc = stage_acquire(c, st, 4 * (size_t)(B + 1) + (size_t)B);
+    FmBatch& b = w.b;
+    b.B = B; b.N = p.N; b.E = p.E; b.U = p.U; b.P = p.P;
+    b.n_tiles = p.n_tiles_msg; b.tile_rows = p.tm_edge;
+    const size_t B1 = (size_t)B + 1;
+    rc = stage_acquire(c, st, 4 * B1 + (size_t)B);
     if (rc) return rc;
-    int32_t* no = c->stage; int32_t* eo = no + (B + 1); int32_t* po = eo + (B + 1); int32_t* to = po + (B + 1); int32_t* ids = to + (B + 1);
+    int32_t* no = c->stage; int32_t* eo = no + B1; int32_t* po = eo + B1; int32_t* to = po + B1; int32_t* ids = to + B1;
     no[0] = eo[0] = po[0] = to[0] = 0;
     for (int i = 0; i < B; ++i) {
         const int n = n_atoms[i];
@@ -1059,34 +1127,17 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
         to[i + 1] = to[i] + (n * (n - 1) + p.tm_edge - 1) / p.tm_edge;
     }
     {   // a copy that fails after earlier ones were enqueued must not leave the staging buffer unguarded: the event is recorded either way
-        hipError_t e_ = hipMemcpyAsync(base + w.off_mol_node, no, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(base + w.off_mol_edge, eo, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(base + w.off_mol_pair, po, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(base + w.off_mol_tile, to, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st);
-        if (e_ == hipSuccess) e_ = hipMemcpyAsync(base + w.off_gid, ids, (size_t)B * 4, hipMemcpyHostToDevice, st);
+        const struct { const int* dst; const int32_t* src; size_t n; } copies[] = {
+            {b.mol_node_off, no, B1}, {b.mol_edge_off, eo, B1}, {b.mol_pair_off, po, B1}, {b.mol_tile_off, to, B1}, {w.mol_gid, ids, (size_t)B}};
+        hipError_t e_ = hipSuccess;
+        for (const auto& k : copies) if (e_ == hipSuccess) e_ = hipMemcpyAsync(const_cast<int*>(k.dst), k.src, k.n * 4, hipMemcpyHostToDevice, st);
         rc = stage_release(c, st);
         if (e_ != hipSuccess) return fail(c, FM_ERR_HIP, "fm_batch_bind: descriptor copy failed: %s", hipGetErrorString(e_));
         if (rc) return rc;
     }
-    FmBatch& b = c->b;
-    b.B = B; b.N = p.N; b.E = p.E; b.U = p.U; b.P = p.P;
-    b.n_tiles = p.n_tiles_msg; b.tile_rows = p.tm_edge;
-    b.mol_tile_off = (const int*)(base + w.off_mol_tile); b.tile_desc = (int4*)(base + w.off_tile_desc);
-    b.mol_node_off = (const int*)(base + w.off_mol_node); b.mol_edge_off = (const int*)(base + w.off_mol_edge); b.mol_pair_off = (const int*)(base + w.off_mol_pair);
-    b.node_mol = (int*)(base + w.off_node_mol); b.node_first_edge = (int*)(base + w.off_first_edge);
-    b.e_src = (int*)(base + w.off_esrc); b.e_dst = (int*)(base + w.off_edst); b.e_pair = (int*)(base + w.off_epair);
-    b.p_e0 = (int*)(base + w.off_pe0); b.p_e1 = (int*)(base + w.off_pe1); b.pair_mol = (int*)(base + w.off_pair_mol);
-    c->s = (float*)(base + w.off_s); c->v = (float*)(base + w.off_v); c->xw = (float*)(base + w.off_xw); c->ef = (float*)(base + w.off_ef);
-    c->Ps = (float*)(base + w.off_Ps); c->Asd = (float*)(base + w.off_Asd); c->PV = (float*)(base + w.off_PV);
-    c->part_s = (float*)(base + w.off_part_s); c->part_v = (float*)(base + w.off_part_v);
-    c->Psd = (float*)(base + w.off_Psd); c->PVd = (float*)(base + w.off_PVd);
-    c->s_tab = c->s_tab_base = (float*)(base + w.off_stab);
+    c->ws = w;
+    c->s_tab = w.s_tab_base;
     c->tab_slot_floats = (size_t)align_up(c->tab_rows, FM_TM) * 256;
-    c->boot.x = (float*)(base + w.off_bx); c->boot.a = (float*)(base + w.off_ba); c->boot.c = (float*)(base + w.off_bc); c->boot.e = (float*)(base + w.off_be);
-    c->tap_s = (float*)(base + w.off_tap_s); c->tap_v = (float*)(base + w.off_tap_v);
-    c->mol_gid = (int*)(base + w.off_gid);
-    c->sa1 = (int32_t*)(base + w.off_sa1); c->sc1 = (int32_t*)(base + w.off_sc1); c->se1 = (int32_t*)(base + w.off_se1);
-    c->Q[0] = (float*)(base + w.off_Q0); c->Q[1] = (float*)(base + w.off_Q1);
     Launch L{c, st};
     const int work = p.E > p.N ? p.E : p.N;
     L("batch_setup", fm_k_batch_setup, dim3((work + 255) / 256), dim3(256), 0, b);
@@ -1096,55 +1147,50 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
 }
 
 int fm_remove_com(fm_ctx* c, void* stream, float* x) {
-    if (!c || !x) return fail(c, FM_ERR_INVALID, "fm_remove_com: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_remove_com: no batch bound");
+    if (const int rc = bound_check(c, "fm_remove_com", x)) return rc;
     Launch L{c, (hipStream_t)stream};
-    L("remove_com", fm_k_remove_com, dim3(c->b.B), dim3(64), 0, x, (const int*)c->b.mol_node_off);
+    L("remove_com", fm_k_remove_com, dim3(c->ws.b.B), dim3(64), 0, x, (const int*)c->ws.b.mol_node_off);
     return L.rc;
 }
 
 int fm_set_molecule_ids(fm_ctx* c, void* stream, const int32_t* ids_host) {
     if (!c) return fail(c, FM_ERR_INVALID, "fm_set_molecule_ids: null context");
     if (!c->bound) return fail(c, FM_ERR_STATE, "fm_set_molecule_ids: no batch bound");
-    int rc = stage_acquire(c, (hipStream_t)stream, (size_t)c->b.B);
+    int rc = stage_acquire(c, (hipStream_t)stream, (size_t)c->ws.b.B);
     if (rc) return rc;
-    for (int i = 0; i < c->b.B; ++i) c->stage[i] = ids_host ? ids_host[i] : i;
-    const hipError_t e_ = hipMemcpyAsync(c->mol_gid, c->stage, (size_t)c->b.B * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
+    for (int i = 0; i < c->ws.b.B; ++i) c->stage[i] = ids_host ? ids_host[i] : i;
+    const hipError_t e_ = hipMemcpyAsync(c->ws.mol_gid, c->stage, (size_t)c->ws.b.B * 4, hipMemcpyHostToDevice, (hipStream_t)stream);
     rc = stage_release(c, (hipStream_t)stream);
     if (e_ != hipSuccess) return fail(c, FM_ERR_HIP, "fm_set_molecule_ids: copy failed: %s", hipGetErrorString(e_));
     return rc;
 }
 
 int fm_prior_philox(fm_ctx* c, void* stream, uint64_t seed, float* x0) {
-    if (!c || !x0) return fail(c, FM_ERR_INVALID, "fm_prior_philox: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_prior_philox: no batch bound");
+    if (const int rc = bound_check(c, "fm_prior_philox", x0)) return rc;
     Launch L{c, (hipStream_t)stream};
-    L("prior_philox", fm_k_prior_philox, dim3(c->b.B), dim3(64), 0, x0, (const int*)c->b.mol_node_off, (const int*)c->mol_gid,
+    L("prior_philox", fm_k_prior_philox, dim3(c->ws.b.B), dim3(64), 0, x0, (const int*)c->ws.b.mol_node_off, (const int*)c->ws.mol_gid,
       (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32));
     return L.rc;
 }
 
 int fm_prior_philox_dense(fm_ctx* c, void* stream, uint64_t seed, const fm_prior_spec* spec, const fm_dense_state* out) {
-    if (!c || !spec || !out || !out->x_t || !out->a_t || !out->c_t || !out->e_t) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_prior_philox_dense: no batch bound");
+    if (const int rc = bound_check(c, "fm_prior_philox_dense", spec && out && out->x_t && out->a_t && out->c_t && out->e_t)) return rc;
     if (c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: this is a CTMC model (masked prior): use fm_prior_philox");
-    const FmBatch& b = c->b;
+    const FmBatch& b = c->ws.b;
     FmPriorDenseArgs a{};
-    const int d[3] = {c->na, c->nc, c->ne};
-    float* outs[3] = {out->a_t, out->c_t, out->e_t};
-    const int* offs[3] = {b.mol_node_off, b.mol_node_off, b.mol_pair_off};
     static const char* const tag[3] = {"a", "c", "e"};
     for (int m = 0; m < 3; ++m) {
         const fm_prior_mod& s = spec->mod[m];
+        const int d = modality(c, m).K;
         if (s.kind < FM_PRIOR_GAUSSIAN || s.kind > FM_PRIOR_C_GIVEN_A) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: unknown prior kind %d for modality %s", s.kind, tag[m]);
         if (s.kind == FM_PRIOR_C_GIVEN_A && m != 1) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: the c-given-a prior is for modality c, not %s", tag[m]);
         if ((s.kind == FM_PRIOR_MARGINAL || s.kind == FM_PRIOR_C_GIVEN_A) && !s.p) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: modality %s needs its distribution p", tag[m]);
-        if (s.kind == FM_PRIOR_BIASED_SIMPLEX && (d[m] < 2 || s.vertex_idx < 0 || s.vertex_idx >= d[m])) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: biased-simplex vertex_idx %d outside the %d categories of %s", s.vertex_idx, d[m], tag[m]);
+        if (s.kind == FM_PRIOR_BIASED_SIMPLEX && (d < 2 || s.vertex_idx < 0 || s.vertex_idx >= d)) return fail(c, FM_ERR_INVALID, "fm_prior_philox_dense: biased-simplex vertex_idx %d outside the %d categories of %s", s.vertex_idx, d, tag[m]);
         FmPriorMod& k = a.mod[m];
-        k.kind = s.kind; k.d = d[m]; k.std = s.std; k.simplex_center = s.simplex_center; k.blur = s.blur; k.has_blur = s.has_blur;
-        k.vertex_prob = s.vertex_prob; k.vertex_idx = s.vertex_idx; k.p = s.p; k.out = outs[m]; k.off = offs[m];
+        k.kind = s.kind; k.d = d; k.std = s.std; k.simplex_center = s.simplex_center; k.blur = s.blur; k.has_blur = s.has_blur;
+        k.vertex_prob = s.vertex_prob; k.vertex_idx = s.vertex_idx; k.p = s.p; k.out = pick3(m, out->a_t, out->c_t, out->e_t); k.off = modality(c, m).off;
     }
-    a.x = out->x_t; a.node_off = b.mol_node_off; a.mol_gid = c->mol_gid;
+    a.x = out->x_t; a.node_off = b.mol_node_off; a.mol_gid = c->ws.mol_gid;
     a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
     Launch L{c, (hipStream_t)stream};
     L("prior_philox_dense", fm_k_prior_philox_dense, dim3(b.B, 4), dim3(256), 0, a);
@@ -1152,41 +1198,35 @@ int fm_prior_philox_dense(fm_ctx* c, void* stream, uint64_t seed, const fm_prior
 }
 
 int fm_philox_tape(fm_ctx* c, void* stream, const fm_step_scalars* sc, const fm_step_noise* out) {
-    if (!c || !sc || !out || !out->q_a || !out->q_c || !out->q_e) return fail(c, FM_ERR_INVALID, "fm_philox_tape: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_philox_tape: no batch bound");
+    if (const int rc = bound_check(c, "fm_philox_tape", sc && out && out->q_a && out->q_c && out->q_e)) return rc;
     if (sc->noise_mode != FM_NOISE_PHILOX) return fail(c, FM_ERR_INVALID, "fm_philox_tape: the step's noise_mode is not FM_NOISE_PHILOX");
     if (sc->dfm_type != FM_DFM_CAMPBELL && sc->dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "fm_philox_tape: unknown dfm_type %d", sc->dfm_type);
-    const FmBatch& b = c->b;
     FmTapeArgs a{};
     auto w = [](const float* p) { return const_cast<float*>(p); };      // caller-owned output tensors travelling in the (read-only) noise struct
-    a.mod[0] = {c->na, b.mol_node_off, w(out->q_a), w(out->u1_a), w(out->u2_a)};
-    a.mod[1] = {c->nc, b.mol_node_off, w(out->q_c), w(out->u1_c), w(out->u2_c)};
-    a.mod[2] = {c->ne, b.mol_pair_off, w(out->q_e), w(out->u1_e), w(out->u2_e)};
-    a.gat = sc->dfm_type == FM_DFM_GAT; a.seed_lo = sc->philox_seed_lo; a.seed_hi = sc->philox_seed_hi; a.step = sc->step_index; a.mol_gid = c->mol_gid;
+    for (int m = 0; m < 3; ++m)
+        a.mod[m] = {modality(c, m).K, modality(c, m).off, w(pick3(m, out->q_a, out->q_c, out->q_e)), w(pick3(m, out->u1_a, out->u1_c, out->u1_e)), w(pick3(m, out->u2_a, out->u2_c, out->u2_e))};
+    a.gat = sc->dfm_type == FM_DFM_GAT; a.seed_lo = sc->philox_seed_lo; a.seed_hi = sc->philox_seed_hi; a.step = sc->step_index; a.mol_gid = c->ws.mol_gid;
     Launch L{c, (hipStream_t)stream};
-    L("philox_tape", fm_k_philox_tape, dim3(b.B, 3), dim3(256), 0, a);
+    L("philox_tape", fm_k_philox_tape, dim3(c->ws.b.B, 3), dim3(256), 0, a);
     return L.rc;
 }
 
 int fm_forward(fm_ctx* c, void* stream, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap, int remove_com,
                const fm_dst* out) {
-    if (!c || !state || !temb || !out) return fail(c, FM_ERR_INVALID, "fm_forward: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_forward: no batch bound");
+    if (const int rc = bound_check(c, "fm_forward", state && temb && out)) return rc;
     if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_forward: endpoint-parameterised model (continuous inputs): use fm_forward_dense");
     return forward_impl(c, (hipStream_t)stream, state, temb, prev, bootstrap, remove_com ? 1 : 0, out);
 }
 
 int fm_forward_dense(fm_ctx* c, void* stream, const fm_dense_state* state, const float* temb, int remove_com, const fm_dst* out) {
-    if (!c || !state || !temb || !out) return fail(c, FM_ERR_INVALID, "fm_forward_dense: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_forward_dense: no batch bound");
+    if (const int rc = bound_check(c, "fm_forward_dense", state && temb && out)) return rc;
     if (c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_forward_dense: this is a CTMC model (token inputs): use fm_forward");
     return evaluate(c, (hipStream_t)stream, nullptr, nullptr, remove_com ? 1 : 0, out, true, state, temb);
 }
 
 int fm_endpoint_step(fm_ctx* c, void* stream, const fm_dense_state* state, const fm_dst* dst, const fm_endpoint_scalars* sc) {
-    if (!c || !state || !dst || !sc) return fail(c, FM_ERR_INVALID, "fm_endpoint_step: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_endpoint_step: no batch bound");
-    const FmBatch& b = c->b;
+    if (const int rc = bound_check(c, "fm_endpoint_step", state && dst && sc)) return rc;
+    const FmBatch& b = c->ws.b;
     FmEndpointStepArgs a{};
     float* xt[4] = {state->x_t, state->a_t, state->c_t, state->e_t};
     const float* x1[4] = {dst->x, dst->a, dst->c, dst->e};
@@ -1201,69 +1241,24 @@ int fm_endpoint_step(fm_ctx* c, void* stream, const fm_dense_state* state, const
 
 int fm_ctmc_step(fm_ctx* c, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
                  const fm_sampled* sampled) {
-    if (!c || !state || !dst || !sc) return fail(c, FM_ERR_INVALID, "fm_ctmc_step: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_ctmc_step: no batch bound");
-    return ctmc_impl(c, (hipStream_t)stream, state, dst, noise, sc, sampled);
+    if (const int rc = bound_check(c, "fm_ctmc_step", state && dst && sc)) return rc;
+    const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
+    return ctmc_impl(c, (hipStream_t)stream, md, state, dst, noise, sc, sampled);
 }
 
 int fm_integrate(fm_ctx* c, void* stream, const fm_state* state, int n_steps, const fm_step_scalars* steps, const float* temb,
                  const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink,
                  int* final_dst) {
-    if (!c || !state || !steps || !temb || !dst_a || !dst_b) return fail(c, FM_ERR_INVALID, "fm_integrate: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_integrate: no batch bound");
-    hipStream_t st = (hipStream_t)stream;
-    const int tt = c->cfg.time_embedding_dim;
-    const FmBatch& b = c->b;
-    const fm_dst* prev = prev0;
-    int cur = (prev0 && prev0->x == dst_a->x) ? 1 : 0;
-    for (int i = 0; i < n_steps; ++i) {
-        const fm_dst* out = cur == 0 ? dst_a : dst_b;
-        const int boot = (!prev && steps[i].t == 0.0f) ? 1 : 0;      // prev is None and (t == 0).all(), vector_field.py:269-272
-        // campbell steps: the COM removal of the endpoint positions runs inside the fused CTMC kernel (one launch and one copy less)
-        // (so do gat steps with in-kernel noise: fm_k_ctmc_gat_fused shares the campbell kernel's position job)
-        const bool defer_com = steps[i].dfm_type == FM_DFM_CAMPBELL || (steps[i].dfm_type == FM_DFM_GAT && steps[i].noise_mode == FM_NOISE_PHILOX);
-        // embedding tables of the next FM_TAB_SLOTS steps in one launch
-        if (i % FM_TAB_SLOTS == 0) {
-            const int nt = n_steps - i < FM_TAB_SLOTS ? n_steps - i : FM_TAB_SLOTS;
-            const int rc0 = embed_table(c, st, temb + (size_t)i * tt, nt);
-            if (rc0) return rc0;
-        }
-        int rc = forward_impl(c, st, state, temb + (size_t)i * tt, prev, boot, defer_com ? 2 : 1, out, i % FM_TAB_SLOTS);
-        if (rc) return rc;
-        fm_sampled smp{};
-        fm_traj_sink frame{};      // step i's frames: the fused CTMC kernel writes them next to the state (no copy nodes per step)
-        if (sink) {
-            smp.a1 = sink->a1 ? sink->a1 + (size_t)i * b.N : nullptr;
-            smp.c1 = sink->c1 ? sink->c1 + (size_t)i * b.N : nullptr;
-            smp.e1 = sink->e1 ? sink->e1 + (size_t)i * b.U : nullptr;
-            frame.x = sink->x ? sink->x + (size_t)i * b.N * 3 : nullptr;
-            frame.a = sink->a ? sink->a + (size_t)i * b.N : nullptr;
-            frame.c = sink->c ? sink->c + (size_t)i * b.N : nullptr;
-            frame.e = sink->e ? sink->e + (size_t)i * b.U : nullptr;
-            frame.x1 = sink->x1 ? sink->x1 + (size_t)i * b.N * 3 : nullptr;
-        }
-        const bool in_kernel = sink && defer_com;      // the fused kernels write the frames too
-        rc = ctmc_impl(c, st, state, out, noise ? &noise[i] : nullptr, &steps[i], &smp, defer_com ? c->xw : nullptr, in_kernel ? &frame : nullptr);
-        if (rc) return rc;
-        if (sink && !in_kernel) {      // tensor-noise 'gat' steps (three small kernels): frames by copy
-            Launch L{c, st};
-            L.copy(frame.x, state->x_t, frame.x ? (size_t)b.N * 12 : 0);
-            L.copy(frame.a, state->a_t, frame.a ? (size_t)b.N * 4 : 0);
-            L.copy(frame.c, state->c_t, frame.c ? (size_t)b.N * 4 : 0);
-            L.copy(frame.e, state->e_t, frame.e ? (size_t)b.U * 4 : 0);
-            L.copy(frame.x1, out->x, frame.x1 ? (size_t)b.N * 12 : 0);
-            if (L.rc) return L.rc;
-        }
-        prev = out;
-        cur ^= 1;
-    }
-    if (final_dst) *final_dst = cur ^ 1;
-    return FM_OK;
+    if (const int rc = bound_check(c, "fm_integrate", state && steps && temb && dst_a && dst_b)) return rc;
+    return step_driver(c, (hipStream_t)stream, state, n_steps, 1, nullptr, temb, prev0, dst_a, dst_b, sink, final_dst,
+                       [&](int i, const fm_dst* prev, const fm_step_scalars*& sc, const fm_step_noise*& nz, MixedStep&) {
+        sc = &steps[i]; nz = noise ? &noise[i] : nullptr;
+        return !prev && steps[i].t == 0.0f ? 1 : 0; });
 }
 
-// what both per-molecule-time entry points refuse (the model families whose time does not enter through the embedding table alone)
-static int mixed_check(fm_ctx* c, const char* fn, int n_groups) {
-    if (!c->bound) return fail(c, FM_ERR_STATE, "%s: no batch bound", fn);
+// what both per-molecule-time entry points refuse: bound_check's, and the model families whose time does not enter through the embedding table alone
+static int mixed_check(fm_ctx* c, const char* fn, bool args_ok, int n_groups) {
+    if (const int rc = bound_check(c, fn, args_ok)) return rc;
     if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) are not supported with per-molecule time", fn);
     if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
     return FM_OK;
@@ -1271,16 +1266,15 @@ static int mixed_check(fm_ctx* c, const char* fn, int n_groups) {
 
 int fm_forward_mixed(fm_ctx* c, void* stream, const fm_state* state, const float* temb, int n_groups, const int32_t* mol_group, const fm_dst* prev,
                      int bootstrap, int remove_com, const fm_dst* out) {
-    if (!c || !state || !temb || !mol_group || !out) return fail(c, FM_ERR_INVALID, "fm_forward_mixed: null argument");
-    if (const int rc = mixed_check(c, "fm_forward_mixed", n_groups)) return rc;
+    if (const int rc = mixed_check(c, "fm_forward_mixed", state && temb && mol_group && out, n_groups)) return rc;
     return forward_impl(c, (hipStream_t)stream, state, temb, prev, bootstrap, remove_com ? 1 : 0, out, -1, mol_group, n_groups);
 }
 
 int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
                        const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
                        const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst) {
-    if (!c || !state || !steps || !steps_dev || !active || !active_dev || !mol_group || !temb || !dst_a || !dst_b) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: null argument");
-    if (const int rc = mixed_check(c, "fm_integrate_mixed", n_groups)) return rc;
+    const bool args_ok = state && steps && steps_dev && active && active_dev && mol_group && temb && dst_a && dst_b;
+    if (const int rc = mixed_check(c, "fm_integrate_mixed", args_ok, n_groups)) return rc;
     if (sink) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: a trajectory sink is not supported with per-molecule time");
     // the launch decisions are made from the host copy, before anything is enqueued
     for (int i = 0; i < n_steps * n_groups; ++i) {
@@ -1295,29 +1289,11 @@ int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_ste
         if (at0 && later) return fail(c, FM_ERR_INVALID, "fm_integrate_mixed: prev0 is NULL and only %d of %d active groups are at t = 0: start the groups at t = 0 in a call of their own", at0, at0 + later);
         boot0 = at0 ? 1 : 0;
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int tt = c->cfg.time_embedding_dim;
-    const int spc = FM_TAB_SLOTS / n_groups;      // steps per table launch: every (step, group) of a chunk owns a slot
-    const fm_dst* prev = prev0;
-    int cur = (prev0 && prev0->x == dst_a->x) ? 1 : 0;
     static const fm_step_scalars philox_step = [] { fm_step_scalars s{}; s.dfm_type = FM_DFM_CAMPBELL; s.noise_mode = FM_NOISE_PHILOX; return s; }();
-    for (int i = 0; i < n_steps; ++i) {
-        const fm_dst* out = cur == 0 ? dst_a : dst_b;
-        if (i % spc == 0) {
-            const int nt = n_steps - i < spc ? n_steps - i : spc;
-            const int rc0 = embed_table(c, st, temb + (size_t)i * n_groups * tt, nt * n_groups);
-            if (rc0) return rc0;
-        }
-        int rc = forward_impl(c, st, state, nullptr, prev, i == 0 ? boot0 : 0, 2, out, (i % spc) * n_groups, mol_group);
-        if (rc) return rc;
-        const MixedStep ms{steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
-        rc = ctmc_impl(c, st, state, out, nullptr, &philox_step, nullptr, c->xw, nullptr, &ms);
-        if (rc) return rc;
-        prev = out;
-        cur ^= 1;
-    }
-    if (final_dst) *final_dst = cur ^ 1;
-    return FM_OK;
+    return step_driver(c, (hipStream_t)stream, state, n_steps, n_groups, mol_group, temb, prev0, dst_a, dst_b, nullptr, final_dst,
+                       [&](int i, const fm_dst*, const fm_step_scalars*& sc, const fm_step_noise*&, MixedStep& mixed) {
+        sc = &philox_step; mixed = {steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
+        return i == 0 ? boot0 : 0; });
 }
 
 int fm_set_tap(fm_ctx* c, const char* name, void* dst) {
@@ -1328,18 +1304,13 @@ int fm_set_tap(fm_ctx* c, const char* name, void* dst) {
 int fm_clear_taps(fm_ctx* c) { if (c) c->taps.clear(); return FM_OK; }
 
 int fm_batch_query(fm_ctx* c, void* stream, const char* name, int32_t* dst) {
-    if (!c || !name || !dst) return fail(c, FM_ERR_INVALID, "fm_batch_query: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_batch_query: no batch bound");
-    const FmBatch& b = c->b;
-    const std::string n = name;
-    const int* src = nullptr; size_t cnt = 0;
-    if (n == "e_src") { src = b.e_src; cnt = b.E; } else if (n == "e_dst") { src = b.e_dst; cnt = b.E; }
-    else if (n == "e_pair") { src = b.e_pair; cnt = b.E; } else if (n == "p_e0") { src = b.p_e0; cnt = b.U; }
-    else if (n == "p_e1") { src = b.p_e1; cnt = b.U; } else if (n == "node_mol") { src = b.node_mol; cnt = b.N; }
-    else if (n == "pair_mol") { src = b.pair_mol; cnt = b.U; }
-    else return fail(c, FM_ERR_INVALID, "fm_batch_query: unknown array %s", name);
-    FM_HIP(c, hipMemcpyAsync(dst, src, cnt * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return FM_OK;
+    if (const int rc = bound_check(c, "fm_batch_query", name && dst)) return rc;
+    const FmBatch& b = c->ws.b;
+    const struct { const char* name; const int* src; int cnt; } arrays[] = {{"e_src", b.e_src, b.E}, {"e_dst", b.e_dst, b.E}, {"e_pair", b.e_pair, b.E},
+        {"p_e0", b.p_e0, b.U}, {"p_e1", b.p_e1, b.U}, {"node_mol", b.node_mol, b.N}, {"pair_mol", b.pair_mol, b.U}};
+    for (const auto& a : arrays)
+        if (!strcmp(name, a.name)) { FM_HIP(c, hipMemcpyAsync(dst, a.src, (size_t)a.cnt * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream)); return FM_OK; }
+    return fail(c, FM_ERR_INVALID, "fm_batch_query: unknown array %s", name);
 }
 
 #ifdef FM_TRACE
@@ -1356,14 +1327,13 @@ int fm_tlog_read(unsigned long long* out, int reset) {
 
 int fm_stability(fm_ctx* c, void* stream, const fm_state* state, const uint32_t* table, int n_types, int fake_atom_token,
                  int explicit_aromaticity, int32_t* out) {
-    if (!c || !state || !table || !out) return fail(c, FM_ERR_INVALID, "fm_stability: null argument");
-    if (!c->bound) return fail(c, FM_ERR_STATE, "fm_stability: no batch bound");
+    if (const int rc = bound_check(c, "fm_stability", state && table && out)) return rc;
     if (!state->a_t || !state->c_t || !state->e_t) return fail(c, FM_ERR_INVALID, "fm_stability: state tokens missing");
     Launch L{c, (hipStream_t)stream};
     FmStabArgs a{};
-    a.b = c->b; a.a = state->a_t; a.c = state->c_t; a.e = state->e_t; a.table = table; a.n_types = n_types; a.n_charges = c->nc;
+    a.b = c->ws.b; a.a = state->a_t; a.c = state->c_t; a.e = state->e_t; a.table = table; a.n_types = n_types; a.n_charges = c->nc;
     a.fake_tok = fake_atom_token; a.ne = c->ne; a.arom = explicit_aromaticity; a.out = out;
-    L("stability", fm_k_stability, dim3(c->b.B), dim3(64), (size_t)c->plan.nmax * 8, a);
+    L("stability", fm_k_stability, dim3(c->ws.b.B), dim3(64), (size_t)c->plan.nmax * 8, a);
     return L.rc;
 }
 

@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/flowmol_hip.h"
@@ -87,6 +88,16 @@ struct BatchPlan {
     int ctmc_threads = 256;   // workgroup size of fm_k_ctmc_fused and fm_k_ctmc_gat_fused (256 | 1024)
 };
 
+// The bound batch's pointers into the caller's workspace: ws_carve (fm_engine.cpp) names every region once, in layout order, with its size
+struct Workspace {
+    FmBatch b{};              // the destination-sorted edge layout (fm_k_batch_setup fills the arrays)
+    float *s = nullptr, *v = nullptr, *xw = nullptr, *ef = nullptr, *Ps = nullptr, *Asd = nullptr, *PV = nullptr, *Psd = nullptr, *PVd = nullptr;
+    float *part_s = nullptr, *part_v = nullptr, *s_tab_base = nullptr, *tap_s = nullptr, *tap_v = nullptr, *Q[2] = {nullptr, nullptr};
+    fm_dst boot{};            // the bootstrap evaluation's endpoint prediction
+    int* mol_gid = nullptr;   // [B] global molecule ids of the Philox noise streams
+    int32_t* x1[3] = {nullptr, nullptr, nullptr};      // sampled endpoint tokens a, c, e of a step whose caller passes no fm_sampled
+};
+
 }  // namespace fmh
 using namespace fmh;
 
@@ -98,7 +109,6 @@ struct fm_ctx {
     int n_cus = 256;          // compute units of the device (fm_create); read by plan_batch only
     ModelPlan mp{};           // the weight copies this model has (fm_create)
     const void *sc_node_W1q = nullptr, *sc_node_W2q = nullptr, *node_head_W1q = nullptr, *node_head_W2q = nullptr;      // quad-row packed copies for fm_k_mlp4
-    float* Q[2] = {nullptr, nullptr};      // (U,256) each, in the workspace
     float rbf_mu_step = 0.f, rbf_inv_sigma = 0.f;
     // ---- weights (one device arena)
     char* arena = nullptr; size_t arena_bytes = 0;
@@ -112,15 +122,9 @@ struct fm_ctx {
     // ---- batch binding
     bool bound = false;
     BatchPlan plan{};         // the bound batch's launch choices (plan_batch)
-    FmBatch b{};
-    float *s = nullptr, *v = nullptr, *xw = nullptr, *ef = nullptr, *Ps = nullptr, *Asd = nullptr, *PV = nullptr;
-    float *part_s = nullptr, *part_v = nullptr, *s_tab = nullptr, *Psd = nullptr, *PVd = nullptr;
-    float* s_tab_base = nullptr; size_t tab_slot_floats = 0;      // FM_TAB_SLOTS embedding tables (one per step of a chunk); s_tab = the current step's
+    Workspace ws{};           // the bound batch's pointers into the caller's workspace (ws_carve)
+    float* s_tab = nullptr; size_t tab_slot_floats = 0;      // the current step's embedding table, one of the FM_TAB_SLOTS at ws.s_tab_base; floats per slot
     const int* tab_slot = nullptr;      // per-molecule time: the caller's device (n_mols) table slot of every molecule, counted from s_tab; null = one table (set with s_tab)
-    float *tap_s = nullptr, *tap_v = nullptr;    // scratch of the aggregated-message taps (parity runs only)
-    fm_dst boot{};
-    int32_t *sa1 = nullptr, *sc1 = nullptr, *se1 = nullptr;
-    int* mol_gid = nullptr;   // [B] global molecule ids of the Philox noise streams
     // ---- pinned host staging of the per-molecule descriptor arrays (fm_batch_bind / fm_set_molecule_ids: 16 B per molecule).  The copies
     // read it asynchronously; `stage_ev` marks their completion, so the next writer waits for THAT event only (long complete by then) and
     // no entry point ever synchronises the stream.
@@ -166,6 +170,26 @@ inline size_t lds_proj(int V, int tm = FM_TM) { return ((size_t)tm * 260 + 3 * (
 inline size_t lds_edge_upd(int TM) { return ((size_t)TM * 164 + TM * 132) * 4 + TM * 4 * 4 + 16; }
 inline size_t lds_edge_upd_sp(int TM) { return (size_t)TM * 132 * 4 + (size_t)TM * 176 * 2 * 2 + TM * 3 * 4; }
 
+inline int bound_check(fm_ctx* c, const char* fn, bool args_ok) {      // what every entry point on the bound batch refuses first; args_ok: no required pointer is null
+    if (!c || !args_ok) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    return c->bound ? FM_OK : fail(c, FM_ERR_STATE, "%s: no batch bound", fn);
+}
+
+// The categorical modalities of the bound batch, m = 0: atom types, 1: charges (both over the node rows), 2: bond orders (over the unordered pairs).  Every
+// per-modality loop of the engine reads this table, and the kernels' own Fm*Mod structs are filled from it.
+struct Modality {
+    int rows, K;                    // rows of the batch, real categories (mask token = K)
+    const int *off, *mol;           // [B+1] first row of every molecule, [rows] molecule of every row
+    int32_t *tok, *x1;              // [rows] the state's tokens (null without a state), the workspace's endpoint-token buffer
+};
+inline Modality modality(const fm_ctx* c, int m, const fm_state* state = nullptr) {
+    const FmBatch& b = c->ws.b;
+    int32_t* const tok = !state ? nullptr : m == 0 ? state->a_t : m == 1 ? state->c_t : state->e_t;
+    if (m == 2) return {b.U, c->ne, b.mol_pair_off, b.pair_mol, tok, c->ws.x1[2]};
+    return {b.N, m == 0 ? c->na : c->nc, b.mol_node_off, b.node_mol, tok, c->ws.x1[m]};
+}
+template <class T> T pick3(int m, T a, T c, T e) { return m == 0 ? a : m == 1 ? c : e; }      // the a / c / e member of a struct that spells the modalities out
+
 // ---------------------------------------------------------------------------------------- launch helper
 inline int kid_of(fm_ctx* c, const char* name) {
     for (size_t i = 0; i < c->prof_names.size(); ++i) if (c->prof_names[i] == name) return (int)i;
@@ -195,15 +219,18 @@ struct Launch {
         hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) rc = fail(c, FM_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
     }
-    void zero(void* dst, size_t bytes) {
-        if (rc != FM_OK || bytes == 0) return;
-        hipError_t e = hipMemsetAsync(dst, 0, bytes, st);
-        if (e != hipSuccess) rc = fail(c, FM_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
+};
+
+// The taps of one evaluation, resolved once: `on` is false when the evaluation takes none or none is registered (every production step), and then no name
+// is built and no lookup made.  Indexed names are "<stem><i><suffix>" (conv0.s, upd1.ef).
+struct Taps {
+    Launch& L; bool on;
+    void* find(const char* stem, int i = -1, const char* suffix = "") const {       // the registered destination of "<stem>" (i < 0) or "<stem><i><suffix>", or null
+        if (!on) return nullptr;
+        const auto it = L.c->taps.find(i < 0 ? std::string(stem) : stem + std::to_string(i) + suffix);
+        return it == L.c->taps.end() ? nullptr : it->second;
     }
-    void tap(const std::string& name, const void* src, size_t bytes) {
-        auto it = c->taps.find(name);
-        if (it != c->taps.end()) copy(it->second, src, bytes);
-    }
+    void operator()(const void* src, size_t bytes, const char* stem, int i = -1, const char* suffix = "") const { if (void* d = find(stem, i, suffix)) L.copy(d, src, bytes); }
 };
 
 // ---------------------------------------------------------------------------------------- kernel instance lists
