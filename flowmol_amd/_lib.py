@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 9
+FM_ABI_VERSION = 10
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
@@ -96,6 +96,10 @@ class fm_prior_spec(C.Structure):
     _fields_ = [('mod', fm_prior_mod * 3)]
 
 
+class fm_cond_tape(C.Structure):
+    _fields_ = [('x0', C.c_void_p), ('u_a', C.c_void_p), ('u_c', C.c_void_p), ('u_e', C.c_void_p)]
+
+
 class FlowMolHipError(RuntimeError):
     pass
 
@@ -128,6 +132,9 @@ _EXPORTS = {
     'fm_integrate_mixed': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_int, C.c_int, C.POINTER(fm_step_scalars), C.c_void_p,
                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_dst), C.POINTER(fm_dst), C.POINTER(fm_dst),
                                      C.POINTER(fm_traj_sink), C.POINTER(C.c_int)]),
+    # ABI 10: conditional path of given molecules
+    'fm_conditional_path': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fm_state), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fm_state),
+                                      C.POINTER(fm_cond_tape)]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

@@ -982,6 +982,8 @@ __device__ __forceinline__ void fm_row_stats8(const float* row, int n, int sub, 
 //   c2 = 0xFFFFFFFE - job, categorical priors of endpoint models (fm_k_prior_philox_dense):  blocks 0..3 = the row's d <= 16 NORMAL draws, the position prior's Box-Muller,
 //        block b -> normals 4b..4b+3 = r0 cos t0, r0 sin t0, r1 cos t1, r1 sin t1 (normal j belongs to category j; every prior kind that needs normals reads these);
 //        blocks 4..7 = the row's d Exp(1) draws (uniform simplex; Exp race of marginal / c-given-a), same word order as the CTMC draws
+//   c2 = 0xFFFFFFFE - job, conditional path of CTMC models (fm_k_conditional_path):  block 8 word 0 = the row's uniform u (fm_u01; masked when u < 1 - alpha_t);
+//        its positions' x_0 is the position prior's entry above
 // (step * 4 + job reaches 0xFFFFFFFC only after 2^30 steps.)  fm_philox_tape writes a step's draws out through the same functions.
 struct FmPhilox4 { unsigned v[4]; };
 __device__ __forceinline__ FmPhilox4 fm_philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {

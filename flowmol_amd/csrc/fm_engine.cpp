@@ -1211,6 +1211,33 @@ int fm_philox_tape(fm_ctx* c, void* stream, const fm_step_scalars* sc, const fm_
     return L.rc;
 }
 
+int fm_conditional_path(fm_ctx* c, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                        const fm_state* out, const fm_cond_tape* tape) {
+    if (const int rc = bound_check(c, "fm_conditional_path", x1 && alpha && out)) return rc;
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_conditional_path: endpoint models (has_mask = 0) have no masked conditional path");
+    if (n_groups < 1) return fail(c, FM_ERR_INVALID, "fm_conditional_path: n_groups = %d, need at least 1", n_groups);
+    if (n_groups > 1 && !mol_group) return fail(c, FM_ERR_INVALID, "fm_conditional_path: mol_group is NULL with n_groups = %d", n_groups);
+    const FmBatch& b = c->ws.b;
+    if (!x1->x_t || !out->x_t) return fail(c, FM_ERR_INVALID, "fm_conditional_path: null argument");
+    if (out->x_t == x1->x_t) return fail(c, FM_ERR_INVALID, "fm_conditional_path: out->x_t aliases x1->x_t (the call is not in-place)");
+    FmCondArgs a{};
+    static const char* const tag[3] = {"a_t", "c_t", "e_t"};
+    for (int m = 0; m < 3; ++m) {
+        const Modality md = modality(c, m);
+        const int32_t* const t1 = pick3(m, x1->a_t, x1->c_t, x1->e_t);
+        int32_t* const to = pick3(m, out->a_t, out->c_t, out->e_t);
+        if (md.rows > 0 && (!t1 || !to)) return fail(c, FM_ERR_INVALID, "fm_conditional_path: null argument");
+        if (to && to == t1) return fail(c, FM_ERR_INVALID, "fm_conditional_path: out->%s aliases x1->%s (the call is not in-place)", tag[m], tag[m]);
+        a.mod[m] = {md.K, t1, to, tape ? pick3(m, tape->u_a, tape->u_c, tape->u_e) : nullptr, md.off};
+    }
+    a.x1 = x1->x_t; a.x_t = out->x_t; a.x0 = tape ? tape->x0 : nullptr; a.node_off = b.mol_node_off;
+    a.mol_gid = c->ws.mol_gid; a.mol_group = n_groups > 1 ? mol_group : nullptr; a.alpha = alpha;
+    a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
+    Launch L{c, (hipStream_t)stream};
+    L("conditional_path", fm_k_conditional_path, dim3(b.B, 4), dim3(256), 0, a);
+    return L.rc;
+}
+
 int fm_forward(fm_ctx* c, void* stream, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap, int remove_com,
                const fm_dst* out) {
     if (const int rc = bound_check(c, "fm_forward", state && temb && out)) return rc;

@@ -2091,6 +2091,61 @@ static __global__ void __launch_bounds__(256) fm_k_prior_philox_dense(FmPriorDen
 }
 
 // ------------------------------------------------------------------------------------------------
+// Conditional path g_t ~ p(g_t | g_0, g_1) of a CTMC model for given molecules g_1 (fm_conditional_path; reference CTMCVectorField.sample_conditional_path,
+// flowmol/models/ctmc_vector_field.py:97-143, t of shape (B,)), from the per-molecule Philox streams.  Grid (B, 4) like fm_k_prior_philox_dense: jobs 0..2 =
+// a_t / c_t / e_t over the molecule's rows (e: unordered pairs), job 3 = the positions.  Molecule m reads row mol_group[m] (row 0 without groups) of
+// alpha (n_groups, 4) = alpha_t of x, a, c, e: workgroup-uniform.
+//   job 3 (:112): x_t = (1 - alpha_x) x_0 + alpha_x (x_1 - per-molecule mean), x_0 = the position prior (fm_prior_x_molecule: fm_prior_philox's bits, staged
+//          through x_t), the mean with fm_k_remove_com's arithmetic, the three operations rounded separately as torch rounds them
+//   jobs 0..2 (:122-134): tok_t = u < 1 - alpha ? mask : tok_1, u = fm_u01(word 0 of block 8) of counter (global molecule id, row, 0xFFFFFFFE - job, 8):
+//          blocks 0..7 of that c2 are the dense priors' (endpoint models), block 8 is this entry's
+// Optional tape: x0 (N,3) and the uniforms u (rows) the call consumed.  Reads x1 only; writes out and the tape only.
+// ------------------------------------------------------------------------------------------------
+struct FmCondMod { int K; const int* tok1; int* out; float* u; const int* off; };
+struct FmCondArgs {
+    FmCondMod mod[3];
+    const float* x1; float* x_t; float* x0; const int* node_off;
+    const int* mol_gid; const int* mol_group; const float* alpha;
+    unsigned seed_lo, seed_hi;
+};
+
+static __global__ void __launch_bounds__(256) fm_k_conditional_path(FmCondArgs a) {
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    const unsigned gid = (unsigned)a.mol_gid[mol];
+    const float* al = a.alpha + (a.mol_group ? a.mol_group[mol] : 0) * 4;
+    if (job == 3) {
+        const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
+        const float ax = al[0], bx = fm_sub_rn(1.0f, ax);
+        __shared__ float com[3];
+        if (tid < 64) {
+            fm_prior_x_molecule(a.x_t, n0, n1, gid, tid, a.seed_lo, a.seed_hi);      // x_0, read back behind the barrier
+            float sx = 0.f, sy = 0.f, sz = 0.f;          // the 64-lane strided sum + xor tree of fm_k_remove_com: identical rounding
+            for (int n = n0 + tid; n < n1; n += 64) { sx += a.x1[n * 3]; sy += a.x1[n * 3 + 1]; sz += a.x1[n * 3 + 2]; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+            const float inv = 1.0f / (float)(n1 - n0);
+            if (tid == 0) { com[0] = sx * inv; com[1] = sy * inv; com[2] = sz * inv; }
+        }
+        __syncthreads();
+        for (int i = n0 * 3 + tid; i < n1 * 3; i += 256) {
+            const float x0 = a.x_t[i], x1c = a.x1[i] - com[(i - n0 * 3) % 3];
+            if (a.x0) a.x0[i] = x0;
+            a.x_t[i] = fm_add_rn(fm_mul_rn(bx, x0), fm_mul_rn(ax, x1c));
+        }
+        return;
+    }
+    const FmCondMod md = a.mod[job];
+    const float thr = fm_sub_rn(1.0f, al[1 + job]);
+    const int r0 = md.off[mol], r1 = md.off[mol + 1];
+    for (int i = r0 + tid; i < r1; i += 256) {
+        const FmPhilox4 rn = fm_philox4x32(gid, (unsigned)(i - r0), 0xFFFFFFFEu - (unsigned)job, 8u, a.seed_lo, a.seed_hi);
+        const float u = fm_u01(rn.v[0]);
+        if (md.u) md.u[i] = u;
+        md.out[i] = u < thr ? md.K : md.tok1[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Valence stability + connectivity of the sampled molecules straight from the final tokens (reference
 // flowmol/analysis/metrics.py:96-117,333-363 with molecule_builder.py:138-157,217-265: fake atoms removed,
 // mask bond token = no bond, valency = sum of bond orders with aromatic = 1.5).  One workgroup per molecule.

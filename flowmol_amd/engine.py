@@ -519,6 +519,41 @@ class Engine:
             self._check(self.lib.fm_philox_tape(self._ctx, self._stream(), C.byref(sc), C.byref(cs)), 'fm_philox_tape')
         return nz
 
+    def conditional_path(self, x1_state, alphas, mol_group=None, seed: int = None, tape: bool = False):
+        """g_t ~ p(g_t | g_0, g_1) for the bound batch's molecules ``x1_state`` (a token state dict, real categories only; left untouched), the
+        reference's CTMCVectorField.sample_conditional_path (ctmc_vector_field.py:97-143) in one launch (fm_conditional_path) with x_0 and the uniforms
+        from the per-molecule Philox streams of ``seed``.  ``alphas``: (G, 4) -- or (4,) for one group -- rows of ``alpha_tables(t)[0]``, alpha_t of
+        x, a, c, e at each time group's t; ``mol_group`` (B,): every molecule's group (None with one group).  Returns the new state dict; with
+        ``tape`` also {'x0', 'u_a', 'u_c', 'u_e'}: the draws the call consumed."""
+        if seed is None:
+            raise ValueError('conditional_path draws from the Philox streams: seed is required')
+        d = self.device
+        al = torch.as_tensor(alphas).detach().to('cpu', torch.float32).reshape(-1, 4).contiguous()
+        G = int(al.shape[0])
+        group = None
+        if mol_group is not None:
+            group = torch.as_tensor(mol_group).detach().to('cpu', torch.int32).reshape(-1)
+            if group.shape[0] != self.B or int(group.min()) < 0 or int(group.max()) >= G:
+                raise ValueError(f'mol_group must hold one group index in [0, {G}) per bound molecule')
+            group = group.to(d)
+        elif G != 1:
+            raise ValueError(f'{G} rows of alphas need mol_group')
+        al = al.to(d)
+        i32 = dict(dtype=torch.int32, device=d)
+        out = {'x_t': torch.empty(self.N, 3, device=d), 'a_t': torch.empty(self.N, **i32), 'c_t': torch.empty(self.N, **i32), 'e_t': torch.empty(self.U, **i32)}
+        tp = cs = None
+        if tape:
+            tp = {'x0': torch.empty(self.N, 3, device=d), 'u_a': torch.empty(self.N, device=d), 'u_c': torch.empty(self.N, device=d), 'u_e': torch.empty(self.U, device=d)}
+            cs = _lib.fm_cond_tape()
+            cs.x0, cs.u_a, cs.u_c, cs.u_e = _ptr(tp['x0']), _ptr(tp['u_a']), _ptr(tp['u_c']), _ptr(tp['u_e'])
+        s1, so = self._state_struct(x1_state), self._state_struct(out)
+        with self._dev():
+            rc = self.lib.fm_conditional_path(self._ctx, self._stream(), C.c_uint64(seed), C.byref(s1), G, _ptr(group), _ptr(al), C.byref(so),
+                                              C.byref(cs) if cs is not None else None)
+        self._check(rc, 'fm_conditional_path')
+        self._keep = [x1_state, al, group, out, tp]
+        return (out, tp) if tape else out
+
     def stability(self, state, table: torch.Tensor, fake_atom_token: int = -1, explicit_aromaticity: bool = False) -> torch.Tensor:
         """Valence stability + connectivity of the bound batch's molecules from their tokens, on the device
         (see fm_stability).  table: (n_types, n_charges) int32 bit masks.  Returns (B,4) int32:

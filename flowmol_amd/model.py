@@ -23,7 +23,7 @@ import torch.distributed as dist
 
 from . import _lib, presets, shard
 from .config import VFConfig, from_reference_hparams
-from .engine import Engine, StepNoise, cat_temp_schedule, forward_weight_schedule, make_step_plan
+from .engine import Engine, IntegrationRun, StepNoise, alpha_tables, cat_temp_schedule, forward_weight_schedule, make_step_plan
 from .molecule import SampledMolecule
 from .priors import (adapt_prior, categorical_prior, default_marginals, draw_categorical_priors,          # noqa: F401  (re-exported)
                      load_marginal_dists, simplex_projection)
@@ -323,6 +323,126 @@ class FlowMol:
         frames = _frames_of(init, traj) if visualize and (frames_in_tuple or not return_tensors) else None
         return self._finish(state, req.n_atoms, frames, return_tensors, frames_in_tuple, xt_traj, ep_traj, t_integrate)
 
+    # ------------------------------------------------------------------ resampling given molecules
+    @torch.no_grad()
+    def resample(self, molecules, start_step, n_timesteps=None, seed=None, mol_ids=None, stochasticity=None, high_confidence_threshold=None,
+                 return_tensors=False, xt_traj=False, ep_traj=False, **kwargs):
+        """Variations of given molecules (no reference entry point; its parts are the reference's): molecule *i* is noised back to time point
+        ``k = start_step[i]`` of its ``T = n_timesteps[i]``-point schedule, ``t = linspace(0, 1, T)[k]``, with the model's own corruption process
+        (CTMCVectorField.sample_conditional_path, ctmc_vector_field.py:97-143: the distribution the network was trained on), and then takes steps
+        ``k .. T-2`` of the unchanged Philox plan of a full ``T``-point run -- the step indices, and so the draws, of ``sample``.  ``start_step = 0``
+        is ``sample`` itself (whatever the molecules hold), ``start_step = T - 1`` returns the centred input; in between, the later the start the
+        closer the result stays to the input.
+
+        ``molecules``: a list of SampledMolecule (their raw x_1, a_1, c_1, e_1, fake atoms included) or the ``(tensors, n_atoms)`` pair of
+        ``sample(return_tensors=True)``; every token must be a real category.  ``start_step`` / ``n_timesteps``: an int, or one per molecule
+        (at most 32 distinct pairs per call).  Noise is Philox only: ``seed`` is required, ``mol_ids`` (default 0..B-1) name the streams.  Molecule *i*
+        is, bit for bit, ``resample([mol_i], start_step[i], n_timesteps[i], seed, mol_ids=[id_i])``.  ``xt_traj`` / ``ep_traj`` (one (T, k) for all
+        molecules only) record T - k frames, frame 0 being the corrupted state.  Raises NotImplementedError for endpoint models, ``tspan``, dfm_type
+        'gat' with a per-molecule argument, trajectories with several (T, k) pairs and more than 32 of those; ``return_tensors`` as in ``sample``."""
+        cfg = self.cfg
+        # ---- arguments: every refusal before the bind and before anything is enqueued; no generator is touched
+        if cfg.parameterization == 'endpoint':
+            raise NotImplementedError('resample: endpoint models are not supported (they have no masked conditional path)')
+        unknown = set(kwargs) - RESAMPLE_KWARGS
+        if unknown:
+            raise TypeError(f'resample() got unexpected keyword arguments {sorted(unknown)}')
+        if kwargs.get('tspan') is not None:
+            raise NotImplementedError('resample: tspan is not supported (start_step indexes the linspace(0, 1, n_timesteps) schedule)')
+        if seed is None:
+            raise ValueError('resample draws from the per-molecule Philox streams: seed is required')
+        dfm_type = kwargs.get('dfm_type') or cfg.dfm_type
+        if dfm_type not in ('campbell', 'gat'):
+            raise ValueError(f"Invalid dfm_type: {dfm_type}")
+        ks, Ts = _step_counts(start_step), _step_counts(n_timesteps)
+        if dfm_type == 'gat' and (ks is not None or Ts is not None):
+            raise NotImplementedError("resample with per-molecule start_step / n_timesteps: dfm_type 'gat' is not supported")
+        x1, n_atoms = self._given_molecules(molecules)
+        B = int(n_atoms.numel())
+        ks = [int(start_step)] * B if ks is None else ks
+        Ts = [int(self.default_n_timesteps if n_timesteps is None else n_timesteps)] * B if Ts is None else Ts
+        if len(ks) != B or len(Ts) != B:
+            raise ValueError(f'start_step / n_timesteps must be an int or give one entry per molecule ({B})')
+        if any(T < 1 or k < 0 or k > T - 1 for k, T in zip(ks, Ts)):
+            raise ValueError('start_step must lie in 0 .. n_timesteps - 1 (and n_timesteps >= 1)')
+        ids = list(range(B)) if mol_ids is None else [int(v) for v in torch.as_tensor(mol_ids).reshape(-1).tolist()]
+        if len(ids) != B:
+            raise ValueError(f'mol_ids has {len(ids)} entries for {B} molecules')
+        pairs = sorted(set(zip(Ts, ks)))
+        visualize = bool(xt_traj or ep_traj)
+        if len(pairs) > 1 and visualize:
+            raise NotImplementedError('resample with several (n_timesteps, start_step) pairs: xt_traj / ep_traj are not supported (no trajectory sink)')
+        if len(pairs) > _lib.FM_TAB_SLOTS:
+            raise NotImplementedError(f'more than {_lib.FM_TAB_SLOTS} distinct (n_timesteps, start_step) pairs in one call ({len(pairs)}): split the call')
+        eng = self.engine
+        args, plan_kw = self._plan_args(stochasticity, high_confidence_threshold, kwargs, dfm_type)
+        plans = {T: make_step_plan(T, *args, philox_seed=int(seed), **plan_kw) for T in sorted({T for T, _ in pairs})}
+        alphas = {(T, k): alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k] for T, k in pairs}
+        sizes = n_atoms.tolist()
+        given = _split_molecules(x1, sizes)
+        # ---- the library refuses a NULL previous endpoint with only some groups at t = 0: molecules that start at step 0 run in an engine call of their own
+        parts = [[i for i in range(B) if ks[i] == 0], [i for i in range(B) if ks[i] > 0]]
+        parts = [p for p in parts if p]
+        results, frames, t_integrate = [None] * B, None, 0.0
+        for part in parts:
+            whole = len(part) == B
+            st1 = x1 if whole else {f: torch.cat([given[i][f] for i in part]) for f in ('x_t', 'a_t', 'c_t', 'e_t')}
+            eng.bind(n_atoms[part])
+            eng.set_molecule_ids(torch.tensor([ids[i] for i in part]))
+            st1 = eng.make_state(st1['x_t'], st1['a_t'], st1['c_t'], st1['e_t'])
+            keys = sorted({(Ts[i], ks[i]) for i in part})
+            group = [keys.index((Ts[i], ks[i])) for i in part]
+            state = eng.conditional_path(st1, torch.stack([alphas[key] for key in keys]), group if len(keys) > 1 else None, seed=int(seed))
+            t0 = time.perf_counter()
+            if len(keys) == 1:
+                (T, k), traj, init = keys[0], None, None
+                if visualize:
+                    traj, init = eng.new_traj(T - 1), _tokens(state, copy=True)
+                IntegrationRun(eng, state, plans[T], None, traj=traj).run(k, T - 1)
+                eng.synchronize()
+                if visualize:
+                    frames = _frames_of(init, {f: v[k:] for f, v in traj.items()})
+            else:
+                eng.integrate_mixed(state, [plans[T] for T, _ in keys], group, start=[k for _, k in keys])
+                eng.synchronize()
+            t_integrate += time.perf_counter() - t0
+            if whole:
+                final = state
+            else:
+                for i, s_ in zip(part, _split_molecules(state, [sizes[i] for i in part])):
+                    results[i] = s_
+        if len(parts) > 1:
+            final = {f: torch.cat([results[i][f] for i in range(B)]).contiguous() for f in ('x_t', 'a_t', 'c_t', 'e_t')}
+        return self._finish(final, n_atoms, frames if not return_tensors else None, return_tensors, False, xt_traj, ep_traj, t_integrate)
+
+    def _given_molecules(self, molecules):
+        """The molecules of a ``resample`` call as one token state on the CPU ({'x_t' (N,3) float32, 'a_t', 'c_t' (N), 'e_t' (U) int64}) and their
+        sizes; ValueError for a token that is not a real category (a mask token, an index out of range) or for shapes that do not fit the sizes."""
+        cfg = self.cfg
+        if isinstance(molecules, (tuple, list)) and len(molecules) == 2 and isinstance(molecules[0], dict):
+            t, n_atoms = molecules
+            n_atoms = torch.as_tensor(n_atoms).detach().to('cpu', torch.int64).reshape(-1)
+            x1 = {f'{k}_t': torch.as_tensor(t[k]).detach().cpu() for k in 'xace'}
+        else:
+            mols = list(molecules)
+            if not mols or not all(isinstance(m, SampledMolecule) for m in mols):
+                raise ValueError('molecules must be a non-empty list of SampledMolecule or the (tensors, n_atoms) pair of sample(return_tensors=True)')
+            n_atoms = torch.tensor([int(m.x_1.shape[0]) for m in mols], dtype=torch.int64)
+            x1 = {'x_t': torch.cat([m.x_1.detach().cpu() for m in mols]), 'a_t': torch.cat([m.a_1.detach().cpu() for m in mols]),
+                  'c_t': torch.cat([m.c_1.detach().cpu() for m in mols]), 'e_t': torch.cat([m.e_1.detach().cpu() for m in mols])}
+        if n_atoms.numel() == 0 or int(n_atoms.min()) < 1:
+            raise ValueError('resample needs at least one molecule, each with at least one atom')
+        N, U = int(n_atoms.sum()), int((n_atoms * (n_atoms - 1) // 2).sum())
+        x1['x_t'] = x1['x_t'].to(torch.float32)
+        if tuple(x1['x_t'].shape) != (N, 3) or tuple(x1['a_t'].shape) != (N,) or tuple(x1['c_t'].shape) != (N,) or tuple(x1['e_t'].shape) != (U,):
+            raise ValueError(f'molecule tensors do not fit the sizes: need x ({N}, 3), a ({N},), c ({N},), e ({U},) per unordered pair')
+        for f, K, what in (('a_t', cfg.n_atom_types, 'atom type'), ('c_t', cfg.n_charges, 'charge'), ('e_t', cfg.n_bond_types, 'bond order')):
+            tok = x1[f] = x1[f].to(torch.int64)
+            if tok.numel() and (int(tok.min()) < 0 or int(tok.max()) >= K):
+                raise ValueError(f'resample: {what} tokens must be real categories 0 .. {K - 1} (no mask token, nothing out of range); '
+                                 f'got {int(tok.min())} .. {int(tok.max())}')
+        return x1, n_atoms
+
     # ---- stage 1: arguments
     def _request(self, n_atoms, n_timesteps, kwargs, xt_traj=False, ep_traj=False, noise=None) -> "_Request":
         """What every entry point does first: name the path, refuse what it does not take -- before the bind and before any draw from a generator --
@@ -485,6 +605,16 @@ ALLOWED_KWARGS = {
     'endpoint': {'inv_temp_func', 'tspan', '_rows', '_frames'} | _PHILOX_KWARGS,
     'mixed': {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'} | _PHILOX_KWARGS,
 }
+
+
+RESAMPLE_KWARGS = {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'}       # resample(): Philox only, so no rng and no noise hooks
+
+
+def _split_molecules(state: Dict[str, torch.Tensor], sizes) -> List[Dict[str, torch.Tensor]]:
+    """A batch's token state {'x_t', 'a_t', 'c_t', 'e_t'} as one dict per molecule (views)."""
+    pairs = [n * (n - 1) // 2 for n in sizes]
+    cols = {k: torch.split(v, pairs if k == 'e_t' else sizes) for k, v in state.items()}
+    return [{k: cols[k][i] for k in state} for i in range(len(sizes))]
 
 
 @dataclass

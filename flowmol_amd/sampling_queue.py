@@ -4,6 +4,7 @@ running batch instead of running them back to back.
 
 Built on per-molecule time (``Engine.integrate_mixed``) and the per-molecule Philox streams: every molecule is, bit for bit, the molecule
 ``model.sample([n], n_timesteps=T, rng='philox', seed=seed, mol_ids=[id])`` run alone, whenever it was admitted and whoever it shared the batch with.
+``submit_from`` admits GIVEN molecules the same way: corrupted to a chosen step of their schedule (``FlowMol.resample``), they join from there.
 Synchronous and single-stream: ``run`` returns when its steps have run; admission happens at the start of a ``run`` call."""
 from __future__ import annotations
 
@@ -12,15 +13,16 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib
-from .engine import IntegrationRun, make_step_plan
+from .engine import IntegrationRun, alpha_tables, make_step_plan
 
 
 class _Request:
-    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev')
+    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev', 'given')
 
-    def __init__(self, ticket, n, T, mol_id):
+    def __init__(self, ticket, n, T, mol_id, start=0, given=None):
         self.ticket, self.n, self.T, self.mol_id = ticket, n, T, mol_id
-        self.pos = 0          # steps taken
+        self.pos = start      # the step it takes next: steps taken, or where a given molecule (submit_from) enters its schedule
+        self.given = given    # submit_from: the molecule to corrupt {'x_t', 'a_t', 'c_t', 'e_t'} (CPU); None: start from the prior
         self.state = None     # {'x_t', 'a_t', 'c_t', 'e_t'}: this molecule's rows, on the device
         self.prev = None      # {'x', 'a', 'c', 'e'}: its previous endpoint prediction
 
@@ -59,6 +61,32 @@ class SamplingQueue:
             tickets.append(t)
         return tickets
 
+    def submit_from(self, molecules, start_step, n_timesteps=None, mol_ids=None) -> List[int]:
+        """Queue given molecules for resampling (``FlowMol.resample``): molecule *i* is corrupted to time point ``start_step[i]`` of its
+        ``n_timesteps[i]``-point schedule at admission and joins the running batch from there; ``start_step >= n_timesteps - 1`` retires at once with the
+        corrupted state.  ``molecules`` / ``start_step`` / ``n_timesteps`` / ``mol_ids`` as in ``resample`` (ids default to the ticket numbers).  Every
+        molecule is, bit for bit, ``model.resample([mol], start_step, n_timesteps, seed, mol_ids=[id])``."""
+        x1, n_atoms = self.model._given_molecules(molecules)
+        sizes = n_atoms.tolist()
+        B = len(sizes)
+        per = lambda v, default: ([int(default if v is None else v)] * B if v is None or isinstance(v, int) or (torch.is_tensor(v) and v.dim() == 0)
+                                  else [int(x) for x in v])
+        ks, Ts = per(start_step, 0), per(n_timesteps, self.model.default_n_timesteps)
+        ids = None if mol_ids is None else [int(v) for v in torch.as_tensor(mol_ids).reshape(-1).tolist()]
+        if len(ks) != B or len(Ts) != B or (ids is not None and len(ids) != B):
+            raise ValueError('start_step / n_timesteps / mol_ids must give one entry per molecule')
+        if any(T < 1 or k < 0 or k > T - 1 for k, T in zip(ks, Ts)):
+            raise ValueError('start_step must lie in 0 .. n_timesteps - 1 (and n_timesteps >= 1)')
+        pairs = [n * (n - 1) // 2 for n in sizes]
+        cols = {f: torch.split(v, pairs if f == 'e_t' else sizes) for f, v in x1.items()}
+        tickets = []
+        for i in range(B):
+            t = self._next_ticket
+            self._next_ticket += 1
+            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1}))
+            tickets.append(t)
+        return tickets
+
     @property
     def idle(self) -> bool:
         return not self._pending and not self._running
@@ -81,35 +109,41 @@ class SamplingQueue:
         return [{k: cols[k][i] for k in d} for i in range(len(sizes))]
 
     def _admit(self):
-        """Newcomers, grouped by step count, take step 0 (prior, bootstrap evaluation, first step) through fm_integrate on a bind of their own; then
-        they join the running list, as long as the batch keeps to the 32 time groups a bind has embedding tables for."""
-        eng = self.model.engine
+        """Newcomers, grouped by schedule and entry step, take their first step through fm_integrate on a bind of their own -- from the prior (step 0:
+        bootstrap evaluation, first step) or, for given molecules, from their conditional path (step k, no previous endpoint) -- then they join the
+        running list, as long as the batch keeps to the 32 time groups a bind has embedding tables for."""
+        eng, cfg = self.model.engine, self.model.cfg
         groups = {(r.T, r.pos) for r in self._running}         # a time group = same schedule, same step
-        by_T: Dict[int, List[_Request]] = {}
+        by_key: Dict[tuple, List[_Request]] = {}
         keep = []
         for r in self._pending:
-            joins = r.T > 2                                    # T <= 2: step 0 is the whole trajectory
-            if joins and (r.T, 1) not in groups and len(groups) >= _lib.FM_TAB_SLOTS:
+            joins = r.pos + 1 < r.T - 1                        # otherwise the first step is the rest of the trajectory
+            if joins and (r.T, r.pos + 1) not in groups and len(groups) >= _lib.FM_TAB_SLOTS:
                 keep.append(r)                                 # waits for a group to finish
                 continue
             if joins:
-                groups.add((r.T, 1))
-            by_T.setdefault(r.T, []).append(r)
+                groups.add((r.T, r.pos + 1))
+            by_key.setdefault((r.T, r.pos, r.given is not None), []).append(r)
         self._pending = keep
-        for T, reqs in by_T.items():
+        for (T, k, given), reqs in by_key.items():
             sizes = [r.n for r in reqs]
             eng.bind(torch.tensor(sizes))
             eng.set_molecule_ids(torch.tensor([r.mol_id for r in reqs]))
-            state = eng.prior_state(eng.prior_philox(self.seed))
+            if given:
+                x1 = {f: torch.cat([r.given[f] for r in reqs]) for f in ('x_t', 'a_t', 'c_t', 'e_t')}
+                alpha = alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k]
+                state = eng.conditional_path(eng.make_state(x1['x_t'], x1['a_t'], x1['c_t'], x1['e_t']), alpha, seed=self.seed)
+            else:
+                state = eng.prior_state(eng.prior_philox(self.seed))
             prev = None
-            if T > 1:
+            if k < T - 1:
                 run = IntegrationRun(eng, state, self._plan(T), None)
-                run.run(0, 1)
-                eng.synchronize()
+                run.run(k, k + 1)
                 prev = run.last_dst()
+            eng.synchronize()
             st, pv = self._split(state, sizes, 'e_t'), (self._split(prev, sizes, 'e') if prev is not None else [None] * len(reqs))
             for r, s_, p_ in zip(reqs, st, pv):
-                r.state, r.prev, r.pos = s_, p_, min(1, T - 1)
+                r.state, r.prev, r.pos, r.given = s_, p_, min(k + 1, T - 1), None
                 (self._running if r.pos < T - 1 else self._done).append(r)
 
     def _retire(self, reqs):

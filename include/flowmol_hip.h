@@ -21,6 +21,8 @@
  *                       (flowmol/models/flowmol.py:417-448), from per-molecule counter-based streams instead of the CPU generator
  *   fm_philox_tape      the draws of CTMCVectorField.step's torch.multinomial / torch.rand calls (ctmc_vector_field.py:349-357,
  *                       373-388, 414-510) as the in-kernel noise mode makes them, materialised in the reference's shapes
+ *   fm_conditional_path CTMCVectorField.sample_conditional_path, ctmc_vector_field.py:97-143: g_t ~ p(g_t | g_0, g_1) for given molecules g_1 at a
+ *                       per-graph time, with x_0 and the uniforms from the per-molecule counter-based streams instead of torch's generator
  *
  * Conventions
  *   - every function returns 0 on success or a negative fm_status; the message is available from
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 9
+#define FM_ABI_VERSION 10
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -331,6 +333,24 @@ int fm_integrate_mixed(fm_ctx* ctx, void* stream, const fm_state* state, int n_s
                        const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group,
                        const float* temb, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink,
                        int* final_dst);
+
+/* --- ABI 10: the conditional path of a CTMC model (has_mask == 1) for given molecules: noise x1 back to an intermediate time with the model's own corruption
+ * process, CTMCVectorField.sample_conditional_path (ctmc_vector_field.py:97-143, t of shape (B,)), in one launch on the bound batch with the ids of
+ * fm_set_molecule_ids.  Molecule m belongs to time group mol_group[m] (DEVICE (n_mols) int32, values in [0, n_groups); NULL with n_groups == 1: group 0) and
+ * reads row g of alpha: DEVICE (n_groups, 4) float32 = alpha_t of x, a, c, e at the group's time (interpolant_scheduler.py:97-153).
+ *   positions (:112)      out->x_t = (1 - alpha_x) x_0 + alpha_x (x1->x_t - per-molecule mean): x_0 = fm_prior_philox's bits for this seed, the mean with
+ *                         fm_remove_com's arithmetic, the three operations rounded separately like torch's
+ *   tokens (:122-134)     out token = u < 1 - alpha ? mask token : x1 token, per atom (a, c) and per unordered pair (e); u = the row's uniform of the stream
+ *                         entry "conditional path" (csrc/fm_device.h), disjoint from every draw of a sampling run
+ * x1 must hold real categories (the kernel copies its tokens, it does not range-check them) and is only read; out must not alias it (no pointer of out may
+ * equal the matching pointer of x1: FM_ERR_INVALID).  tape (may be NULL, as may any of its members) receives the draws the call consumed -- x0 (N,3), u_a, u_c
+ * (N), u_e (U) -- the role fm_philox_tape plays for steps: the reference's sample_conditional_path fed with them in place of x_0 and torch.rand gives out.
+ * Does not synchronise, allocates nothing and needs no workspace beyond the bind's.  FM_ERR_INVALID also for an endpoint model, n_groups < 1 and
+ * n_groups > 1 with a NULL mol_group.  The state it writes continues through fm_integrate / fm_integrate_mixed with a first step at t > 0 and prev0 == NULL:
+ * no bootstrap runs and the first evaluation is not self-conditioned (vector_field.py:269-289). */
+typedef struct fm_cond_tape { float* x0; float* u_a; float* u_c; float* u_e; } fm_cond_tape;   /* optional outputs, any may be NULL */
+int fm_conditional_path(fm_ctx* ctx, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                        const fm_state* out, const fm_cond_tape* tape);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
