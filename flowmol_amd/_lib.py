@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 10
+FM_ABI_VERSION = 11
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
@@ -100,6 +100,14 @@ class fm_cond_tape(C.Structure):
     _fields_ = [('x0', C.c_void_p), ('u_a', C.c_void_p), ('u_c', C.c_void_p), ('u_e', C.c_void_p)]
 
 
+class fm_loss_rows(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('a', C.c_void_p), ('c', C.c_void_p), ('e', C.c_void_p)]
+
+
+class fm_distort_tape(C.Structure):
+    _fields_ = [('z', C.c_void_p), ('u', C.c_void_p)]
+
+
 class FlowMolHipError(RuntimeError):
     pass
 
@@ -135,6 +143,10 @@ _EXPORTS = {
     # ABI 10: conditional path of given molecules
     'fm_conditional_path': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fm_state), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fm_state),
                                       C.POINTER(fm_cond_tape)]),
+    # ABI 11: denoising loss of given molecules
+    'fm_denoising_loss': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.POINTER(fm_state), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(fm_loss_rows),
+                                    C.c_void_p]),
+    'fm_distort_philox': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_distort_tape)]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

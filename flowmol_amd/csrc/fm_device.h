@@ -984,6 +984,8 @@ __device__ __forceinline__ void fm_row_stats8(const float* row, int n, int sub, 
 //        blocks 4..7 = the row's d Exp(1) draws (uniform simplex; Exp race of marginal / c-given-a), same word order as the CTMC draws
 //   c2 = 0xFFFFFFFE - job, conditional path of CTMC models (fm_k_conditional_path):  block 8 word 0 = the row's uniform u (fm_u01; masked when u < 1 - alpha_t);
 //        its positions' x_0 is the position prior's entry above
+//   c2 = 0xFFFFFFFF, c1 = atom, geometry distortion of the denoising loss (fm_k_distort_philox):  block 1 = the atom's three normals z by the position prior's Box-Muller
+//        (r0 cos t0, r0 sin t0, r1 cos t1); block 2 word 0 = its uniform u (fm_u01; distorted when u < p).  Block 0 stays the position prior's
 // (step * 4 + job reaches 0xFFFFFFFC only after 2^30 steps.)  fm_philox_tape writes a step's draws out through the same functions.
 struct FmPhilox4 { unsigned v[4]; };
 __device__ __forceinline__ FmPhilox4 fm_philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {

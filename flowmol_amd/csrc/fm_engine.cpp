@@ -196,21 +196,26 @@ template <int A, int B, int TM = FM_TM> Inst<MlpPairFn> mlp_pair_inst() { return
 template <int MODE> Inst<Mlp4Fn> mlp4_inst() { return {{MODE}, fm_k_mlp4<MODE>, (size_t)FM_MLP4_LDS_BYTES}; }
 template <int MODE4, int B> Inst<Mlp4PairFn> mlp4_pair_inst() { return {{MODE4, B}, fm_k_mlp4_pair<MODE4, B>, lds_mlp_max(16)}; }
 template <int V, int TM = FM_TM> Inst<ProjFn> proj_inst() { return {{V, TM}, fm_k_node_proj<V, TM>, lds_proj(V, TM)}; }
-template <int TM, bool NARROW, bool HEAD = false> Inst<EdgeUpdFn> eupd_inst() { return {{TM, NARROW, HEAD}, fm_k_edge_update<TM, NARROW, HEAD>, lds_edge_upd(TM)}; }
+template <int TM, bool NARROW, bool HEAD = false, bool LOSS = false> Inst<EdgeUpdFn> eupd_inst() { return {{TM, NARROW, HEAD, LOSS}, fm_k_edge_update<TM, NARROW, HEAD, LOSS>, lds_edge_upd(TM)}; }
 template <int TM, int FMT> Inst<EdgeUpdSpFn> eupd_sp_inst() { return {{TM, FMT}, fm_k_edge_update_sp<TM, FMT>, lds_edge_upd_sp(TM)}; }
 
 const InstList<MlpFn> mlp_instances{"mode, tile_rows", {
     mlp_inst<FM_MLP_TABLE>(), mlp_inst<FM_MLP_SC_NODE>(), mlp_inst<FM_MLP_NODE_HEAD>(), mlp_inst<FM_MLP_EDGE_HEAD>(), mlp_inst<FM_MLP_SC_EDGE>(),
     mlp_inst<FM_MLP_SC_EDGE, 32>(), mlp_inst<FM_MLP_EDGE_HEAD, 32>(),
     mlp_inst<FM_MLP_SC_NODE, 16>(), mlp_inst<FM_MLP_NODE_HEAD, 16>(), mlp_inst<FM_MLP_EDGE_HEAD, 16>(), mlp_inst<FM_MLP_SC_EDGE, 16>(),
-    mlp_inst<FM_MLP_TABLE, 16>()}};       // compiled and opted in, never selected: the token / dense embeddings run 64-row tiles
+    mlp_inst<FM_MLP_TABLE, 16>(),         // compiled and opted in, never selected: the token / dense embeddings run 64-row tiles
+    // the heads with the loss epilogue (fm_denoising_loss): one instance per head instance above
+    mlp_inst<FM_MLP_NODE_LOSS>(), mlp_inst<FM_MLP_EDGE_LOSS>(), mlp_inst<FM_MLP_EDGE_LOSS, 32>(), mlp_inst<FM_MLP_NODE_LOSS, 16>(), mlp_inst<FM_MLP_EDGE_LOSS, 16>()}};
 const InstList<MlpPairFn> mlp_pair_instances{"mode_a, mode_b, tile_rows", {
     mlp_pair_inst<FM_MLP_SC_NODE, FM_MLP_SC_EDGE>(), mlp_pair_inst<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD>(),
-    mlp_pair_inst<FM_MLP_SC_NODE, FM_MLP_SC_EDGE, 16>(), mlp_pair_inst<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, 16>()}};
-const InstList<Mlp4Fn> mlp4_instances{"mode", {mlp4_inst<FM_MLP4_SC_NODE>(), mlp4_inst<FM_MLP4_NODE_HEAD>(), mlp4_inst<FM_MLP4_PROJ0>()}};
-const InstList<Mlp4PairFn> mlp4_pair_instances{"mode_a, mode_b", {mlp4_pair_inst<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>(), mlp4_pair_inst<FM_MLP4_NODE_HEAD, FM_MLP_EDGE_HEAD>()}};
+    mlp_pair_inst<FM_MLP_SC_NODE, FM_MLP_SC_EDGE, 16>(), mlp_pair_inst<FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, 16>(),
+    mlp_pair_inst<FM_MLP_NODE_LOSS, FM_MLP_EDGE_LOSS>(), mlp_pair_inst<FM_MLP_NODE_LOSS, FM_MLP_EDGE_LOSS, 16>()}};
+const InstList<Mlp4Fn> mlp4_instances{"mode", {mlp4_inst<FM_MLP4_SC_NODE>(), mlp4_inst<FM_MLP4_NODE_HEAD>(), mlp4_inst<FM_MLP4_PROJ0>(), mlp4_inst<FM_MLP4_NODE_LOSS>()}};
+const InstList<Mlp4PairFn> mlp4_pair_instances{"mode_a, mode_b", {mlp4_pair_inst<FM_MLP4_SC_NODE, FM_MLP_SC_EDGE>(), mlp4_pair_inst<FM_MLP4_NODE_HEAD, FM_MLP_EDGE_HEAD>(),
+                                                                          mlp4_pair_inst<FM_MLP4_NODE_LOSS, FM_MLP_EDGE_LOSS>()}};
 const InstList<ProjFn> node_proj_instances{"V, tile_rows", {proj_inst<32>(), proj_inst<16>(), proj_inst<32, 16>(), proj_inst<16, 16>()}};
-const InstList<EdgeUpdFn> edge_update_instances{"tile_rows, narrow, head", {eupd_inst<32, false>(), eupd_inst<64, false>(), eupd_inst<32, true>(), eupd_inst<32, false, true>()}};
+const InstList<EdgeUpdFn> edge_update_instances{"tile_rows, narrow, head, loss", {eupd_inst<32, false>(), eupd_inst<64, false>(), eupd_inst<32, true>(), eupd_inst<32, false, true>(),
+                                                                                eupd_inst<32, false, true, true>()}};
 const InstList<EdgeUpdSpFn> edge_update_sp_instances{"tile_rows, half_planes", {eupd_sp_inst<32, 0>(), eupd_sp_inst<32, 1>()}};
 // fused campbell step, keyed like its gat sibling (ctmc_gat_instances, fm_host.h); per-molecule time (`mixed`) is a kernel with an argument struct of its own,
 // hence a list of its own.  No dynamic LDS; the workgroup size is BatchPlan::ctmc_threads
@@ -267,7 +272,7 @@ FmMlp4Args mlp4_args(const FmMlpArgs& a, int N, const MlpW& w, const void* W1q, 
     q.s_tab = a.s_tab; q.tok_a = a.tok_a; q.tok_c = a.tok_c; q.n_c1 = a.n_c1; q.tab_slot = a.tab_slot; q.node_mol = a.node_mol; q.slot_rows = a.slot_rows;
     q.prev_a = a.prev_a; q.prev_c = a.prev_c; q.prev_x = a.prev_x; q.x_t = a.x_t;
     q.na = a.na; q.nc = a.nc; q.rbf_mu_step = a.rbf_mu_step; q.rbf_inv_sigma = a.rbf_inv_sigma;
-    q.in = a.in; q.out = a.out; q.out2 = a.out2;
+    q.in = a.in; q.out = a.out; q.out2 = a.out2; q.tgt_a = a.tgt_a; q.tgt_c = a.tgt_c;
     return q;
 }
 
@@ -385,7 +390,7 @@ void conv_pass(Launch& L, fm_ctx* c, const Taps& tap, int it, int n_pass, const 
 
 // The molecule update after convolution i: positions and EdgeUpdate's node terms (kernels of their own in the unfused sequence, else done by node_update),
 // then EdgeUpdate.  last: the evaluation's last pass, whose EdgeUpdate may run the edge head as its epilogue -- returns whether it did
-bool mol_update(Launch& L, fm_ctx* c, const Taps& tap, int i, bool last, const fm_dst* out) {
+bool mol_update(Launch& L, fm_ctx* c, const Taps& tap, int i, bool last, const fm_dst* out, const fm_state* xt, const fm_state* loss_x1) {
     const BatchPlan& p = c->plan;
     const Workspace& w = c->ws;
     const int V = c->V, TN = p.tm_node, N = w.b.N, E = w.b.E;
@@ -409,7 +414,8 @@ bool mol_update(Launch& L, fm_ctx* c, const Taps& tap, int i, bool last, const f
     } else if (head_done) {
         // the evaluation's last EdgeUpdate: its rows feed the edge head and nothing else -- tiles of 16 pairs, the head as the epilogue, no ef store
         eu.hW1 = c->edge_head.W1; eu.hb1 = c->edge_head.b1; eu.hW2 = c->edge_head.W2; eu.hb2 = c->edge_head.b2; eu.out_e = out->e; eu.ne = c->ne;
-        launch_inst(L, edge_update_instances, {32, false, true}, "edge_update_head", dim3((w.b.U + 15) / 16), blk, lds_edge_upd(32), eu);
+        if (loss_x1) { eu.tok_e = xt->e_t; eu.tgt_e = loss_x1->e_t; }
+        launch_inst(L, edge_update_instances, {32, false, true, loss_x1 ? 1 : 0}, "edge_update_head", dim3((w.b.U + 15) / 16), blk, lds_edge_upd(32), eu);
     } else {
         const int tm = p.tm_eupd;
         launch_inst(L, edge_update_instances, {tm, c->mp.narrow_f, false}, "edge_update", dim3((E + tm - 1) / tm), blk, lds_edge_upd(tm), eu);
@@ -419,17 +425,23 @@ bool mol_update(Launch& L, fm_ctx* c, const Taps& tap, int i, bool last, const f
     return head_done;
 }
 
-// The output heads.  head_done: the edge head ran as the epilogue of the last EdgeUpdate, only the node head is left
-void heads(Launch& L, fm_ctx* c, const FmMlpArgs& base, bool mlp4, bool head_done, const fm_dst* out) {
+// The output heads.  head_done: the edge head ran as the epilogue of the last EdgeUpdate, only the node head is left.  loss_x1 (fm_denoising_loss): the same
+// launches with the heads' loss instances -- out->a / c / e receive one nll per row, from the tokens of xt and the target tokens of loss_x1
+void heads(Launch& L, fm_ctx* c, const FmMlpArgs& base, bool mlp4, bool head_done, const fm_dst* out, const fm_state* xt, const fm_state* loss_x1) {
     FmMlpArgs a = base, e = base;
     a.in = c->ws.s; a.out = out->a; a.out2 = out->c;
     e.ef = c->ws.ef; e.p_e0 = c->ws.b.p_e0; e.p_e1 = c->ws.b.p_e1; e.out = out->e;
-    launch_mlp_stage(L, c->plan, mlp4, FM_MLP4_NODE_HEAD, FM_MLP_NODE_HEAD, FM_MLP_EDGE_HEAD, "heads", "node_head", head_done ? nullptr : "edge_head",
+    if (loss_x1) {
+        a.tok_a = xt->a_t; a.tok_c = xt->c_t; a.tgt_a = loss_x1->a_t; a.tgt_c = loss_x1->c_t;
+        e.tok_e = xt->e_t; e.tgt_e = loss_x1->e_t;
+    }
+    launch_mlp_stage(L, c->plan, mlp4, loss_x1 ? FM_MLP4_NODE_LOSS : FM_MLP4_NODE_HEAD, loss_x1 ? FM_MLP_NODE_LOSS : FM_MLP_NODE_HEAD,
+                     loss_x1 ? FM_MLP_EDGE_LOSS : FM_MLP_EDGE_HEAD, "heads", "node_head", head_done ? nullptr : "edge_head",
                      mlp4_args(a, c->ws.b.N, c->node_head, c->node_head_W1q, c->node_head_W2q), a, c->node_head, e, c->edge_head, c->plan.edge_head32);
 }
 
 int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* prev, int remove_com, const fm_dst* out,
-             bool taps_on, const fm_dense_state* dense = nullptr, const float* temb = nullptr) {
+             bool taps_on, const fm_dense_state* dense = nullptr, const float* temb = nullptr, const fm_state* loss_x1 = nullptr) {
     Launch L{c, st};
     const Taps tap{L, taps_on && !c->taps.empty()};
     const fm_config& cf = c->cfg;
@@ -444,9 +456,9 @@ int evaluate(fm_ctx* c, hipStream_t st, const fm_state* state, const fm_dst* pre
     bool head_done = false;
     for (int it = 0; it < n_pass; ++it) {
         conv_pass(L, c, tap, it, n_pass, dense ? dense->x_t : state->x_t, mlp4, it < n_pq);
-        if (cf.update_after[it % cf.n_convs] >= 0) head_done = mol_update(L, c, tap, it % cf.n_convs, it == n_pass - 1, out);
+        if (cf.update_after[it % cf.n_convs] >= 0) head_done = mol_update(L, c, tap, it % cf.n_convs, it == n_pass - 1, out, state, loss_x1);
     }
-    heads(L, c, base, mlp4, head_done, out);
+    heads(L, c, base, mlp4, head_done, out, state, loss_x1);
     if (remove_com != 2) {       // 2: the caller's fused CTMC kernel centres the raw positions (ws.xw) and writes out->x itself
         L.copy(out->x, c->ws.xw, (size_t)c->ws.b.N * 3 * 4);
         if (remove_com) L("remove_com", fm_k_remove_com, dim3(c->ws.b.B), dim3(64), 0, out->x, (const int*)c->ws.b.mol_node_off);
@@ -474,7 +486,7 @@ int embed_table(fm_ctx* c, hipStream_t st, const float* temb, int n_tables = 1) 
 // table_slot >= 0: the caller (step_driver) has already built this step's table into that slot, and temb is not read (it may be null); else the n_tables
 // tables are built here from temb's rows.  tab_slot (per-molecule time): device (n_mols) slot of every molecule's table, counted from `table_slot`
 int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap,
-                 int remove_com, const fm_dst* out, int table_slot = -1, const int* tab_slot = nullptr, int n_tables = 1) {
+                 int remove_com, const fm_dst* out, int table_slot = -1, const int* tab_slot = nullptr, int n_tables = 1, const fm_state* loss_x1 = nullptr) {
     int rc = 0;
     if (table_slot < 0) { table_slot = 0; rc = embed_table(c, st, temb, n_tables); }
     if (rc) return rc;
@@ -495,7 +507,7 @@ int forward_impl(fm_ctx* c, hipStream_t st, const fm_state* state, const float* 
         prev = &boot;
     }
     if (!sc) prev = nullptr;
-    return evaluate(c, st, state, prev, remove_com, out, true);
+    return evaluate(c, st, state, prev, remove_com, out, true, nullptr, nullptr, loss_x1);
 }
 
 __global__ void fm_k_noop() {}
@@ -1295,6 +1307,59 @@ int fm_forward_mixed(fm_ctx* c, void* stream, const fm_state* state, const float
                      int bootstrap, int remove_com, const fm_dst* out) {
     if (const int rc = mixed_check(c, "fm_forward_mixed", state && temb && mol_group && out, n_groups)) return rc;
     return forward_impl(c, (hipStream_t)stream, state, temb, prev, bootstrap, remove_com ? 1 : 0, out, -1, mol_group, n_groups);
+}
+
+int fm_denoising_loss(fm_ctx* c, void* stream, const fm_state* xt, const fm_state* x1, const float* temb, int n_groups, const int32_t* mol_group,
+                      const fm_loss_rows* rows, float* mol_out) {
+    const char* const fn = "fm_denoising_loss";
+    if (const int rc = bound_check(c, fn, xt && x1 && rows && mol_out)) return rc;
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) are not supported: the loss of the masked (CTMC) parameterisation only", fn);
+    if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
+    if (n_groups > 1 && !mol_group) return fail(c, FM_ERR_INVALID, "%s: mol_group is NULL with n_groups = %d", fn, n_groups);
+    if (!rows->x || !rows->a || !rows->c || !rows->e) return fail(c, FM_ERR_INVALID, "%s: rows->%s is NULL (all four row buffers are required)", fn,
+                                                                  !rows->x ? "x" : !rows->a ? "a" : !rows->c ? "c" : "e");
+    const FmBatch& b = c->ws.b;
+    if (!xt->x_t || !xt->a_t || !xt->c_t || !x1->x_t || !x1->a_t || !x1->c_t || (b.U > 0 && (!xt->e_t || !x1->e_t))) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    // cnt_e is a float: exact up to 2^24 rows per molecule
+    if ((int64_t)c->plan.nmax * (c->plan.nmax - 1) / 2 > (1 << 24))
+        return fail(c, FM_ERR_INVALID, "%s: a molecule of %d atoms has more than 2^24 pair rows: its row count is not exact in float32", fn, c->plan.nmax);
+    const void* const in[] = {xt->x_t, xt->a_t, xt->c_t, xt->e_t, x1->x_t, x1->a_t, x1->c_t, x1->e_t, temb, mol_group};
+    const void* const outp[] = {rows->x, rows->a, rows->c, rows->e, mol_out};
+    static const char* const out_tag[] = {"rows->x", "rows->a", "rows->c", "rows->e", "mol_out"};
+    for (int o = 0; o < 5; ++o) {
+        for (const void* p : in) if (p && p == outp[o]) return fail(c, FM_ERR_INVALID, "%s: %s aliases an input", fn, out_tag[o]);
+        for (int q = 0; q < o; ++q) if (outp[q] == outp[o]) return fail(c, FM_ERR_INVALID, "%s: %s aliases %s", fn, out_tag[o], out_tag[q]);
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    if (temb) {      // one evaluation, the heads in their loss variant: the raw positions stay in the workspace (remove_com = 2: no copy, no COM removal)
+        const fm_dst out{nullptr, rows->a, rows->c, rows->e};
+        if (const int rc = forward_impl(c, st, xt, temb, nullptr, 0, 2, &out, -1, n_groups > 1 ? mol_group : nullptr, n_groups, x1)) return rc;
+    }
+    FmLossReduceArgs a{};
+    a.node_off = b.mol_node_off; a.pair_off = b.mol_pair_off;
+    a.x_pred = temb ? c->ws.xw : nullptr; a.x_tgt = x1->x_t; a.rows_x = rows->x;
+    for (int m = 0; m < 3; ++m) { a.rows[m] = pick3(m, rows->a, rows->c, rows->e); a.tok_t[m] = pick3(m, xt->a_t, xt->c_t, xt->e_t); a.mask[m] = modality(c, m).K; }
+    a.out = mol_out;
+    Launch L{c, st};
+    L("denoise_reduce", fm_k_denoise_reduce, dim3(b.B), dim3(64), 0, a);
+    return L.rc;
+}
+
+int fm_distort_philox(fm_ctx* c, void* stream, uint64_t seed, float p, int n_groups, const int32_t* mol_group, const int32_t* group_on, float* x,
+                      const fm_distort_tape* tape) {
+    const char* const fn = "fm_distort_philox";
+    if (const int rc = bound_check(c, fn, group_on && x)) return rc;
+    if (n_groups < 1) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d, need at least 1", fn, n_groups);
+    if (n_groups > 1 && !mol_group) return fail(c, FM_ERR_INVALID, "%s: mol_group is NULL with n_groups = %d", fn, n_groups);
+    if (!(p >= 0.0f && p <= 1.0f)) return fail(c, FM_ERR_INVALID, "%s: p = %g is not a probability", fn, (double)p);
+    if (tape && (tape->z == x || tape->u == x)) return fail(c, FM_ERR_INVALID, "%s: the tape aliases x", fn);
+    FmDistortArgs a{};
+    a.x = x; a.node_off = c->ws.b.mol_node_off; a.mol_gid = c->ws.mol_gid; a.mol_group = n_groups > 1 ? mol_group : nullptr; a.group_on = group_on;
+    a.p = p; a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
+    if (tape) { a.z = tape->z; a.u = tape->u; }
+    Launch L{c, (hipStream_t)stream};
+    L("distort_philox", fm_k_distort_philox, dim3(c->ws.b.B), dim3(64), 0, a);
+    return L.rc;
 }
 
 int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,

@@ -90,7 +90,29 @@ enum FmMlpMode {
     FM_MLP_NODE_HEAD = 2, // x = s; out = softmax over [0,na) and [na,na+nc) of the logits
     FM_MLP_EDGE_HEAD = 3, // x = ef[e0]+ef[e1] per pair; out = softmax over ne logits
     FM_MLP_SC_EDGE = 4,   // x = [p_e | rbf(d(x1_prev)) - rbf(d(x_t))]; layer-1 adds T1[token]; out = ef_tab[token] + silu(.)
+    FM_MLP_NODE_LOSS = 5, // NODE_HEAD with the loss epilogue (fm_head_row<true>): out / out2 = one nll per node for atom type / charge
+    FM_MLP_EDGE_LOSS = 6, // EDGE_HEAD with the loss epilogue: out = one nll per pair
 };
+constexpr bool fm_mlp_node_head(int mode) { return mode == FM_MLP_NODE_HEAD || mode == FM_MLP_NODE_LOSS; }
+constexpr bool fm_mlp_edge_head(int mode) { return mode == FM_MLP_EDGE_HEAD || mode == FM_MLP_EDGE_LOSS; }
+
+// One row of an output head, the ONE place that turns a row's n logits into what the head writes (the two MLP tiles and the head fused into the last
+// EdgeUpdate all end here).  m is the running fmaxf and the sum runs in column order.
+//   LOSS = false (every sampling instance): out[0..n) = softmax(lg) (vector_field.py:336-344,364-367)
+//   LOSS = true (fm_denoising_loss): out[0] = -log_softmax(lg)[target] = (logf(sum_c expf(l_c - m)) + m) - l_target as torch's CrossEntropyLoss on logits
+//          evaluates it (flowmol.py:408 with vector_field.py:217 apply_softmax=False); target < 0 = a row the reference's ignore_index rule drops: +0.0f
+// fm_loss_target applies that rule (flowmol.py:378-384): a row counts only while its token in x_t is the mask token.
+__device__ __forceinline__ int fm_loss_target(const int* tok_t, const int* tok_1, int row, int mask) { return tok_t[row] == mask ? tok_1[row] : -1; }
+template <bool LOSS>
+__device__ __forceinline__ void fm_head_row(const float* lg, int n, float* out, int target) {
+    if (LOSS && target < 0) { out[0] = 0.f; return; }
+    float m = lg[0];
+    for (int c = 1; c < n; ++c) m = fmaxf(m, lg[c]);
+    float s = 0.f;
+    for (int c = 0; c < n; ++c) s += expf(lg[c] - m);
+    if (LOSS) out[0] = (logf(s) + m) - lg[target];
+    else for (int c = 0; c < n; ++c) out[c] = expf(lg[c] - m) / s;
+}
 
 struct FmMlpArgs {
     int rows;                 // number of valid rows
@@ -131,6 +153,8 @@ struct FmMlpArgs {
     // SC_NODE, per-molecule time (fm_forward_mixed / fm_integrate_mixed): node n reads table slot tab_slot[node_mol[n]], slot_rows table rows apart
     // (s_tab = slot 0).  null = one table for the whole batch
     const int* tab_slot; const int* node_mol; int slot_rows;
+    // loss modes: tok_a / tok_c / tok_e are the tokens of x_t, these the target tokens of x_1 (fm_loss_target).  Last, so that no other field moves
+    const int* tgt_a; const int* tgt_c; const int* tgt_e;
 };
 
 // TM = rows per tile: 64 (throughput: every weight fragment serves four row tiles) or 16 (small batches: a tile's two dependent GEMMs are
@@ -200,7 +224,7 @@ __device__ __forceinline__ void fm_mlp2_tile(const FmMlpArgs& a, int tile, float
             }
             X[r * a.ldx + 256 + c] = v;
         }
-    } else if (MODE == FM_MLP_NODE_HEAD) {
+    } else if (fm_mlp_node_head(MODE)) {
         const int left = a.rows - row0;
         const auto rs = fm_buf(a.in + (size_t)row0 * 256, (unsigned)(left < TM ? left : TM) * 1024u);
         constexpr int NQ = TM * 64 / FM_THREADS;
@@ -212,7 +236,7 @@ __device__ __forceinline__ void fm_mlp2_tile(const FmMlpArgs& a, int tile, float
             const int idx = tid + k * FM_THREADS, r = idx >> 6, c4 = idx & 63;
             *reinterpret_cast<float4*>(X + r * a.ldx + c4 * 4) = q[k];
         }
-    } else if (MODE == FM_MLP_EDGE_HEAD) {
+    } else if (fm_mlp_edge_head(MODE)) {
         int* pr = meta + 3 * TM;                              // [64] second edge of the pair
         if (tid < TM) {
             const int p = row0 + tid;
@@ -286,7 +310,7 @@ __device__ __forceinline__ void fm_mlp2_tile(const FmMlpArgs& a, int tile, float
         X[row * a.ldx + col] = v;
     };
     // the heads have 1-2 output column tiles: single-tile jobs keep 4-8 waves busy instead of 1-2
-    if (MODE == FM_MLP_NODE_HEAD || MODE == FM_MLP_EDGE_HEAD) fm_block_gemm<1, 1>(Hb, a.ldh, TM / 16, a.H / 8, a.W2, a.O / 16, epi2);
+    if (fm_mlp_node_head(MODE) || fm_mlp_edge_head(MODE)) fm_block_gemm<1, 1>(Hb, a.ldh, TM / 16, a.H / 8, a.W2, a.O / 16, epi2);
     else fm_block_gemm<TM / 16, 1>(Hb, a.ldh, TM / 16, a.H / 8, a.W2, a.O / 16, epi2);
     __syncthreads();
 
@@ -365,22 +389,15 @@ __device__ __forceinline__ void fm_mlp2_tile(const FmMlpArgs& a, int tile, float
         if (sub == 0 && grow < a.rows) {
             const float* lg = X + r * a.ldx;
             if (MODE == FM_MLP_NODE_HEAD) {
-                float m = lg[0];
-                for (int c = 1; c < a.na; ++c) m = fmaxf(m, lg[c]);
-                float s = 0.f;
-                for (int c = 0; c < a.na; ++c) s += expf(lg[c] - m);
-                for (int c = 0; c < a.na; ++c) a.out[(size_t)grow * a.na + c] = expf(lg[c] - m) / s;
-                m = lg[a.na];
-                for (int c = 1; c < a.nc; ++c) m = fmaxf(m, lg[a.na + c]);
-                s = 0.f;
-                for (int c = 0; c < a.nc; ++c) s += expf(lg[a.na + c] - m);
-                for (int c = 0; c < a.nc; ++c) a.out2[(size_t)grow * a.nc + c] = expf(lg[a.na + c] - m) / s;
+                fm_head_row<false>(lg, a.na, a.out + (size_t)grow * a.na, 0);
+                fm_head_row<false>(lg + a.na, a.nc, a.out2 + (size_t)grow * a.nc, 0);
+            } else if (MODE == FM_MLP_EDGE_HEAD) {
+                fm_head_row<false>(lg, a.ne, a.out + (size_t)grow * a.ne, 0);
+            } else if (MODE == FM_MLP_NODE_LOSS) {
+                fm_head_row<true>(lg, a.na, a.out + grow, fm_loss_target(a.tok_a, a.tgt_a, grow, a.na));
+                fm_head_row<true>(lg + a.na, a.nc, a.out2 + grow, fm_loss_target(a.tok_c, a.tgt_c, grow, a.nc));
             } else {
-                float m = lg[0];
-                for (int c = 1; c < a.ne; ++c) m = fmaxf(m, lg[c]);
-                float s = 0.f;
-                for (int c = 0; c < a.ne; ++c) s += expf(lg[c] - m);
-                for (int c = 0; c < a.ne; ++c) a.out[(size_t)grow * a.ne + c] = expf(lg[c] - m) / s;
+                fm_head_row<true>(lg, a.ne, a.out + grow, fm_loss_target(a.tok_e, a.tgt_e, grow, a.ne));
             }
         }
     }
@@ -418,7 +435,7 @@ __global__ void __launch_bounds__(FM_THREADS) fm_k_mlp2_pair(FmMlpArgs a, FmMlpA
 // (round 6: fm_rows4_linear runs the regular tiles' fma chains, one column group of 64 per wave; rounds 4-5 split K over the eight waves -- another order):
 // bit-identical to the 16- / 64-row MLP tiles, so the choice follows the batch size in canonical mode too.
 // ------------------------------------------------------------------------------------------------
-enum FmMlp4Mode { FM_MLP4_SC_NODE = 0, FM_MLP4_NODE_HEAD = 1, FM_MLP4_PROJ0 = 2 };
+enum FmMlp4Mode { FM_MLP4_SC_NODE = 0, FM_MLP4_NODE_HEAD = 1, FM_MLP4_PROJ0 = 2, FM_MLP4_NODE_LOSS = 3 };      // NODE_LOSS: NODE_HEAD with the loss epilogue (fm_head_row<true>)
 struct FmMlp4Args {
     int N;
     const void* W1q; const float* b1;          // quad-row packed (fm_wave_gemm4): SC_NODE K = 320 ([s_tab (256) | p_a | p_c | rbf | 0]), NODE_HEAD K = 256; N = 256
@@ -432,6 +449,8 @@ struct FmMlp4Args {
     const float* in;                           // NODE_HEAD / PROJ0: s (N,256)
     // PROJ0: the first convolution's Ps = s * Ws_src; v = 0 (vector_field.py:246), so PV = 0 as well; working copy of the positions
     const void* Wps4; float* Ps; float* PV; int pv_w; float* v_init; int V; const float* x_src; float* x_dst;
+    // NODE_LOSS: tok_a / tok_c are the tokens of x_t, these the target tokens of x_1 (fm_loss_target); out / out2 = one nll per node.  Last: no other field moves
+    const int* tgt_a; const int* tgt_c;
 };
 #define FM_MLP4_LDX 324          // >= 320 columns, 16-byte rows
 #define FM_MLP4_LDH 260
@@ -499,16 +518,13 @@ __device__ __forceinline__ void fm_mlp4_tile(const FmMlp4Args& a, int tile, floa
         if (tid < rows) {        // softmax heads (vector_field.py:336-339,364-367): one lane per row, the arithmetic of fm_mlp2_tile
             const float* lg = X + tid * LDX;
             const int n = row0 + tid;
-            float m = lg[0];
-            for (int c = 1; c < a.na; ++c) m = fmaxf(m, lg[c]);
-            float sum = 0.f;
-            for (int c = 0; c < a.na; ++c) sum += expf(lg[c] - m);
-            for (int c = 0; c < a.na; ++c) a.out[(size_t)n * a.na + c] = expf(lg[c] - m) / sum;
-            m = lg[a.na];
-            for (int c = 1; c < a.nc; ++c) m = fmaxf(m, lg[a.na + c]);
-            sum = 0.f;
-            for (int c = 0; c < a.nc; ++c) sum += expf(lg[a.na + c] - m);
-            for (int c = 0; c < a.nc; ++c) a.out2[(size_t)n * a.nc + c] = expf(lg[a.na + c] - m) / sum;
+            if (MODE == FM_MLP4_NODE_LOSS) {
+                fm_head_row<true>(lg, a.na, a.out + n, fm_loss_target(a.tok_a, a.tgt_a, n, a.na));
+                fm_head_row<true>(lg + a.na, a.nc, a.out2 + n, fm_loss_target(a.tok_c, a.tgt_c, n, a.nc));
+            } else {
+                fm_head_row<false>(lg, a.na, a.out + (size_t)n * a.na, 0);
+                fm_head_row<false>(lg + a.na, a.nc, a.out2 + (size_t)n * a.nc, 0);
+            }
         }
     }
 }
@@ -1272,14 +1288,18 @@ struct FmEdgeUpdArgs {
     const float2* hW1; const float* hb1;    // K = 128, N = 128
     const float2* hW2; const float* hb2;    // K = 128, N = 16 (ne real columns)
     float* out_e; int ne;                   // (U, ne) bond-order probabilities
+    // LOSS instances (fm_denoising_loss): out_e = (U) one nll per pair (fm_head_row<true>), from the pair's token in x_t and its target token (fm_loss_target).
+    // Last: no other field moves
+    const int* tok_e; const int* tgt_e;
 };
 
 // HEAD = false: a tile is TM consecutive directed edges (internal order).  HEAD = true (TM = 32): a tile is 16 consecutive unordered pairs, rows 2k / 2k + 1 =
 // the pair's two directed edges (src < dst first, the reference's upper edge): same per-row arithmetic, rows gathered instead of streamed, and the epilogue
 // is the edge head of those 16 pairs instead of the store of the rows.
-template <int TM, bool NARROW, bool HEAD = false>
+template <int TM, bool NARROW, bool HEAD = false, bool LOSS = false>
 __global__ void __launch_bounds__(FM_THREADS) fm_k_edge_update(FmEdgeUpdArgs a) {
     static_assert(!HEAD || (TM == 32 && !NARROW), "the fused edge head exists for 32-row tiles of full-width models");
+    static_assert(!LOSS || HEAD, "the loss epilogue is the fused edge head's");
     HIP_DYNAMIC_SHARED(float, lds)
     constexpr int LDX = 164, LDH = 132, MT = TM / 16, LPR = FM_THREADS / TM;
     float* X = lds;                       // [TM][164]: ef(128) | rbf(32)
@@ -1447,11 +1467,8 @@ __global__ void __launch_bounds__(FM_THREADS) fm_k_edge_update(FmEdgeUpdArgs a) 
                     for (int w = 1; w < 8; ++w) v += part[(w * 16 + tid) * 16 + c];
                     lg[c] = v + a.hb2[c];
                 }
-                float m = lg[0];
-                for (int c = 1; c < a.ne; ++c) m = fmaxf(m, lg[c]);
-                float sum = 0.f;
-                for (int c = 0; c < a.ne; ++c) sum += expf(lg[c] - m);
-                for (int c = 0; c < a.ne; ++c) a.out_e[(size_t)p * a.ne + c] = expf(lg[c] - m) / sum;
+                if constexpr (LOSS) fm_head_row<true>(lg, a.ne, a.out_e + p, fm_loss_target(a.tok_e, a.tgt_e, p, a.ne));
+                else fm_head_row<false>(lg, a.ne, a.out_e + (size_t)p * a.ne, 0);
             }
         }
     }
@@ -2142,6 +2159,101 @@ static __global__ void __launch_bounds__(256) fm_k_conditional_path(FmCondArgs a
         const float u = fm_u01(rn.v[0]);
         if (md.u) md.u[i] = u;
         md.out[i] = u < thr ? md.K : md.tok1[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Geometry distortion of FlowMol.forward (fm_distort_philox; reference flowmol/models/flowmol.py:333-337): for every atom of a molecule whose time group is
+// switched on (group_on[mol_group[m]] != 0: the caller's t > distort_t),  x += (z * [u < p]) * 0.5  with three normals z and one uniform u per atom from the
+// molecule's stream: counter (global molecule id, atom, 0xFFFFFFFF, block), block 1 = z by the position prior's Box-Muller (r0 cos t0, r0 sin t0, r1 cos t1),
+// block 2 word 0 = u (fm_u01).  Block 0 of that c2 is the position prior's.  The three operations are rounded separately, as torch rounds them.  One wave per
+// molecule.  Optional tape: z (N,3) and u (N) of EVERY atom, switched on or not (the draws are a function of seed, molecule id and atom alone).
+// ------------------------------------------------------------------------------------------------
+struct FmDistortArgs {
+    float* x; const int* node_off; const int* mol_gid; const int* mol_group; const int* group_on;
+    float p; unsigned seed_lo, seed_hi; float* z; float* u;
+};
+static __global__ void __launch_bounds__(64) fm_k_distort_philox(FmDistortArgs a) {
+    const int mol = blockIdx.x, lane = threadIdx.x;
+    const bool on = a.group_on[a.mol_group ? a.mol_group[mol] : 0] != 0;
+    if (!on && !a.z && !a.u) return;
+    const unsigned gid = (unsigned)a.mol_gid[mol];
+    const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
+    for (int n = n0 + lane; n < n1; n += 64) {
+        const FmPhilox4 rz = fm_philox4x32(gid, (unsigned)(n - n0), 0xFFFFFFFFu, 1u, a.seed_lo, a.seed_hi);
+        const FmPhilox4 ru = fm_philox4x32(gid, (unsigned)(n - n0), 0xFFFFFFFFu, 2u, a.seed_lo, a.seed_hi);
+        const float r0 = sqrtf(2.0f * fm_exp1(rz.v[0])), r1 = sqrtf(2.0f * fm_exp1(rz.v[2]));
+        const float t0 = 6.283185307179586f * fm_u01(rz.v[1]), t1 = 6.283185307179586f * fm_u01(rz.v[3]);
+        const float z[3] = {r0 * cosf(t0), r0 * sinf(t0), r1 * cosf(t1)};
+        const float u = fm_u01(ru.v[0]);
+        if (a.z) { a.z[n * 3] = z[0]; a.z[n * 3 + 1] = z[1]; a.z[n * 3 + 2] = z[2]; }
+        if (a.u) a.u[n] = u;
+        if (on) {
+            const float mk = u < a.p ? 1.0f : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) a.x[n * 3 + k] = fm_add_rn(a.x[n * 3 + k], fm_mul_rn(fm_mul_rn(z[k], mk), 0.5f));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-molecule sums of the denoising-loss row terms (fm_denoising_loss; reference flowmol/models/flowmol.py:388-413 reduces them over the batch): molecule m ->
+// out[m] = {se_x, 3 n_atoms, nll_a, cnt_a, nll_c, cnt_c, nll_e, cnt_e}.  One wave per molecule, so no work is split by batch position.
+//   SUMMATION ORDER (canonical: a function of the molecule alone).  A molecule's rows of one term -- atoms, or unordered pairs in upper-triangle order -- are
+//   cut into 16-row chunks counted from the molecule's FIRST row (the last chunk may be short).  A chunk's sum starts at +0 and adds its rows in row order;
+//   the molecule's sum starts at +0 and adds the chunk sums in chunk order.  (The edge-message aggregation rule: 16-row chunks, chunks in order.)
+//   Lane l of pass q owns chunk 64 q + l; the chunk sums are then added in lane order through __shfl, by every lane alike.
+//   cnt_* = rows whose token in x_t is the mask token (the rows fm_loss_target keeps), counted in integers.
+//   x_pred != null: the position term of atom n, se = ((dx dx) + dy dy) + dz dz with d = x_pred - x_tgt in separately rounded operations (MSELoss, not
+//   COM-removed: vector_field.py:217 remove_com=False), is computed here and written to rows_x first; null: rows_x holds the caller's terms.
+// ------------------------------------------------------------------------------------------------
+struct FmLossReduceArgs {
+    const int* node_off; const int* pair_off;
+    const float* x_pred; const float* x_tgt; float* rows_x;
+    const float* rows[3]; const int* tok_t[3]; int mask[3];      // a, c, e
+    float* out;
+};
+__device__ __forceinline__ float fm_chunk_sum(const float* t, int r0, int r1, int lane) {
+    float total = 0.f;
+    const int nch = (r1 - r0 + 15) >> 4;
+    for (int c0 = 0; c0 < nch; c0 += 64) {
+        float cs = 0.f;
+        if (c0 + lane < nch) {
+            const int b = r0 + (c0 + lane) * 16, e = b + 16 < r1 ? b + 16 : r1;
+            for (int i = b; i < e; ++i) cs += t[i];
+        }
+        const int live = nch - c0 < 64 ? nch - c0 : 64;
+        for (int j = 0; j < live; ++j) total += __shfl(cs, j);
+    }
+    return total;
+}
+static __global__ void __launch_bounds__(64) fm_k_denoise_reduce(FmLossReduceArgs a) {
+    const int mol = blockIdx.x, lane = threadIdx.x;
+    const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
+    if (a.x_pred) {
+        for (int n = n0 + lane; n < n1; n += 64) {
+            const float dx = fm_sub_rn(a.x_pred[n * 3], a.x_tgt[n * 3]), dy = fm_sub_rn(a.x_pred[n * 3 + 1], a.x_tgt[n * 3 + 1]);
+            const float dz = fm_sub_rn(a.x_pred[n * 3 + 2], a.x_tgt[n * 3 + 2]);
+            a.rows_x[n] = fm_add_rn(fm_add_rn(fm_mul_rn(dx, dx), fm_mul_rn(dy, dy)), fm_mul_rn(dz, dz));
+        }
+        __syncthreads();      // the wave's own stores, read back below
+    }
+    float r[8];
+    r[0] = fm_chunk_sum(a.rows_x, n0, n1, lane);
+    r[1] = (float)(3 * (n1 - n0));
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int r0 = m == 2 ? a.pair_off[mol] : n0, r1 = m == 2 ? a.pair_off[mol + 1] : n1;
+        r[2 + 2 * m] = fm_chunk_sum(a.rows[m], r0, r1, lane);
+        int cnt = 0;
+        for (int i = r0 + lane; i < r1; i += 64) cnt += a.tok_t[m][i] == a.mask[m] ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+        r[3 + 2 * m] = (float)cnt;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a.out[mol * 8 + k] = r[k];
     }
 }
 

@@ -554,6 +554,72 @@ class Engine:
         self._keep = [x1_state, al, group, out, tp]
         return (out, tp) if tape else out
 
+    def _time_groups(self, t):
+        """``t`` (a number, or one value per bound molecule) as (distinct float32 values, device (B,) int32 group of every molecule or None for one group)."""
+        if torch.is_tensor(t) and t.dim() > 0:
+            tv = t.detach().to('cpu', torch.float32).reshape(-1)
+            if tv.shape[0] != self.B:
+                raise ValueError(f't has {tv.shape[0]} entries, the bound batch {self.B} molecules')
+            vals, group = torch.unique(tv, return_inverse=True)
+            return vals, group.to(torch.int32).to(self.device)
+        return torch.tensor([_f32(t)], dtype=torch.float32), None
+
+    def denoising_loss(self, xt_state, x1_state, t, rows=None):
+        """The denoising-loss terms of the bound batch (fm_denoising_loss; the reference's FlowMol.forward after its sample_conditional_path call,
+        flowmol.py:339-413): one evaluation on ``xt_state`` at ``t`` -- a number or a (B,) tensor with at most 32 distinct values -- with the heads' loss
+        epilogue (CrossEntropyLoss on logits, vector_field.py:217), then one reduction.  ``x1_state`` holds the targets: real-category tokens and the
+        centred positions.  Returns {'mol': (B,8) = se_x, 3 n_atoms, nll_a, cnt_a, nll_c, cnt_c, nll_e, cnt_e per molecule, 'rows': {'x', 'a', 'c' (N),
+        'e' (U)}}: squared errors and nll per row, +0.0 on the rows the reference ignores (token of x_t not the mask token).  It never bootstraps.
+        ``rows`` (testing the reduction alone): the caller's row terms, four float32 tensors; no evaluation runs, ``t`` is not read and the tokens of
+        ``xt_state`` only say which rows count."""
+        d = self.device
+        if rows is None:
+            vals, group = self._time_groups(t)
+            temb = torch.stack([time_embedding_host(float(v), self.cfg.time_embedding_dim) for v in vals]).to(d).contiguous()
+            rows = {'x': torch.empty(self.N, device=d), 'a': torch.empty(self.N, device=d), 'c': torch.empty(self.N, device=d), 'e': torch.empty(self.U, device=d)}
+        else:
+            vals, group, temb = [0.0], None, None
+            rows = {k: rows[k].detach().to(d, torch.float32).contiguous() for k in 'xace'}
+            if [int(rows[k].numel()) for k in 'xace'] != [self.N, self.N, self.N, self.U]:
+                raise ValueError('rows must hold N, N, N and U terms')
+        mol = torch.empty(self.B, 8, device=d)
+        rs = _lib.fm_loss_rows()
+        no_pairs = torch.empty(1, device=d) if self.U == 0 else None      # a batch of single atoms: a valid address that is never dereferenced
+        rs.x, rs.a, rs.c, rs.e = _ptr(rows['x']), _ptr(rows['a']), _ptr(rows['c']), _ptr(rows['e'] if no_pairs is None else no_pairs)
+        st, s1 = self._state_struct(xt_state), self._state_struct(x1_state)
+        with self._dev():
+            rc = self.lib.fm_denoising_loss(self._ctx, self._stream(), C.byref(st), C.byref(s1), _ptr(temb), len(vals), _ptr(group), C.byref(rs), _ptr(mol))
+        self._check(rc, 'fm_denoising_loss')
+        self._keep = [xt_state, x1_state, temb, group, rows, mol, no_pairs]
+        return {'mol': mol, 'rows': rows}
+
+    def distort(self, x: torch.Tensor, p: float, on, seed: int = None, tape: bool = False):
+        """The geometry distortion of the reference's FlowMol.forward (flowmol.py:333-337; fm_distort_philox) in place on ``x`` (N,3): every atom of a
+        molecule with ``on`` set -- a bool, or one per bound molecule: the caller's t > distort_t -- gets x += (z * [u < p]) * 0.5 with z, u from the
+        per-molecule Philox streams of ``seed``.  Returns x; with ``tape`` also {'z' (N,3), 'u' (N)}: the draws of every atom, switched on or not."""
+        if seed is None:
+            raise ValueError('distort draws from the Philox streams: seed is required')
+        d = self.device
+        assert x.is_contiguous() and x.dtype == torch.float32 and tuple(x.shape) == (self.N, 3) and x.device == d
+        flags = torch.as_tensor(on).detach().to('cpu').reshape(-1).to(torch.int32)
+        if flags.shape[0] == 1:
+            group, flags = None, flags.to(d)
+        elif flags.shape[0] == self.B:
+            group, flags = flags.to(d), torch.tensor([0, 1], dtype=torch.int32, device=d)      # two groups: off, on
+        else:
+            raise ValueError(f'on must be one flag or one per bound molecule ({self.B})')
+        tp = ts = None
+        if tape:
+            tp = {'z': torch.empty(self.N, 3, device=d), 'u': torch.empty(self.N, device=d)}
+            ts = _lib.fm_distort_tape()
+            ts.z, ts.u = _ptr(tp['z']), _ptr(tp['u'])
+        with self._dev():
+            rc = self.lib.fm_distort_philox(self._ctx, self._stream(), C.c_uint64(seed), C.c_float(p), int(flags.shape[0]), _ptr(group), _ptr(flags), _ptr(x),
+                                            C.byref(ts) if ts is not None else None)
+        self._check(rc, 'fm_distort_philox')
+        self._keep = [x, group, flags, tp]
+        return (x, tp) if tape else x
+
     def stability(self, state, table: torch.Tensor, fake_atom_token: int = -1, explicit_aromaticity: bool = False) -> torch.Tensor:
         """Valence stability + connectivity of the bound batch's molecules from their tokens, on the device
         (see fm_stability).  table: (n_types, n_charges) int32 bit masks.  Returns (B,4) int32:

@@ -6,7 +6,8 @@
     model = flowmol.load_pretrained('flowmol3').cuda().eval()
     mols = model.sample_random_sizes(n_molecules=10, n_timesteps=250)
 
-Training, losses, optimizers and the chemistry metrics are out of scope.
+``denoising_loss`` is the reference's ``forward`` (297-415, what ``validation_step`` logs).  Training, optimizers and the chemistry metrics are
+out of scope.
 """
 from __future__ import annotations
 
@@ -133,6 +134,7 @@ class FlowMol:
         self.device = torch.device('cpu')
         self._engine: Optional[Engine] = None
         self.last_timing: Dict[str, object] = {}
+        self.loss_hparams: Dict[str, object] = {}      # the checkpoint's loss settings (load_from_checkpoint); presets have none: denoising_loss defaults to off
         self.build_n_atoms_dist(n_atoms_hist or cfg.n_atoms_hist)
 
     # ------------------------------------------------------------------ construction
@@ -147,7 +149,11 @@ class FlowMol:
     def load_from_checkpoint(cls, ckpt_path, **kw) -> "FlowMol":
         hp, sd = read_checkpoint(ckpt_path)
         check_reference_hparams(hp)
-        return cls(from_reference_hparams(hp), sd, **kw)
+        model = cls(from_reference_hparams(hp), sd, **kw)
+        # what FlowMol.forward reads besides the network (flowmol.py:29-55, the reference's defaults for missing keys): the defaults of denoising_loss
+        defaults = {'time_scaled_loss': True, 'weight_ae': False, 'target_blur': 0.0, 'distort_p': 0.0, 'distort_t': 0.5, 'total_loss_weights': None}
+        model.loss_hparams = {k: hp.get(k, v) for k, v in defaults.items()}
+        return model
 
     # nn.Module-ish conveniences of the documented usage (readme.md:44-49)
     def to(self, device) -> "FlowMol":
@@ -414,6 +420,105 @@ class FlowMol:
         if len(parts) > 1:
             final = {f: torch.cat([results[i][f] for i in range(B)]).contiguous() for f in ('x_t', 'a_t', 'c_t', 'e_t')}
         return self._finish(final, n_atoms, frames if not return_tensors else None, return_tensors, False, xt_traj, ep_traj, t_integrate)
+
+    def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
+        """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --
+        corrupt every molecule to its time ``t``, evaluate the network once, and compare its logits and positions with the molecule.  The standard check
+        of a ported checkpoint: compare ``losses`` on a few hundred dataset molecules with what training logged.
+
+        ``molecules``: as in ``resample``.  ``t`` is required: a float, or one value in [0, 1) per molecule -- ``torch.rand(B)`` is the reference's
+        protocol (:328).  Noise is Philox only: ``seed`` is required, ``mol_ids`` (default 0..B-1) name the streams.  ``distort``: ``(distort_p, distort_t)``
+        of the geometry distortion (:333-337), ``False`` for none; ``time_scaled``: the reference's ``time_scaled_loss``.  Both default to the checkpoint's
+        hparams (``self.loss_hparams``; presets: off).  Per call: centre, ``Engine.conditional_path``, optional ``Engine.distort``,
+        ``Engine.denoising_loss``; more than 32 distinct ``t`` are served by sorting on ``t`` and binding several batches, which canonical arithmetic makes
+        invisible: molecule *i* of any call is, bit for bit, ``denoising_loss([mol_i], t[i], seed=s, mol_ids=[id_i])``.
+
+        Returns ``per_molecule`` (B,8) = {se_x, 3 n_atoms, nll_a, cnt_a, nll_c, cnt_c, nll_e, cnt_e} and ``rows`` {'x', 'a', 'c' (N), 'e' (U)} (CPU), and
+        ``losses`` {'x', 'a', 'c', 'e'}: the reference's four batch values, formed from the table on the host as its code forms them (:388-413).
+        Unscaled: x = mean over the 3N elements; a categorical value = sum nll / sum cnt (NaN when nothing is masked, as in torch).  Time-scaled: weights
+        ``clamp(alpha / (1 - alpha), 0.05, 1.5)`` per molecule and feature (interpolant_scheduler.py:87-95); x = mean of weight * squared error; a
+        categorical value is what the reference's code EVALUATES, not what it presumably meant: ``loss (rows,) * weight (rows, 1)`` broadcasts to a
+        (rows, rows) outer product, so the value is mean(loss over all rows, ignored rows as 0) * mean(weight over rows).  ``total`` (:259-267) is returned
+        when ``total_loss_weights`` is given (argument or hparams; missing features weigh 1).  One deliberate difference: the evaluation never takes the
+        reference's eval-mode bootstrap pass for a batch that is entirely at t = 0, which depends on the batch.  NotImplementedError for ``weight_ae``,
+        ``target_blur != 0`` and endpoint models; ValueError, before anything is enqueued, for ``t`` outside [0, 1), a mask token and a missing seed."""
+        cfg, hp = self.cfg, getattr(self, 'loss_hparams', None) or {}
+        if cfg.parameterization == 'endpoint':
+            raise NotImplementedError('denoising_loss: endpoint models are not supported (the loss of the masked CTMC parameterisation only)')
+        if hp.get('weight_ae', False):
+            raise NotImplementedError('denoising_loss: weight_ae=True (class-weighted cross-entropy) is not implemented')
+        if float(hp.get('target_blur', 0.0)) != 0.0:
+            raise NotImplementedError(f"denoising_loss: target_blur={hp['target_blur']} != 0 (soft targets) is not implemented")
+        if seed is None:
+            raise ValueError('denoising_loss draws from the per-molecule Philox streams: seed is required')
+        x1, n_atoms = self._given_molecules(molecules)
+        B = int(n_atoms.numel())
+        tv = torch.as_tensor(t).detach().to('cpu', torch.float32).reshape(-1)
+        tv = tv.expand(B).clone() if tv.numel() == 1 else tv
+        if tv.numel() != B:
+            raise ValueError(f't must be a float or give one value per molecule ({B})')
+        if not bool(((tv >= 0) & (tv < 1)).all()):
+            raise ValueError('denoising_loss: t must lie in [0, 1)')
+        ids = list(range(B)) if mol_ids is None else [int(v) for v in torch.as_tensor(mol_ids).reshape(-1).tolist()]
+        if len(ids) != B:
+            raise ValueError(f'mol_ids has {len(ids)} entries for {B} molecules')
+        if distort is None:
+            distort = (float(hp.get('distort_p', 0.0)), float(hp.get('distort_t', 0.5)))
+        distort = None if not distort or float(distort[0]) <= 0.0 else (float(distort[0]), float(distort[1]))
+        time_scaled = bool(hp.get('time_scaled_loss', False)) if time_scaled is None else bool(time_scaled)
+        total_loss_weights = hp.get('total_loss_weights') if total_loss_weights is None else total_loss_weights
+        # ---- batches of at most FM_TAB_SLOTS distinct times, molecules sorted on t
+        vals = torch.unique(tv).tolist()
+        eng, sizes = self.engine, n_atoms.tolist()
+        given = _split_molecules(x1, sizes)
+        table, rows = [None] * B, [None] * B
+        for lo in range(0, len(vals), _lib.FM_TAB_SLOTS):
+            chunk = set(vals[lo:lo + _lib.FM_TAB_SLOTS])
+            part = [i for i in sorted(range(B), key=lambda i: float(tv[i])) if float(tv[i]) in chunk]
+            st1 = {f: torch.cat([given[i][f] for i in part]) for f in ('x_t', 'a_t', 'c_t', 'e_t')}
+            eng.bind(n_atoms[part])
+            eng.set_molecule_ids(torch.tensor([ids[i] for i in part]))
+            raw = eng.make_state(st1['x_t'], st1['a_t'], st1['c_t'], st1['e_t'])
+            target = dict(raw, x_t=eng.remove_com(raw['x_t'].clone()))      # x_1 - mean with the arithmetic the conditional path centres with
+            tp = tv[part]
+            tvals, group = torch.unique(tp, return_inverse=True)
+            alphas = alpha_tables(tvals.clone(), cfg.schedule_type, cfg.cosine_params)[0]
+            state = eng.conditional_path(raw, alphas, group if tvals.numel() > 1 else None, seed=int(seed))
+            if distort is not None:
+                eng.distort(state['x_t'], distort[0], tp > distort[1], seed=int(seed))
+            res = eng.denoising_loss(state, target, tp)
+            eng.synchronize()
+            mol = res['mol'].cpu()
+            per = _split_molecules({f'{k}_t': res['rows'][k].cpu() for k in 'ace'}, [sizes[i] for i in part])
+            xs = torch.split(res['rows']['x'].cpu(), [sizes[i] for i in part])
+            for j, i in enumerate(part):
+                table[i] = mol[j]
+                rows[i] = {'x': xs[j], 'a': per[j]['a_t'], 'c': per[j]['c_t'], 'e': per[j]['e_t']}
+        table = torch.stack(table)
+        out = {'per_molecule': table, 'rows': {k: torch.cat([r[k] for r in rows]) for k in 'xace'},
+               'losses': self.batch_losses(table, tv, n_atoms, time_scaled)}
+        if total_loss_weights is not None:
+            out['total'] = sum(float(total_loss_weights.get(f, 1.0)) * out['losses'][f] for f in 'xace')
+        return out
+
+    def batch_losses(self, table: torch.Tensor, t: torch.Tensor, n_atoms: torch.Tensor, time_scaled: bool) -> Dict[str, torch.Tensor]:
+        """The reference's four batch values (flowmol.py:388-413) from the per-molecule table of ``denoising_loss``, in float32 on the host; see there."""
+        table, losses = table.to('cpu', torch.float32), {}
+        n = n_atoms.to(torch.float32)
+        n_rows = {'x': n, 'a': n, 'c': n, 'e': n * (n - 1) / 2}
+        if time_scaled:
+            alpha = alpha_tables(t.detach().to('cpu', torch.float32).clone(), self.cfg.schedule_type, self.cfg.cosine_params)[0]
+            w = torch.clamp(alpha / (1 - alpha), min=0.05, max=1.5)      # (B,4), interpolant_scheduler.py:87-95
+        for f, name in enumerate('xace'):
+            term, cnt = table[:, 2 * f], table[:, 2 * f + 1]
+            if not time_scaled:
+                losses[name] = term.sum() / cnt.sum()
+            elif name == 'x':
+                losses[name] = (w[:, f] * term).sum() / cnt.sum()
+            else:      # (rows,) * (rows, 1): the mean of an outer product
+                R = n_rows[name].sum()
+                losses[name] = (term.sum() / R) * ((w[:, f] * n_rows[name]).sum() / R)
+        return losses
 
     def _given_molecules(self, molecules):
         """The molecules of a ``resample`` call as one token state on the CPU ({'x_t' (N,3) float32, 'a_t', 'c_t' (N), 'e_t' (U) int64}) and their

@@ -23,6 +23,9 @@
  *                       373-388, 414-510) as the in-kernel noise mode makes them, materialised in the reference's shapes
  *   fm_conditional_path CTMCVectorField.sample_conditional_path, ctmc_vector_field.py:97-143: g_t ~ p(g_t | g_0, g_1) for given molecules g_1 at a
  *                       per-graph time, with x_0 and the uniforms from the per-molecule counter-based streams instead of torch's generator
+ *   fm_denoising_loss   the part of FlowMol.forward after sample_conditional_path, flowmol/models/flowmol.py:339-413: one evaluation on logits
+ *                       (vector_field.py:217 apply_softmax=False, remove_com=False), CrossEntropyLoss / MSELoss row terms, per-molecule sums
+ *   fm_distort_philox   the geometry distortion of FlowMol.forward, flowmol.py:333-337, from the per-molecule counter-based streams
  *
  * Conventions
  *   - every function returns 0 on success or a negative fm_status; the message is available from
@@ -55,7 +58,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 10
+#define FM_ABI_VERSION 11
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -351,6 +354,34 @@ int fm_integrate_mixed(fm_ctx* ctx, void* stream, const fm_state* state, int n_s
 typedef struct fm_cond_tape { float* x0; float* u_a; float* u_c; float* u_e; } fm_cond_tape;   /* optional outputs, any may be NULL */
 int fm_conditional_path(fm_ctx* ctx, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
                         const fm_state* out, const fm_cond_tape* tape);
+
+/* --- ABI 11: the denoising loss of given molecules, FlowMol.forward (flowmol/models/flowmol.py:297-415) after its sample_conditional_path call.
+ * fm_denoising_loss runs ONE evaluation of the bound batch on xt -- the launch plan of fm_forward_mixed(prev = NULL, bootstrap = 0, remove_com = 0), temb / n_groups /
+ * mol_group as there (mol_group may be NULL with n_groups == 1) -- with the output heads in their loss variant, then one reduction launch.  The heads keep their logits
+ * on chip (vector_field.py:217: apply_softmax=False) and write, per row, what CrossEntropyLoss(reduction='none') gives on them (flowmol.py:408):
+ *   rows->a, rows->c (N), rows->e (U, upper-triangle order)   nll = (logf(sum_c expf(l_c - m)) + m) - l_target, m = max_c l_c: -log_softmax(l)[target] as torch evaluates it;
+ *                         +0.0 for a row the ignore_index rule drops, i.e. whose token in xt is not the mask token (flowmol.py:378-384)
+ *   rows->x (N)           se = ((dx dx) + dy dy) + dz dz, d = predicted x_1 (not COM-removed) - x1->x_t, separately rounded: MSELoss(reduction='none') summed over xyz
+ *   mol_out (n_mols, 8)   {se_x, 3 n_atoms, nll_a, cnt_a, nll_c, cnt_c, nll_e, cnt_e}: the molecule's sums of the row terms in the canonical order documented at
+ *                         fm_k_denoise_reduce (csrc/fm_kernels.h: 16-row chunks from the molecule's first row, rows in order, chunks in order) and the number of
+ *                         rows that count.  The reference's batch values follow on the host: mean x = sum se_x / sum 3 n_atoms, categorical = sum nll / sum cnt
+ *                         (flowmol.py:388-413; FlowMol.denoising_loss in flowmol_amd/model.py also restates the time-scaled variant).
+ * x1 holds the targets: real-category tokens (the kernels index the logits with them, they do not range-check them), and x_t = the centred positions
+ * x_1 - mean the conditional path used.  xt and x1 are only read.
+ * temb == NULL skips the evaluation: rows then holds the CALLER's row terms (all four), xt's tokens say which rows count, and only the reduction runs.
+ * It never bootstraps: the reference's eval-mode special case `prev is None and (t == 0).all()` (vector_field.py:269-272) depends on the whole batch and is the one
+ * deliberate difference.  Does not synchronise, allocates nothing and needs no workspace beyond the bind's.  FM_ERR_INVALID, with a message, for an endpoint model,
+ * n_groups outside 1..32, a NULL member of rows, rows or mol_out aliasing an input or each other, and a molecule with more than 2^24 pair rows (cnt_e is a float). */
+typedef struct fm_loss_rows { float* x; float* a; float* c; float* e; } fm_loss_rows;   /* caller-owned: (N) se, (N), (N), (U) nll; all required */
+int fm_denoising_loss(fm_ctx* ctx, void* stream, const fm_state* xt, const fm_state* x1, const float* temb, int n_groups, const int32_t* mol_group,
+                      const fm_loss_rows* rows, float* mol_out /* (n_mols, 8) */);
+/* fm_distort_philox: flowmol.py:333-337 in place on x (N,3): every atom of a molecule whose group is switched on (group_on: DEVICE (n_groups) int32, non-zero where the
+ * group's t > distort_t; mol_group as above) gets x += (z * [u < p]) * 0.5, three normals z and one uniform u per atom from the stream entry "distortion" (csrc/fm_device.h,
+ * DESIGN.md section 6), disjoint from every other draw.  tape (may be NULL, as may its members): z (N,3) and u (N) of every atom, switched on or not.  Same conventions;
+ * FM_ERR_INVALID for n_groups < 1, a NULL mol_group with n_groups > 1, p outside [0, 1] and a tape that aliases x. */
+typedef struct fm_distort_tape { float* z; float* u; } fm_distort_tape;
+int fm_distort_philox(fm_ctx* ctx, void* stream, uint64_t seed, float p, int n_groups, const int32_t* mol_group,
+                      const int32_t* group_on /* DEVICE (n_groups) */, float* x, const fm_distort_tape* tape);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
