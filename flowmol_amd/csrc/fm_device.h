@@ -45,6 +45,7 @@ __device__ __forceinline__ int fm_trace_slot(int id) {
                                         ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) << 32); }
 #define FM_MARK_ARG , int fm_tb_
 #define FM_MARK_PASS(b) , (b)
+#define FM_MARK_FWD , fm_tb_
 #define FM_MARK(id) do { if (threadIdx.x == 0 && blockIdx.x < 16384 && gridDim.x > 20000) { const int sl_ = fm_trace_slot(id); \
         if (sl_ >= 0) fm_trace[blockIdx.x * 16 + sl_] = __builtin_readcyclecounter(); } } while (0)
 #define FM_MARKB(k) FM_MARK(fm_tb_ + (k))
@@ -53,6 +54,7 @@ __device__ unsigned long long fm_tlog[64];
 #define FM_MARK_DECL unsigned long long fm_tl_ = __builtin_readcyclecounter();
 #define FM_MARK_ARG , unsigned long long& fm_tl_, int fm_tb_
 #define FM_MARK_PASS(b) , fm_tl_, (b)
+#define FM_MARK_FWD , fm_tl_, fm_tb_
 #define FM_MARK(id) do { if (threadIdx.x == 0) { unsigned long long now_ = __builtin_readcyclecounter(); \
         atomicAdd(&fm_tlog[(id)], now_ - fm_tl_); fm_tl_ = now_; } } while (0)
 #define FM_MARKB(k) FM_MARK(fm_tb_ + (k))
@@ -60,6 +62,7 @@ __device__ unsigned long long fm_tlog[64];
 #define FM_MARK_DECL
 #define FM_MARK_ARG
 #define FM_MARK_PASS(b)
+#define FM_MARK_FWD
 #define FM_MARK(id) ((void)0)
 #define FM_MARKB(k) ((void)0)
 #endif
@@ -387,6 +390,86 @@ __device__ __forceinline__ f32x4 fm_wave_gemm_1x1(const float* A, int lda, const
     return acc0 + acc1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// GEMMs whose weight fragments were requested EARLIER (32-row f32 edge-message tiles, fm_gvp_core_pf).  The small GEMMs of a GVP -- [Wh | Wcp], Wu,
+// gates -- are one or two single-tile jobs per wave, each a few MFMAs behind an L2 round trip, and the scalar GEMM starts with one: the phases are
+// latency.  Their B fragments depend on nothing the tile computes, so they are requested one phase ahead, behind a VALU / LDS phase that asks nothing of
+// the vector memory pipe (VMEM returns in order: requests are issued in the order of use), and a wave's two jobs of one phase, which share their column
+// tiles, use ONE set of fragments.  Every function below issues the MFMA sequence of the function it stands in for: the same bits.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float2 fm_a_frag(const float* ap, int ks) {      // the lane's A fragment of k-superstep ks (one ds_read_b64: fm_frag_load)
+    const f32x2 t = *(const volatile __attribute__((address_space(3))) f32x2*)(ap + 8 * ks);
+    float2 a; a.x = t[0]; a.y = t[1];
+    return a;
+}
+
+// request the fragments of k-supersteps 0 .. K8-1, column tiles 0 .. NT-1 from the wave-uniform base `wp`; pinned here (hipcc sinks a load to its first use)
+template <int K8, int NTB, int NT = NTB>
+__device__ __forceinline__ void fm_wfrag_request(float2 (&b)[K8][NTB], const float2* __restrict__ wp, size_t wstep, int lane) {
+#pragma unroll
+    for (int ks = 0; ks < K8; ++ks)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) b[ks][nt] = fm_wload(wp, (int)(((size_t)ks * wstep + (size_t)nt * 64) * sizeof(float2)), lane);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// fm_wave_gemm<1, NT> over K8 k-supersteps with the B fragments in registers (x pass, then y pass per superstep)
+template <int K8, int NT, int NTB>
+__device__ __forceinline__ void fm_tile_gemm_regb(f32x4 (&acc)[NT], const float* ap, const float2 (&b)[K8][NTB]) {
+    float2 a[K8];
+#pragma unroll
+    for (int ks = 0; ks < K8; ++ks) a[ks] = fm_a_frag(ap, ks);
+#pragma unroll
+    for (int ks = 0; ks < K8; ++ks) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks].x, b[ks][nt].x, acc[nt], 0, 0, 0);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks].y, b[ks][nt].y, acc[nt], 0, 0, 0);
+    }
+}
+
+// fm_wave_gemm_1x1<K8, CH> (CH even) with the B fragments in registers: even k-supersteps on one accumulator, odd ones on the other, added at the end
+template <int K8>
+__device__ __forceinline__ f32x4 fm_wave_gemm_1x1_regb(const float* ap, const float2 (&b)[K8][1]) {
+    static_assert(K8 % 2 == 0, "pairs of k-supersteps");
+    float2 a[K8];
+#pragma unroll
+    for (int ks = 0; ks < K8; ++ks) a[ks] = fm_a_frag(ap, ks);
+    f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < K8; q += 2) {
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q].x, b[q][0].x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q + 1].x, b[q + 1][0].x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q].y, b[q][0].y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q + 1].y, b[q + 1][0].y, acc1, 0, 0, 0);
+    }
+    return acc0 + acc1;
+}
+
+// fm_wave_gemm<MT, NT, TAILX> with compile-time K8 whose B fragments of k-supersteps 0 and 1 are in registers (`pb`): the 3-set pipeline starts with
+// two LDS reads instead of an L2 round trip.  Straight-line code: immediate LDS offsets, scalar weight offsets.
+template <int MT, int NT, int K8, bool TAILX>
+__device__ __forceinline__ void fm_wave_gemm_pre(f32x4 (&acc)[MT][NT], const float* ap, int lda, const float2* __restrict__ wp, size_t wstep, int lane,
+                                                 const float2 (&pb)[2][NT]) {
+    static_assert(K8 >= 2, "two k-supersteps are preloaded");
+    float2 a[3][MT], b[3][NT];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) a[s][mt] = fm_a_frag(ap + mt * 16 * lda, s);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) b[s][nt] = pb[s][nt];
+    }
+#pragma unroll
+    for (int i = 0; i < K8; ++i) {
+        if (i + 2 < K8) fm_frag_load<MT, NT>(a[(i + 2) % 3], b[(i + 2) % 3], ap, lda, wp, wstep, i + 2, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (TAILX && i + 1 == K8) fm_frag_mma_x<MT, NT>(acc, a[i % 3], b[i % 3]);
+        else fm_frag_mma<MT, NT>(acc, a[i % 3], b[i % 3]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // block-level GEMM over an (mtiles x ntiles) grid of 16x16 output tiles: super-tiles of MT x NT tiles
 // are dealt round-robin to the 8 waves; epi(row, col, value) is called for every output element.
 // No barriers inside: the caller orders LDS hazards.
@@ -668,10 +751,19 @@ struct FmGvpTile {
 // RG > 0 (node kernels of small batches): only rows 0 .. 4 RG - 1 of the TM-row frame are nodes; the scalar GEMM -- the one phase whose cost
 // scales with the tile height -- runs on those rows with fm_wave_gemm4 (64 columns on each of waves 0..3, one fma chain per output element in the k-order of the
 // regular tiles' 16x16x4 MFMAs: the bits of the regular 16- / 32-row tiles); every other phase is the TM-row code over the frame.
-template <int V, int VOUT, bool FIRST, bool SIGMOID, int TM, int NTH, int HX = 0, int SP = 0, bool LAST = false, bool PQ = false, int RG = 0>
-__device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, float* G, const FmGvpW& w,
-                                            float (&pre)[TM / 16][1024 / NTH][4] FM_MARK_ARG) {
+//
+// PF (the f32 32-row edge-message tiles with 32 vector channels; fm_gvp_core below is PF = false): the weight fragments of the latency phases are requested
+// a phase ahead and shared by a wave's two jobs (see fm_wfrag_request):
+//   Wu:           at the start of the GVP (they arrive behind the [Wh | Wcp] and cross / norm phases); the wave's two jobs share them
+//   scalar GEMM:  k-supersteps 0 and 1 at the start of the Wu phase, which by then asks nothing of the vector memory pipe
+//   gates:        behind the scalar GEMM, in front of the barrier and the SiLU
+//   [Wh | Wcp]:   of the NEXT GVP (`wn`), behind the gate GEMM, in front of the gating loop; they travel in `bw` (16 VGPRs); two jobs share them
+// Same MFMA sequences as the plain path, so the same bits; LDS unchanged.
+template <int V, int VOUT, bool FIRST, bool SIGMOID, int TM, int NTH, int HX, int SP, bool LAST, bool PQ, int RG, bool PF>
+__device__ __forceinline__ void fm_gvp_core_pf(float* X, float* Vin, float* Vh, float* G, const FmGvpW& w, const FmGvpW& wn, float2 (&bw)[V / 8][2],
+                                               float (&pre)[TM / 16][1024 / NTH][4] FM_MARK_ARG) {
     typedef FmGvpTile<V, TM, HX> T;
+    static_assert(!PF || (V == 32 && VOUT == 32 && TM == 32 && NTH == 512 && SP == 0 && HX == 0 && RG == 0), "PF is for the f32 32-row edge-message tiles, V = 32");
     unsigned short* const XH = reinterpret_cast<unsigned short*>(X);
     unsigned short* const XL = XH + TM * FM_LDP;
     constexpr int FMT = SP == 3 ? 1 : 0;                 // SP: 1 = two bf16 planes, 2 = three bf16 planes, 3 = two half planes
@@ -701,10 +793,35 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
     static_assert(NTH % VOUT == 0, "one gate channel per thread");
     const float bias_g = w.bg[tid % VOUT];
 
+    // PF: the wave's Wu jobs are the 16-row tiles wave, wave + NW, .. of Vh times column tile wave % (VOP / 16) -- one set of fragments, requested now
+    constexpr int SNU = VOP / 16;
+    static_assert(!PF || NW % SNU == 0, "a wave's Wu jobs share their column tile");
+    float2 bu[PF ? KUC / 8 : 1][1], pbs[2][PF ? NTW : 1];      // pbs: k-supersteps 0, 1 of the scalar GEMM's weights, requested at the start of the Wu phase
+    if constexpr (PF) fm_wfrag_request(bu, w.Wu + (size_t)(wave % SNU) * 64, (size_t)SNU * 64, lane);
+
     if (!FIRST && !(FM_ABLATE & 4)) {
         // Vh[:, 0..V+15] = Vin(3TM x V) * [Wh | Wcp | 0]
         constexpr int RT = 3 * TM / 16, CT = (V + 16) / 16;
-        if constexpr (CT == 3) {
+        if constexpr (PF) {
+            // the jobs of the CT == 3 branch below (job & 1 = wave & 1: NW is even) on the fragments the GVP before requested into `bw`
+            static_assert(CT == 3 && NW % 2 == 0, "jobs {column tiles 0, 1} / {2}, a wave's jobs of one kind");
+            for (int job = wave; job < 2 * RT; job += NW) {
+                const int rt = job >> 1;
+                const float* ap = Vin + (size_t)(rt * 16 + (lane & 15)) * T::LDVI + 2 * (lane >> 4);
+                float* D = Vh + (rt * 16 + 4 * (lane >> 4)) * T::LDVH + (lane & 15);
+                if (wave & 1) {
+                    f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+                    fm_tile_gemm_regb<V / 8, 1, 2>(acc, ap, bw);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) D[r * T::LDVH + 32] = acc[0][r];
+                } else {
+                    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+                    fm_tile_gemm_regb<V / 8, 2, 2>(acc, ap, bw);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { D[r * T::LDVH] = acc[0][r]; D[r * T::LDVH + 16] = acc[1][r]; }
+                }
+            }
+        } else if constexpr (CT == 3) {
             // V = 32: column tiles {0, 1} as one job, {2} ([Wcp | 0]) as another: 2 RT jobs instead of 3 RT single-tile jobs -- one round of the
             // eight waves for a 16-row tile instead of two (each job is four k-steps behind one L2 round trip: the phase is latency, not MFMA time)
             for (int job = wave; job < 2 * RT; job += NW) {
@@ -777,12 +894,27 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
     }
     __syncthreads();
     FM_MARKB(1);
+    // PF: k-supersteps 0 and 1 of the scalar GEMM's weights (the Wu fragments arrived long ago: nothing is queued in front of these)
+    if constexpr (PF) fm_wfrag_request(pbs, w.Ws + (size_t)(NTW * wave) * 64, (size_t)16 * 64, lane);
     // Vu = Vh_full * Wu -> Vin (the input vectors are dead by now)
+    if constexpr (PF) {
+        // fm_block_gemm<1, 1>'s jobs (super-tile st = wave, wave + NW, ..: row tile st / SNU, column tile st % SNU = wave % SNU) on the fragments in `bu`
+        const int n0 = wave % SNU;
+        for (int st = wave; st < (3 * TM / 16) * SNU; st += NW) {
+            const int m0 = st / SNU;
+            f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+            fm_tile_gemm_regb<KUC / 8, 1, 1>(acc, Vh + (size_t)(m0 * 16 + (lane & 15)) * T::LDVH + 2 * (lane >> 4), bu);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Vin[(m0 * 16 + 4 * (lane >> 4) + r) * T::LDVI + n0 * 16 + (lane & 15)] = acc[0][r];
+        }
+    } else {
     fm_block_gemm<1, 1>(Vh, T::LDVH, 3 * TM / 16, KUC / 8, w.Wu, VOP / 16,
                         [&](int row, int col, float v) { Vin[row * T::LDVI + col] = v; });
     }
+    }
     // scalar linear: TM x K -> 256, wave w owns column tiles NTW*w .. NTW*w+NTW-1 for all MT row tiles
     float keep[(SP && LAST) ? MT : 1][(SP && LAST) ? NTW : 1][4];     // split precision, last GVP: the f32 scalar output for the aggregation
+    float2 bgt[PF ? 16 : 1][1];                                       // PF: the fragments of the wave's gate job
     if constexpr (RG > 0) {
         constexpr int KQ = (SOFF + KUC) / 4;
         const int g = wave & 3;
@@ -820,7 +952,14 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
         FM_MARKB(2);
         if (SP == 2) fm_wave_gemm_sp3<MT, NTW>(acc, XH, XL, 0, (SOFF + KUC + 31) / 32, w.Ws_sp, 16, NTW * wave, lane);
         else if (SP) { if (!(FM_ABLATE & 32)) fm_wave_gemm_sp<MT, NTW, FM_LDP, FMT>(acc, XH, XL, 0, (SOFF + KUC + 31) / 32, w.Ws_sp, 16, NTW * wave, lane); }
-        else if (!(FM_ABLATE & 32)) fm_wave_gemm<MT, NTW, !FIRST>(acc, X, FM_LDX, K8S, w.Ws, 16, NTW * wave, lane);
+        else if constexpr (PF) {
+            if (!(FM_ABLATE & 32)) fm_wave_gemm_pre<MT, NTW, K8S, !FIRST>(acc, X + (lane & 15) * FM_LDX + 2 * (lane >> 4), FM_LDX, w.Ws + (size_t)(NTW * wave) * 64, (size_t)16 * 64, lane, pbs);
+        } else if (!(FM_ABLATE & 32)) fm_wave_gemm<MT, NTW, !FIRST>(acc, X, FM_LDX, K8S, w.Ws, 16, NTW * wave, lane);
+        if constexpr (PF) {      // this wave's gate job (below): all its fragments, behind the scalar GEMM's and in front of the barrier and the SiLU
+            constexpr int NJ_ = (TM / 16) * (VOP / 16);
+            static_assert(2 * NJ_ == NW, "one gate job per wave");
+            fm_wfrag_request(bgt, w.Wg + (size_t)(wave / NJ_) * 16 * (VOP / 16) * 64 + (size_t)((wave % NJ_) % (VOP / 16)) * 64, (size_t)(VOP / 16) * 64, lane);
+        }
         FM_MARKB(3);
         __syncthreads();                      // every wave has finished reading X (and Vh)
         FM_MARKB(4);
@@ -873,6 +1012,8 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
             else fm_wave_gemm_sp<1, 1, FM_LDP, FMT>(ga, XH + half * (256 / KS), XL + half * (256 / KS), m0 * 16, 8 / KS,
                                   static_cast<const char*>(w.Wg_sp) + (size_t)half * (8 / KS) * (VOP / 16) * 2 * 64 * 16, VOP / 16, n0, lane);
             g = ga[0][0] * (1.0f / fm_sp_wscale<FMT>());
+        } else if constexpr (PF) {
+            g = fm_wave_gemm_1x1_regb<32 / KS>(X + (size_t)(m0 * 16 + (lane & 15)) * FM_LDX + half * (256 / KS) + 2 * (lane >> 4), bgt);
         } else {
             g = fm_wave_gemm_1x1<32 / KS, 8>(X + (size_t)m0 * 16 * FM_LDX + half * (256 / KS), FM_LDX,
                                              w.Wg + (size_t)half * (32 / KS) * (VOP / 16) * 64, VOP / 16, n0, lane);
@@ -880,6 +1021,11 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
         float* go = (half ? gpart(half) : G) + (m0 * 16 + 4 * (lane >> 4)) * FM_LDG + n0 * 16 + (lane & 15);
 #pragma unroll
         for (int r = 0; r < 4; ++r) go[r * FM_LDG] = g[r];
+    }
+    // PF: the [Wh | Wcp] fragments of the NEXT GVP's jobs of this wave: column tiles {0, 1} (even waves) or {2} (odd waves) of its three
+    if constexpr (PF && !LAST) {
+        if (wave & 1) fm_wfrag_request<V / 8, 2, 1>(bw, wn.Wv1 + 2 * 64, (size_t)3 * 64, lane);
+        else fm_wfrag_request<V / 8, 2, 2>(bw, wn.Wv1, (size_t)3 * 64, lane);
     }
     FM_MARKB(6);
     __syncthreads();
@@ -904,6 +1050,13 @@ __device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, flo
     }
     __syncthreads();
     FM_MARKB(7);
+}
+
+template <int V, int VOUT, bool FIRST, bool SIGMOID, int TM, int NTH, int HX = 0, int SP = 0, bool LAST = false, bool PQ = false, int RG = 0>
+__device__ __forceinline__ void fm_gvp_core(float* X, float* Vin, float* Vh, float* G, const FmGvpW& w,
+                                            float (&pre)[TM / 16][1024 / NTH][4] FM_MARK_ARG) {
+    float2 none[V / 8][2];      // never touched with PF = false
+    fm_gvp_core_pf<V, VOUT, FIRST, SIGMOID, TM, NTH, HX, SP, LAST, PQ, RG, false>(X, Vin, Vh, G, w, w, none, pre FM_MARK_FWD);
 }
 
 // per-element addend of the first edge GVP's scalar linear: addend[row of rowoff[..]][col] for this lane's accumulator elements.

@@ -1026,7 +1026,10 @@ static int plan_batch(fm_ctx* c, const int32_t* n_atoms, int B, BatchPlan& p) {
     // composition of its batch (see FM_CHUNK_E in fm_kernels.h for the aggregation order).  Tile heights -- incl. the 4 RG-node instances and the 4-row node
     // MLPs, whose GEMMs keep the regular tiles' order since round 6 (fm_wave_gemm4) -- follow the batch size in both modes.  -1: the pair slab follows the
     // batch size too (round 5's rule).  The Q tables (U KB each) exist in the workspace only when the batch uses them.
-    if (U > 0 && (cf.pair_slab > 0 || cf.canonical >= 0 || (U + 31) / 32 >= 16LL * n_cus)) p.n_pq = m.slab_convs;      // ModelPlan::slab_convs: which models
+    // The pair-slab instance gathers a tile's Q rows with 31-bit byte offsets (pair - the tile's smallest pair) * 1024 inside ONE molecule's pairs: like the
+    // fused edge head above that holds for n < 2049 atoms; a batch with a larger molecule runs the full instance on every convolution (forced or canonical alike).
+    const bool pq_fits = (long long)nmax * (nmax - 1) * 512 < 0x7ffffe00LL;
+    if (U > 0 && pq_fits && (cf.pair_slab > 0 || cf.canonical >= 0 || (U + 31) / 32 >= 16LL * n_cus)) p.n_pq = m.slab_convs;      // ModelPlan::slab_convs: which models
     // Node- and pair-side MLPs with the same inputs share one launch while the batch is small (launch_mlp_stage); fm_config.pair_mlps = 1 | -1 forces either
     const int mlp_tiles = (p.N + FM_TM - 1) / FM_TM + (U + FM_TM - 1) / FM_TM;
     p.pair_mlps = cf.fuse_node >= 0 && (cf.pair_mlps ? cf.pair_mlps > 0 : mlp_tiles <= n_cus);

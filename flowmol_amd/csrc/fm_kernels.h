@@ -880,9 +880,13 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
     }
     __syncthreads();
     FM_MARK(1);
-    fm_gvp_core<V, V, true, true, TM, NTH, HX, SP, false, PQ != 0>(X, Vin, Vh, G, a.g0, pre FM_MARK_PASS(10));
-    fm_gvp_core<V, V, false, true, TM, NTH, HX, SP, false>(X, Vin, Vh, G, a.g1, pre FM_MARK_PASS(20));
-    fm_gvp_core<V, V, false, true, TM, NTH, HX, SP, true>(X, Vin, Vh, G, a.g2, pre FM_MARK_PASS(30));
+    // f32 32-row tiles with 32 vector channels: the weight fragments of the GVPs' latency phases are requested a phase ahead (fm_gvp_core_pf); `bw` carries
+    // the [Wh | Wcp] fragments a GVP requests for the next one.  Every other instance keeps the plain sequence.
+    constexpr bool PF = V == 32 && TM == 32 && NTH == 512 && SP == 0 && HX == 0;
+    float2 bw[V / 8][2];
+    fm_gvp_core_pf<V, V, true, true, TM, NTH, HX, SP, false, PQ != 0, 0, PF>(X, Vin, Vh, G, a.g0, a.g1, bw, pre FM_MARK_PASS(10));
+    fm_gvp_core_pf<V, V, false, true, TM, NTH, HX, SP, false, false, 0, PF>(X, Vin, Vh, G, a.g1, a.g2, bw, pre FM_MARK_PASS(20));
+    fm_gvp_core_pf<V, V, false, true, TM, NTH, HX, SP, true, false, 0, PF>(X, Vin, Vh, G, a.g2, a.g2, bw, pre FM_MARK_PASS(30));
 
     if (a.dbg_s) {
         for (int idx = tid; idx < TM * 256; idx += NTH) {
@@ -1105,13 +1109,22 @@ __global__ void __launch_bounds__(FM_THREADS) fm_k_node_update(FmNodeUpdArgs a) 
     }
     __syncthreads();
     const int s_width = NARROW ? a.s_real : 256;
+    // full-width f32 32-row tiles: the GVPs' weight fragments are requested a phase ahead (fm_gvp_core_pf); the first GVP's [Wh | Wcp] fragments here, in
+    // front of the layer norm (column tiles {0, 1} on even waves, {2} on odd ones)
+    constexpr bool PF = V == 32 && TM == 32 && SP == 0 && RG == 0 && !NARROW;
+    float2 bw[V / 8][2];
+    if constexpr (PF) {
+        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        if (wave & 1) fm_wfrag_request<V / 8, 2, 1>(bw, a.g0.Wv1 + 2 * 64, (size_t)3 * 64, lane);
+        else fm_wfrag_request<V / 8, 2, 2>(bw, a.g0.Wv1, (size_t)3 * 64, lane);
+    }
     fm_gvp_layernorm_tile<V, TM, SP>(X, Vin, a.ln1_g, a.ln1_b, row0, N, a.s, a.v, s_width, RV);     // s1, v1 -> HBM (needed for the residual)
     {
         FM_MARK_DECL
         float pre[TM / 16][2][4];
-        fm_gvp_core<V, V, false, true, TM, FM_THREADS, 0, SP, false, false, RG>(X, Vin, Vh, G, a.g0, pre FM_MARK_PASS(50));
-        fm_gvp_core<V, V, false, true, TM, FM_THREADS, 0, SP, false, false, RG>(X, Vin, Vh, G, a.g1, pre FM_MARK_PASS(50));
-        fm_gvp_core<V, V, false, true, TM, FM_THREADS, 0, SP, true, false, RG>(X, Vin, Vh, G, a.g2, pre FM_MARK_PASS(50));      // SP: leaves the f32 tile for the residual
+        fm_gvp_core_pf<V, V, false, true, TM, FM_THREADS, 0, SP, false, false, RG, PF>(X, Vin, Vh, G, a.g0, a.g1, bw, pre FM_MARK_PASS(50));
+        fm_gvp_core_pf<V, V, false, true, TM, FM_THREADS, 0, SP, false, false, RG, PF>(X, Vin, Vh, G, a.g1, a.g2, bw, pre FM_MARK_PASS(50));
+        fm_gvp_core_pf<V, V, false, true, TM, FM_THREADS, 0, SP, true, false, RG, PF>(X, Vin, Vh, G, a.g2, a.g2, bw, pre FM_MARK_PASS(50));      // SP: leaves the f32 tile for the residual
     }
     {   // residual: + (s1, v1), re-read from HBM with 16-byte loads (rows beyond N read 0)
         constexpr int NQ = TM * 64 / FM_THREADS;
