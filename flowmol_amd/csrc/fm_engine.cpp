@@ -221,6 +221,10 @@ const InstList<EdgeUpdSpFn> edge_update_sp_instances{"tile_rows, half_planes", {
 // hence a list of its own.  No dynamic LDS; the workgroup size is BatchPlan::ctmc_threads
 const InstList<decltype(&fm_k_ctmc_fused_mixed<256>)> ctmc_mixed_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused_mixed<1024>, 0}, {{256}, fm_k_ctmc_fused_mixed<256>, 0}}};
 const InstList<decltype(&fm_k_ctmc_fused<256>)> ctmc_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused<1024>, 0}, {{256}, fm_k_ctmc_fused<256>, 0}}};
+// the same three kernels with frozen rows (fm_ctmc_step_inpaint / fm_integrate_inpaint): lists of their own, so the lists above launch what they always did
+const InstList<decltype(&fm_k_ctmc_fused_keep<256>)> ctmc_keep_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused_keep<1024>, 0}, {{256}, fm_k_ctmc_fused_keep<256>, 0}}};
+const InstList<decltype(&fm_k_ctmc_fused_mixed_keep<256>)> ctmc_mixed_keep_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_fused_mixed_keep<1024>, 0}, {{256}, fm_k_ctmc_fused_mixed_keep<256>, 0}}};
+const InstList<decltype(&fm_k_ctmc_gat_fused_keep<256>)> ctmc_gat_keep_instances{"ctmc_threads", {{{1024}, fm_k_ctmc_gat_fused_keep<1024>, 0}, {{256}, fm_k_ctmc_gat_fused_keep<256>, 0}}};
 
 // fm_k_mlp2<mode, tm> over `rows` rows
 void launch_mlp(Launch& L, int mode, const char* name, FmMlpArgs a, const MlpW& w, int rows, int tm = FM_TM) {
@@ -514,11 +518,14 @@ __global__ void fm_k_noop() {}
 
 // device arrays of one call-step of fm_integrate_mixed (FmCtmcMixedArgs)
 struct MixedStep { const fm_step_scalars* steps; const int* active; const int* mol_group; };
+// frozen rows of one step (fm_ctmc_step_inpaint / fm_integrate_inpaint): the kernels' FmKeepArgs -- alpha filled for a batch at one time -- and, with per-molecule
+// time, this call-step's (n_groups, 4) row of the caller's device alpha_next array
+struct KeepStep { FmKeepArgs k; const float* alpha_dev; };
 
 // frame: this step's slice of the trajectory sink (x, a, c, e, x1 used; a1 / c1 / e1 travel in `smp`); campbell steps write it inside the fused kernel
 int ctmc_impl(fm_ctx* c, hipStream_t st, const Modality (&md)[3], const fm_state* state, const fm_dst* dst, const fm_step_noise* nz,
               const fm_step_scalars* sc, const fm_sampled* smp, const float* x_raw = nullptr, const fm_traj_sink* frame = nullptr,
-              const MixedStep* mixed = nullptr) {
+              const MixedStep* mixed = nullptr, const KeepStep* keep = nullptr) {
     Launch L{c, st};
     // profiling only: an event pair around an empty kernel, once per step.  Its elapsed time is what a pair adds to every profiled launch
     // (event signalling + the dispatch that cannot overlap the previous kernel's tail); fm_profile_get("event_overhead") lets the caller
@@ -552,19 +559,24 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const Modality (&md)[3], const fm_state
         fill_fused(f);
         for (int m = 0; m < 3; ++m) { f.mod[m].cf = sc->gat_cf[m]; f.mod[m].cb = sc->gat_cb[m]; }
         f.temp = sc->cat_temperature; f.fw = sc->gat_fw; f.bw = sc->gat_bw; f.dt_cat = sc->dt;
-        launch_inst(L, ctmc_gat_instances(), {nt}, "ctmc", grid, blk, 0, f);
+        if (keep) launch_inst(L, ctmc_gat_keep_instances, {nt}, "ctmc_keep", grid, blk, 0, f, keep->k);
+        else launch_inst(L, ctmc_gat_instances(), {nt}, "ctmc", grid, blk, 0, f);
         return L.rc;
     }
     if (sc->dfm_type == FM_DFM_GAT) {      // tensor noise: the Euler step and one flat kernel per modality
         if (!nz->q_a) return fail(c, FM_ERR_INVALID, "%s", missing);
-        L("x_step", fm_k_x_step, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3);
+        if (keep) L("x_step_keep", fm_k_x_step_keep, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3,
+                    FmKeepX{keep->k.keep[0], keep->k.x0, keep->k.x1c, keep->k.alpha[0]});
+        else L("x_step", fm_k_x_step, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3);
         for (int m = 0; m < 3; ++m) {
             if (md[m].rows == 0) continue;
             FmGatArgs a{};
             fill_mod(a, m);
             a.rows = md[m].rows; a.q = pick3(m, nz->q_a, nz->q_c, nz->q_e);
             a.temp = sc->cat_temperature; a.cf = sc->gat_cf[m]; a.cb = sc->gat_cb[m]; a.fw = sc->gat_fw; a.bw = sc->gat_bw; a.dt = sc->dt;
-            L("ctmc_gat", fm_k_ctmc_gat, dim3((a.rows + 255) / 256), dim3(256), 0, a);
+            if (keep) L("ctmc_gat_keep", fm_k_ctmc_gat_keep, dim3((a.rows + 255) / 256), dim3(256), 0, a,
+                        FmKeepMod{keep->k.keep[m], keep->k.tok1[m], keep->k.u[m], 1.0f - keep->k.alpha[1 + m]});
+            else L("ctmc_gat", fm_k_ctmc_gat, dim3((a.rows + 255) / 256), dim3(256), 0, a);
         }
         return L.rc;
     }
@@ -579,18 +591,21 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const Modality (&md)[3], const fm_state
     f.temp = sc->cat_temperature; f.hc_thresh = sc->hc_thresh; f.last_step = sc->last_step; f.philox = philox;
     if (!philox && (!nz->q_a || !nz->u1_a || !nz->q_e)) return fail(c, FM_ERR_INVALID, "%s", missing);
     // per-molecule time: the scalars of `f` are unused, every molecule reads its group's from the caller's device arrays
-    if (mixed) launch_inst(L, ctmc_mixed_instances, {nt}, "ctmc_mixed", grid, blk, 0, FmCtmcMixedArgs{f, mixed->steps, mixed->active, mixed->mol_group});
+    if (mixed && keep) launch_inst(L, ctmc_mixed_keep_instances, {nt}, "ctmc_mixed_keep", grid, blk, 0, FmCtmcMixedArgs{f, mixed->steps, mixed->active, mixed->mol_group}, keep->k, keep->alpha_dev);
+    else if (keep) launch_inst(L, ctmc_keep_instances, {nt}, "ctmc_keep", grid, blk, 0, f, keep->k);
+    else if (mixed) launch_inst(L, ctmc_mixed_instances, {nt}, "ctmc_mixed", grid, blk, 0, FmCtmcMixedArgs{f, mixed->steps, mixed->active, mixed->mol_group});
     else launch_inst(L, ctmc_instances, {nt}, "ctmc", grid, blk, 0, f);
     return L.rc;
 }
 
 // The step loop of fm_integrate and fm_integrate_mixed: the endpoint predictions ping-pong between dst_a and dst_b from prev0 on, the embedding tables of a
 // chunk of steps are built in one launch (`tabs` tables per step, temb: n_steps x tabs rows; tab_slot: forward_impl), every step is one evaluation and one CTMC
-// step with its frame of the sink.  step(i, prev, sc, nz, mixed) sets what differs per step (mixed.mol_group stays null for a batch at one time) and returns
+// step with its frame of the sink.  keep_of(i): step i's frozen rows (fm_integrate_inpaint), absent for every other caller.  step(i, prev, sc, nz, mixed) sets what differs per step (mixed.mol_group stays null for a batch at one time) and returns
 // the bootstrap flag (no previous prediction and t = 0, vector_field.py:269-272); the entry points check their arguments first: a refused call enqueues nothing.
 template <class StepFn>
 int step_driver(fm_ctx* c, hipStream_t st, const fm_state* state, int n_steps, int tabs, const int* tab_slot, const float* temb, const fm_dst* prev0,
-                const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst, StepFn step) {
+                const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst, StepFn step,
+                const std::function<const KeepStep*(int)>& keep_of = nullptr) {
     const int tt = c->cfg.time_embedding_dim, spc = FM_TAB_SLOTS / tabs;      // steps per table launch: every table of a chunk owns a slot
     const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
     const fm_dst* prev = prev0;
@@ -619,7 +634,8 @@ int step_driver(fm_ctx* c, hipStream_t st, const fm_state* state, int n_steps, i
             frame.x = pos(sink->x); frame.a = tok(sink->a, 0); frame.c = tok(sink->c, 1); frame.e = tok(sink->e, 2); frame.x1 = pos(sink->x1);
         }
         const bool in_kernel = sink && defer_com;      // the fused kernels write the frames too
-        rc = ctmc_impl(c, st, md, state, out, nz, sc, &smp, defer_com ? c->ws.xw : nullptr, in_kernel ? &frame : nullptr, mixed.mol_group ? &mixed : nullptr);
+        rc = ctmc_impl(c, st, md, state, out, nz, sc, &smp, defer_com ? c->ws.xw : nullptr, in_kernel ? &frame : nullptr, mixed.mol_group ? &mixed : nullptr,
+                       keep_of ? keep_of(i) : nullptr);
         if (rc) return rc;
         if (sink && !in_kernel) {      // tensor-noise 'gat' steps (three small kernels): frames by copy
             Launch L{c, st};
@@ -1389,6 +1405,104 @@ int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_ste
                        [&](int i, const fm_dst*, const fm_step_scalars*& sc, const fm_step_noise*&, MixedStep& mixed) {
         sc = &philox_step; mixed = {steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
         return i == 0 ? boot0 : 0; });
+}
+
+// What both frozen-row entry points refuse, before anything is enqueued, and the kernels' view of the caller's struct.  others: every pointer the call writes
+// through or reads as the evolving state (state, endpoint buffers, sampled tokens, sink).
+static int inpaint_check(fm_ctx* c, const char* fn, const fm_inpaint* inp, std::initializer_list<const void*> others, FmKeepArgs& k) {
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) have no masked conditional path to freeze rows on", fn);
+    const bool pairs = c->ws.b.U > 0;
+    const void* const mem[] = {inp->keep_atom, inp->keep_pair, inp->x0, inp->x1c, inp->a1, inp->c1, inp->e1, inp->u_a, inp->u_c, inp->u_e};
+    static const char* const tag[] = {"keep_atom", "keep_pair", "x0", "x1c", "a1", "c1", "e1", "u_a", "u_c", "u_e"};
+    static const bool pair_only[] = {false, true, false, false, false, false, true, false, false, true};
+    for (int i = 0; i < 10; ++i) {
+        if (!mem[i] && (pairs || !pair_only[i])) return fail(c, FM_ERR_INVALID, "%s: fm_inpaint.%s is NULL", fn, tag[i]);
+        for (const void* o : others) if (mem[i] && o == mem[i]) return fail(c, FM_ERR_INVALID, "%s: fm_inpaint.%s aliases the state, an endpoint buffer or the sink", fn, tag[i]);
+    }
+    k = FmKeepArgs{};
+    k.keep[0] = k.keep[1] = inp->keep_atom; k.keep[2] = inp->keep_pair;
+    k.tok1[0] = inp->a1; k.tok1[1] = inp->c1; k.tok1[2] = inp->e1;
+    k.u[0] = inp->u_a; k.u[1] = inp->u_c; k.u[2] = inp->u_e;
+    k.x0 = inp->x0; k.x1c = inp->x1c;
+    return FM_OK;
+}
+// keep_pair of the caller's struct from keep_atom: one launch per call, ahead of the steps
+static int keep_pairs(fm_ctx* c, hipStream_t st, const fm_inpaint* inp) {
+    const FmBatch& b = c->ws.b;
+    Launch L{c, st};
+    L("keep_pairs", fm_k_keep_pairs, dim3((b.U + 255) / 256), dim3(256), 0, (const unsigned char*)inp->keep_atom, (unsigned char*)inp->keep_pair,
+      (const int*)b.p_e0, (const int*)b.e_src, (const int*)b.e_dst, b.U);
+    return L.rc;
+}
+
+int fm_ctmc_step_inpaint(fm_ctx* c, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
+                         const fm_sampled* sampled, const fm_inpaint* inp, const float* alpha_next) {
+    const char* const fn = "fm_ctmc_step_inpaint";
+    if (const int rc = bound_check(c, fn, state && dst && sc && inp && alpha_next)) return rc;
+    KeepStep ks{};
+    if (const int rc = inpaint_check(c, fn, inp, {state->x_t, state->a_t, state->c_t, state->e_t, dst->x, dst->a, dst->c, dst->e,
+                                                  sampled ? sampled->a1 : nullptr, sampled ? sampled->c1 : nullptr, sampled ? sampled->e1 : nullptr}, ks.k)) return rc;
+    if (sc->dfm_type != FM_DFM_CAMPBELL && sc->dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "%s: unknown dfm_type %d", fn, sc->dfm_type);
+    if (sc->noise_mode != FM_NOISE_PHILOX && !noise) return fail(c, FM_ERR_INVALID, "%s: noise tensors missing (noise_mode FM_NOISE_TENSORS)", fn);
+    for (int k = 0; k < 4; ++k) ks.k.alpha[k] = alpha_next[k];
+    if (const int rc = keep_pairs(c, (hipStream_t)stream, inp)) return rc;
+    const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
+    return ctmc_impl(c, (hipStream_t)stream, md, state, dst, noise, sc, sampled, nullptr, nullptr, nullptr, &ks);
+}
+
+int fm_integrate_inpaint(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                         const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                         const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                         const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev) {
+    const char* const fn = "fm_integrate_inpaint";
+    const bool one = n_groups == 1;
+    const bool args_ok = state && steps && temb && dst_a && dst_b && inp && alpha_next && (one || (steps_dev && active && active_dev && mol_group && alpha_next_dev));
+    if (const int rc = bound_check(c, fn, args_ok)) return rc;
+    if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
+    static const fm_traj_sink no_sink{};
+    const fm_traj_sink& sk = sink ? *sink : no_sink;
+    FmKeepArgs k0{};
+    if (const int rc = inpaint_check(c, fn, inp, {state->x_t, state->a_t, state->c_t, state->e_t, dst_a->x, dst_a->a, dst_a->c, dst_a->e, dst_b->x, dst_b->a, dst_b->c, dst_b->e,
+                                                  sk.x, sk.a, sk.c, sk.e, sk.x1, sk.a1, sk.c1, sk.e1}, k0)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    std::vector<KeepStep> ks((size_t)std::max(n_steps, 0));
+    for (int i = 0; i < n_steps; ++i) {
+        ks[i].k = k0;
+        if (one) for (int q = 0; q < 4; ++q) ks[i].k.alpha[q] = alpha_next[(size_t)i * 4 + q];
+        else ks[i].alpha_dev = alpha_next_dev + (size_t)i * n_groups * 4;
+    }
+    const auto keep_of = [&](int i) { return (const KeepStep*)&ks[i]; };
+    if (one) {      // a batch at one time: fm_integrate's steps (campbell or gat, either noise mode, trajectory sink) through the single-schedule kernels
+        for (int i = 0; i < n_steps; ++i) {
+            if (steps[i].dfm_type != FM_DFM_CAMPBELL && steps[i].dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "%s: unknown dfm_type %d (step %d)", fn, steps[i].dfm_type, i);
+            if (steps[i].noise_mode != FM_NOISE_PHILOX && !noise) return fail(c, FM_ERR_INVALID, "%s: noise tensors missing (noise_mode FM_NOISE_TENSORS, step %d)", fn, i);
+        }
+        if (const int rc = keep_pairs(c, st, inp)) return rc;
+        return step_driver(c, st, state, n_steps, 1, nullptr, temb, prev0, dst_a, dst_b, sink, final_dst,
+                           [&](int i, const fm_dst* prev, const fm_step_scalars*& sc, const fm_step_noise*& nz, MixedStep&) {
+            sc = &steps[i]; nz = noise ? &noise[i] : nullptr;
+            return !prev && steps[i].t == 0.0f ? 1 : 0; }, keep_of);
+    }
+    // per-molecule time: fm_integrate_mixed's refusals and launch decisions
+    if (sink) return fail(c, FM_ERR_INVALID, "%s: a trajectory sink is not supported with per-molecule time", fn);
+    for (int i = 0; i < n_steps * n_groups; ++i) {
+        if (!active[i]) continue;
+        if (steps[i].dfm_type != FM_DFM_CAMPBELL) return fail(c, FM_ERR_INVALID, "%s: dfm_type gat is not supported with per-molecule time (step %d, group %d)", fn, i / n_groups, i % n_groups);
+        if (steps[i].noise_mode != FM_NOISE_PHILOX) return fail(c, FM_ERR_INVALID, "%s: FM_NOISE_TENSORS is not supported with per-molecule time (step %d, group %d)", fn, i / n_groups, i % n_groups);
+    }
+    int boot0 = 0;
+    if (!prev0 && n_steps > 0) {
+        int at0 = 0, later = 0;
+        for (int g = 0; g < n_groups; ++g) if (active[g]) (steps[g].t == 0.0f ? at0 : later) += 1;
+        if (at0 && later) return fail(c, FM_ERR_INVALID, "%s: prev0 is NULL and only %d of %d active groups are at t = 0: start the groups at t = 0 in a call of their own", fn, at0, at0 + later);
+        boot0 = at0 ? 1 : 0;
+    }
+    if (const int rc = keep_pairs(c, st, inp)) return rc;
+    static const fm_step_scalars philox_step = [] { fm_step_scalars s{}; s.dfm_type = FM_DFM_CAMPBELL; s.noise_mode = FM_NOISE_PHILOX; return s; }();
+    return step_driver(c, st, state, n_steps, n_groups, mol_group, temb, prev0, dst_a, dst_b, nullptr, final_dst,
+                       [&](int i, const fm_dst*, const fm_step_scalars*& sc, const fm_step_noise*&, MixedStep& mixed) {
+        sc = &philox_step; mixed = {steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
+        return i == 0 ? boot0 : 0; }, keep_of);
 }
 
 int fm_set_tap(fm_ctx* c, const char* name, void* dst) {

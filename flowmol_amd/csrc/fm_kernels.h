@@ -1715,10 +1715,37 @@ struct FmCtmcFusedArgs {
     float* sink_x; float* sink_x1;
 };
 
+// Frozen rows (fm_ctmc_step_inpaint / fm_integrate_inpaint: replacement conditioning).  The step runs on every row as it always does; a row whose flag is set
+// then takes, in the store that writes the new state, the conditional path of the GIVEN molecule at the step's new time (fm_k_conditional_path's arithmetic
+// on that call's own tape: nothing is drawn here).  FmNoKeep: the instances of fm_ctmc_step / fm_integrate / fm_integrate_mixed, whose code is untouched.
+//   FmKeepMod (jobs 0..2)   tok = u < thr ? mask : tok1, thr = 1 - alpha_next of the modality; keep: per atom (a, c) or per pair (e: both atoms kept)
+//   FmKeepX (job 3)         x = (1 - ax) x0 + ax x1c, separately rounded; keep: per atom
+// alpha_next is workgroup-uniform; flags and path inputs are plain per-row loads behind the flag.
+struct FmNoKeep { static constexpr bool on = false; };
+struct FmKeepMod { static constexpr bool on = true; const unsigned char* keep; const int* tok1; const float* u; float thr; };
+struct FmKeepX { static constexpr bool on = true; const unsigned char* keep; const float* x0; const float* x1c; float ax; };
+struct FmKeepArgs {                 // a, c, e: keep[0] == keep[1] == the caller's keep_atom, keep[2] == keep_pair
+    const unsigned char* keep[3]; const int* tok1[3]; const float* u[3];
+    const float* x0; const float* x1c;
+    float alpha[4];                 // alpha_next of x, a, c, e (single-schedule kernels; the mixed kernel reads its group's row from memory)
+};
+__device__ __forceinline__ FmKeepMod fm_keep_mod(const FmKeepArgs& k, int job, float alpha) { return {k.keep[job], k.tok1[job], k.u[job], fm_sub_rn(1.0f, alpha)}; }
+__device__ __forceinline__ FmKeepX fm_keep_x(const FmKeepArgs& k, float ax) { return {k.keep[0], k.x0, k.x1c, ax}; }
+template <class KX>
+__device__ __forceinline__ float fm_keep_x_select(const KX& kx, int i, float xn) {
+    if constexpr (KX::on) { if (kx.keep[i / 3]) xn = fm_add_rn(fm_mul_rn(fm_sub_rn(1.0f, kx.ax), kx.x0[i]), fm_mul_rn(kx.ax, kx.x1c[i])); }
+    return xn;
+}
+template <class KP>
+__device__ __forceinline__ int fm_keep_tok_select(const KP& kp, int i, int K, int nt) {
+    if constexpr (KP::on) { if (kp.keep[i]) nt = kp.u[i] < kp.thr ? K : kp.tok1[i]; }
+    return nt;
+}
+
 // Job 3 of the fused CTMC kernels (campbell: fm_k_ctmc_fused, gat: fm_k_ctmc_gat_fused): the Euler step of one molecule's positions, the deferred COM removal of
 // the raw endpoint positions and the trajectory-sink stores.  A: the kernel's argument struct (x_t, x1, node_off, coef, dt, scale, x_raw, x1_out, sink_x, sink_x1).
-template <int NT, class A>
-__device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
+template <int NT, class A, class KX = FmNoKeep>
+__device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid, const KX& kx = KX{}) {
     const int n0 = a.node_off[mol], n1 = a.node_off[mol + 1];
     if (a.x_raw) {
         __shared__ float com[3];
@@ -1735,7 +1762,7 @@ __device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
             const float x1 = a.x_raw[i] - com[(i - n0 * 3) % 3];
             a.x1_out[i] = x1;
             const float vf = fm_mul_rn(a.coef, fm_sub_rn(x1, a.x_t[i]));
-            const float xn = fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale));
+            const float xn = fm_keep_x_select(kx, i, fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale)));
             a.x_t[i] = xn;
             if (a.sink_x) a.sink_x[i] = xn;
             if (a.sink_x1) a.sink_x1[i] = x1;
@@ -1745,7 +1772,7 @@ __device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
     for (int i = n0 * 3 + tid; i < n1 * 3; i += NT) {
         const float x1 = a.x1[i];
         const float vf = fm_mul_rn(a.coef, fm_sub_rn(x1, a.x_t[i]));
-        const float xn = fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale));
+        const float xn = fm_keep_x_select(kx, i, fm_add_rn(a.x_t[i], fm_mul_rn(fm_mul_rn(a.dt, vf), a.scale)));
         a.x_t[i] = xn;
         if (a.sink_x) a.sink_x[i] = xn;
         if (a.sink_x1) a.sink_x1[i] = x1;
@@ -1756,8 +1783,8 @@ __device__ __forceinline__ void fm_ctmc_x_job(const A& a, int mol, int tid) {
 // and a 47-atom molecule's 1081 pair rows are five dependent load-compute rounds of 256 threads but two of 1024 (one molecule: 13.9 -> 8 us per step)
 // Jobs 0..2: modality `job` (descriptor md) of molecule `mol`; the step's scalars are a's and md's.  One body for the kernel whose scalars are launch
 // arguments (fm_k_ctmc_fused) and the one that reads them per molecule from memory (fm_k_ctmc_fused_mixed)
-template <int NT>
-__device__ __forceinline__ void fm_ctmc_mod_job(const FmCtmcFusedArgs& a, const FmCtmcMod& md, int (&red)[2][NT / 64], int mol, int job, int tid) {
+template <int NT, class KP = FmNoKeep>
+__device__ __forceinline__ void fm_ctmc_mod_job(const FmCtmcFusedArgs& a, const FmCtmcMod& md, int (&red)[2][NT / 64], int mol, int job, int tid, const KP& kp = KP{}) {
     const int r0 = md.off[mol], r1 = md.off[mol + 1], K = md.K;
     const unsigned gid = a.philox ? (unsigned)a.mol_gid[mol] : 0u, ctr2 = (unsigned)a.step * 4u + (unsigned)job;
     int cm = 0, ch = 0;
@@ -1821,6 +1848,7 @@ __device__ __forceinline__ void fm_ctmc_mod_job(const FmCtmcFusedArgs& a, const 
         int nt = tok;
         if (!a.last_step) { if ((u2 < md.mask_prob) && !masked) nt = K; }
         if (will_unmask) nt = x1;
+        nt = fm_keep_tok_select(kp, i, K, nt);
         md.xt[i] = nt;
         md.x1[i] = x1;
         if (md.sink_t) md.sink_t[i] = nt;
@@ -1834,6 +1862,16 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused(FmCtmcFusedArgs a) {
     if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid); return; }
     const FmCtmcMod md = a.mod[job];
     fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid);
+}
+
+// fm_k_ctmc_fused with frozen rows (fm_ctmc_step_inpaint, fm_integrate_inpaint with one group): same grid, same bodies, the select on the stores
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_fused_keep(FmCtmcFusedArgs a, FmKeepArgs k) {
+    __shared__ int red[2][NT / 64];
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid, fm_keep_x(k, k.alpha[0])); return; }
+    const FmCtmcMod md = a.mod[job];
+    fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid, fm_keep_mod(k, job, k.alpha[1 + job]));
 }
 
 // Per-molecule time (fm_integrate_mixed): the campbell step of a batch whose molecules sit at different points of different schedules.  Molecule `mol`
@@ -1861,6 +1899,25 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_fused_mixed(FmCtmcMixedArgs m) {
     FmCtmcMod md = m.f.mod[job];
     md.unmask_prob = s.unmask_prob[job]; md.mask_prob = s.mask_prob[job];
     fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid);
+}
+
+// fm_k_ctmc_fused_mixed with frozen rows (fm_integrate_inpaint with several groups): alpha_next (n_groups, 4) is this call-step's row of the caller's device
+// array, read per group like the step scalars; an inactive group is skipped altogether, the overwrite included
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_fused_mixed_keep(FmCtmcMixedArgs m, FmKeepArgs k, const float* __restrict__ alpha_next) {
+    __shared__ int red[2][NT / 64];
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    const int g = m.mol_group[mol];
+    if (!m.active[g]) return;
+    const fm_step_scalars& s = m.steps[g];
+    FmCtmcFusedArgs a = m.f;
+    a.temp = s.cat_temperature; a.hc_thresh = s.hc_thresh; a.last_step = s.last_step;
+    a.coef = s.x_coef; a.dt = s.dt; a.scale = s.x_scale;
+    a.seed_lo = s.philox_seed_lo; a.seed_hi = s.philox_seed_hi; a.step = s.step_index;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid, fm_keep_x(k, alpha_next[g * 4])); return; }
+    FmCtmcMod md = m.f.mod[job];
+    md.unmask_prob = s.unmask_prob[job]; md.mask_prob = s.mask_prob[job];
+    fm_ctmc_mod_job<NT>(a, md, red, mol, job, tid, fm_keep_mod(k, job, alpha_next[g * 4 + 1 + job]));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1958,6 +2015,53 @@ __global__ void __launch_bounds__(NT) fm_k_ctmc_gat_fused(FmGatFusedArgs a) {
         md.x1[i] = amax;
         if (md.sink_t) md.sink_t[i] = best;
     }
+}
+// fm_k_ctmc_gat_fused with frozen rows: the kernel above, the select on its stores (a kernel of its own, so that the one above keeps its code)
+template <int NT>
+__global__ void __launch_bounds__(NT) fm_k_ctmc_gat_fused_keep(FmGatFusedArgs a, FmKeepArgs k) {
+    const int mol = blockIdx.x, job = blockIdx.y, tid = threadIdx.x;
+    if (job == 3) { fm_ctmc_x_job<NT>(a, mol, tid, fm_keep_x(k, k.alpha[0])); return; }
+    const FmGatMod md = a.mod[job];
+    const FmKeepMod kp = fm_keep_mod(k, job, k.alpha[1 + job]);
+    const int r0 = md.off[mol], r1 = md.off[mol + 1], K = md.K;
+    const unsigned gid = (unsigned)a.mol_gid[mol], ctr2 = (unsigned)a.step * 4u + (unsigned)job;
+    for (int i = r0 + tid; i < r1; i += NT) {
+        float q[16];
+        fm_philox_exp_row(q, K + 1, gid, (unsigned)(i - r0), ctr2, 0u, a.seed_lo, a.seed_hi);
+        int amax;
+        const int best = fm_keep_tok_select(kp, i, K, fm_gat_row(md.p + (size_t)i * K, K, md.xt[i], [&q](int k) { return q[k & 15]; }, a.temp, md.cf, md.cb, a.fw, a.bw, a.dt_cat, amax));
+        md.xt[i] = best;
+        md.x1[i] = amax;
+        if (md.sink_t) md.sink_t[i] = best;
+    }
+}
+
+// Tensor-noise gat steps with frozen rows (fm_ctmc_step_inpaint, fm_integrate_inpaint with one group): fm_k_x_step and fm_k_ctmc_gat, the select on their stores
+static __global__ void __launch_bounds__(256) fm_k_x_step_keep(float* __restrict__ x_t, const float* __restrict__ x1, float coef, float dt, float scale, int n3, FmKeepX kx) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n3) {
+        const float vf = fm_mul_rn(coef, fm_sub_rn(x1[i], x_t[i]));
+        x_t[i] = fm_keep_x_select(kx, i, fm_add_rn(x_t[i], fm_mul_rn(fm_mul_rn(dt, vf), scale)));
+    }
+}
+static __global__ void __launch_bounds__(256) fm_k_ctmc_gat_keep(FmGatArgs a, FmKeepMod kp) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.rows) return;
+    const float* qrow = a.q + (size_t)i * (a.K + 1);
+    int amax;
+    const int best = fm_gat_row(a.p + (size_t)i * a.K, a.K, a.xt[i], [qrow](int k) { return qrow[k]; }, a.temp, a.cf, a.cb, a.fw, a.bw, a.dt, amax);
+    a.xt[i] = fm_keep_tok_select(kp, i, a.K, best);
+    a.x1[i] = amax;
+}
+
+// keep_pair[u] = both atoms of pair u kept: once per fm_ctmc_step_inpaint / fm_integrate_inpaint call into the caller's (U) buffer, from the bound batch's
+// pair -> edge -> atom tables (p_e0: the pair's upper edge)
+static __global__ void __launch_bounds__(256) fm_k_keep_pairs(const unsigned char* __restrict__ keep_atom, unsigned char* __restrict__ keep_pair,
+                                                               const int* __restrict__ p_e0, const int* __restrict__ e_src, const int* __restrict__ e_dst, int U) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= U) return;
+    const int e = p_e0[u];
+    keep_pair[u] = (keep_atom[e_src[e]] && keep_atom[e_dst[e]]) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------

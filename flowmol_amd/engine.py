@@ -778,6 +778,91 @@ class Engine:
         self._keep = [state, prev, dst]
         return dst[final.value]
 
+    # ------------------------------------------------------------------ frozen atoms (replacement conditioning)
+    def inpaint_spec(self, x1_state, keep, seed: int) -> Dict[str, torch.Tensor]:
+        """The tensors of an ``fm_inpaint`` struct for the bound batch (and its molecule ids): ``keep`` (N,) marks the atoms of the given molecules
+        ``x1_state`` that stay as given.  'x0' and 'u_a' / 'u_c' / 'u_e' are the tape of ``conditional_path(x1_state, ..., seed, tape=True)`` (they do not
+        depend on alpha), 'x1c' the given positions after ``remove_com``, 'a1' / 'c1' / 'e1' copies of the given tokens, 'keep_pair' (U,) scratch that
+        every call fills.  ``x1_state`` is left untouched."""
+        d = self.device
+        k = torch.as_tensor(keep).detach().reshape(-1)
+        if k.shape[0] != self.N:
+            raise ValueError(f'keep has {k.shape[0]} entries, the bound batch {self.N} atoms')
+        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True)
+        return {'keep_atom': (k != 0).to(torch.uint8).to(d).contiguous(), 'keep_pair': torch.zeros(self.U, dtype=torch.uint8, device=d),
+                'x0': tape['x0'], 'x1c': self.remove_com(x1_state['x_t'].detach().to(d, torch.float32).contiguous().clone()),
+                'a1': x1_state['a_t'].detach().to(d, torch.int32).contiguous().clone(), 'c1': x1_state['c_t'].detach().to(d, torch.int32).contiguous().clone(),
+                'e1': x1_state['e_t'].detach().to(d, torch.int32).contiguous().clone(), 'u_a': tape['u_a'], 'u_c': tape['u_c'], 'u_e': tape['u_e']}
+
+    @staticmethod
+    def _inpaint_struct(spec) -> "_lib.fm_inpaint":
+        s = _lib.fm_inpaint()
+        for name, _ in _lib.fm_inpaint._fields_:
+            setattr(s, name, _ptr(spec[name]) if spec[name].numel() else None)      # a batch without pairs: empty pair tensors travel as NULL
+        return s
+
+    def ctmc_step_inpaint(self, state, dst, noise: Optional[StepNoise], sc: fm_step_scalars, spec, alpha_next, sampled: Optional[Dict[str, torch.Tensor]] = None):
+        """``ctmc_step`` with the frozen rows of ``spec`` (``inpaint_spec``) put back onto the given molecule's conditional path at ``alpha_next``
+        (4 values: alpha_t of x, a, c, e at the time the step arrives at) inside the step kernel (fm_ctmc_step_inpaint)."""
+        st, d, ip = self._state_struct(state), self._dst_struct(dst), self._inpaint_struct(spec)
+        nz = noise.c_struct() if noise is not None else None
+        smp = fm_sampled()
+        if sampled is not None:
+            smp.a1, smp.c1, smp.e1 = _ptr(sampled['a1']), _ptr(sampled['c1']), _ptr(sampled['e1'])
+        al = (C.c_float * 4)(*[float(v) for v in torch.as_tensor(alpha_next, dtype=torch.float32).reshape(-1).tolist()])
+        with self._dev():
+            rc = self.lib.fm_ctmc_step_inpaint(self._ctx, self._stream(), C.byref(st), C.byref(d), C.byref(nz) if nz is not None else None, C.byref(sc),
+                                               C.byref(smp), C.byref(ip), al)
+        self._check(rc, 'fm_ctmc_step_inpaint')
+        self._keep = [state, dst, noise, sampled, spec]
+        return state
+
+    def plan_alphas(self, plan: StepPlan) -> torch.Tensor:
+        """alpha_t (T, 4: x, a, c, e) at the time points of ``plan``: row i + 1 is the ``alpha_next`` of its step i."""
+        return alpha_tables(plan.t.clone(), self.cfg.schedule_type, self.cfg.cosine_params)[0]
+
+    def integrate_inpaint(self, state, plans: Sequence[StepPlan], mol_group, spec, start: Optional[Sequence[int]] = None, n_steps: Optional[int] = None,
+                          prev=None):
+        """``integrate_mixed`` with the frozen rows of ``spec`` (``inpaint_spec``): after every step the kept atoms -- and the pairs between two kept
+        atoms -- of every active molecule sit on the given molecule's conditional path at the step's new time point (fm_integrate_inpaint).  Arguments
+        and return value as in ``integrate_mixed``; one plan (``mol_group`` may then be None) runs the single-schedule step kernels, so gat plans pass."""
+        G = len(plans)
+        start = [0] * G if start is None else [int(v) for v in start]
+        left = [len(pl.scalars) - s0 for pl, s0 in zip(plans, start)]
+        if len(start) != G or min(left, default=0) < 0:
+            raise ValueError('start must give one step index inside its plan per group')
+        n = max(left, default=0) if n_steps is None else int(n_steps)
+        group = torch.zeros(self.B, dtype=torch.int32) if mol_group is None and G == 1 else torch.as_tensor(mol_group).detach().to('cpu', torch.int32).reshape(-1)
+        if group.shape[0] != self.B or (G and (int(group.min()) < 0 or int(group.max()) >= G)):
+            raise ValueError(f'mol_group must hold one group index in [0, {G}) per bound molecule')
+        if n <= 0:
+            return None
+        scal, act, temb = mixed_step_arrays(plans, start, n, self.cfg.time_embedding_dim)
+        tabs = [self.plan_alphas(pl) for pl in plans]
+        al = torch.zeros(n, G, 4)
+        for k in range(n):
+            for g in range(G):
+                if start[g] + k + 1 < tabs[g].shape[0]:
+                    al[k, g] = tabs[g][start[g] + k + 1]
+        al = al.contiguous()
+        d = self.device
+        scal_dev = torch.frombuffer(bytearray(bytes(scal)), dtype=torch.uint8).to(d)
+        act_dev = torch.tensor(list(act), dtype=torch.int32).to(d)
+        temb, group, al_dev = temb.to(d).contiguous(), group.to(d), al.to(d)
+        dst = [self.new_dst(), self.new_dst()]
+        ds = [self._dst_struct(dst[0]), self._dst_struct(dst[1])]
+        st, ip = self._state_struct(state), self._inpaint_struct(spec)
+        p = self._dst_struct(prev) if prev is not None else None
+        final = C.c_int(0)
+        with self._dev():
+            rc = self.lib.fm_integrate_inpaint(self._ctx, self._stream(), C.byref(st), n, G, scal, _ptr(scal_dev), act, _ptr(act_dev), _ptr(group), _ptr(temb), None,
+                                               C.byref(p) if p is not None else None, C.byref(ds[0]), C.byref(ds[1]), None, C.byref(final), C.byref(ip),
+                                               C.cast(C.c_void_p(al.data_ptr()), C.POINTER(C.c_float)), _ptr(al_dev))
+        self._check(rc, 'fm_integrate_inpaint')
+        self.synchronize()
+        self._keep = [state, prev, dst, spec]
+        return dst[final.value]
+
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):
         self._check(self.lib.fm_profile_enable(self._ctx, int(on)), 'fm_profile_enable')
@@ -793,8 +878,13 @@ class IntegrationRun:
     step's prediction, so a trajectory can be advanced in several fm_integrate calls (bench.py times a
     window of steps; Engine.integrate runs them all)."""
 
-    def __init__(self, eng: Engine, state, plan: StepPlan, noise_for_step, traj=None):
+    def __init__(self, eng: Engine, state, plan: StepPlan, noise_for_step, traj=None, inpaint=None):
+        """``inpaint``: the spec of ``Engine.inpaint_spec`` -- every step then freezes its rows (fm_integrate_inpaint with one group, which keeps
+        the trajectory sink and the noise callback); None: fm_integrate."""
         self.eng, self.state, self.plan, self.noise_for_step, self.traj = eng, state, plan, noise_for_step, traj
+        self.inpaint = inpaint
+        self._ip = eng._inpaint_struct(inpaint) if inpaint is not None else None
+        self._alphas = eng.plan_alphas(plan) if inpaint is not None else None
         tt = eng.cfg.time_embedding_dim
         self.temb_all = (torch.stack([time_embedding_host(sc.t, tt) for sc in plan.scalars]) if plan.scalars
                          else torch.zeros(0, tt)).to(eng.device).contiguous()      # n_timesteps = 1: no step, the prior is the result
@@ -839,12 +929,18 @@ class IntegrationRun:
                 for name in ('x', 'a', 'c', 'e', 'x1', 'a1', 'c1', 'e1'):
                     tsr = self.traj.get(name)
                     setattr(sink, name, _ptr(tsr[a:]) if tsr is not None else None)
+            prev = C.byref(self._dsts[self.prev_idx]) if self.prev_idx is not None else None
             with eng._dev():
-                rc = eng.lib.fm_integrate(eng._ctx, eng._stream(), C.byref(self._st), k, scal, _ptr(self.temb_all[a:]), nzs,
-                                          C.byref(self._dsts[self.prev_idx]) if self.prev_idx is not None else None,
-                                          C.byref(self._dsts[0]), C.byref(self._dsts[1]),
-                                          C.byref(sink) if sink is not None else None, C.byref(final))
-            eng._check(rc, 'fm_integrate')
+                if self._ip is None:
+                    rc = eng.lib.fm_integrate(eng._ctx, eng._stream(), C.byref(self._st), k, scal, _ptr(self.temb_all[a:]), nzs, prev,
+                                              C.byref(self._dsts[0]), C.byref(self._dsts[1]),
+                                              C.byref(sink) if sink is not None else None, C.byref(final))
+                else:
+                    al = (C.c_float * (4 * k))(*self._alphas[a + 1:b + 1].reshape(-1).tolist())
+                    rc = eng.lib.fm_integrate_inpaint(eng._ctx, eng._stream(), C.byref(self._st), k, 1, scal, None, None, None, None, _ptr(self.temb_all[a:]), nzs, prev,
+                                                      C.byref(self._dsts[0]), C.byref(self._dsts[1]),
+                                                      C.byref(sink) if sink is not None else None, C.byref(final), C.byref(self._ip), al, None)
+            eng._check(rc, 'fm_integrate' if self._ip is None else 'fm_integrate_inpaint')
             self.prev_idx = final.value
             # bound the noise kept alive: a chunk's tensors are released once the GPU has passed the event recorded behind it.  The host waits for
             # the chunk BEFORE the previous one only, so two chunks stay enqueued and the device never idles (a device-wide synchronise here

@@ -332,7 +332,7 @@ class FlowMol:
     # ------------------------------------------------------------------ resampling given molecules
     @torch.no_grad()
     def resample(self, molecules, start_step, n_timesteps=None, seed=None, mol_ids=None, stochasticity=None, high_confidence_threshold=None,
-                 return_tensors=False, xt_traj=False, ep_traj=False, **kwargs):
+                 return_tensors=False, xt_traj=False, ep_traj=False, keep=None, **kwargs):
         """Variations of given molecules (no reference entry point; its parts are the reference's): molecule *i* is noised back to time point
         ``k = start_step[i]`` of its ``T = n_timesteps[i]``-point schedule, ``t = linspace(0, 1, T)[k]``, with the model's own corruption process
         (CTMCVectorField.sample_conditional_path, ctmc_vector_field.py:97-143: the distribution the network was trained on), and then takes steps
@@ -345,7 +345,15 @@ class FlowMol:
         (at most 32 distinct pairs per call).  Noise is Philox only: ``seed`` is required, ``mol_ids`` (default 0..B-1) name the streams.  Molecule *i*
         is, bit for bit, ``resample([mol_i], start_step[i], n_timesteps[i], seed, mol_ids=[id_i])``.  ``xt_traj`` / ``ep_traj`` (one (T, k) for all
         molecules only) record T - k frames, frame 0 being the corrupted state.  Raises NotImplementedError for endpoint models, ``tspan``, dfm_type
-        'gat' with a per-molecule argument, trajectories with several (T, k) pairs and more than 32 of those; ``return_tensors`` as in ``sample``."""
+        'gat' with a per-molecule argument, trajectories with several (T, k) pairs and more than 32 of those; ``return_tensors`` as in ``sample``.
+
+        ``keep`` (frozen atoms, replacement conditioning): a bool tensor over the concatenated atoms, or a list with one bool sequence per molecule,
+        marking the atoms -- fake atoms included -- that stay exactly as given while the model regenerates the rest (scaffold decoration, linker design).
+        Every step runs on the whole molecule as always; then the kept atoms (position, type, charge) and the bonds between two kept atoms are put back
+        onto the given molecule's conditional path at the new time, inside the step kernel, so the network always sees the kept part at the noise level it
+        was trained on.  On models with alpha(1) = 1 the kept rows of the result are the CENTRED input rows bit for bit; the result is not re-centred:
+        its frame is that of the given molecule.  A bond with one free atom is free.  ``None`` or all-False is the call without ``keep``.  Sharding
+        across ranks and the command line do not take ``keep``."""
         cfg = self.cfg
         # ---- arguments: every refusal before the bind and before anything is enqueued; no generator is touched
         if cfg.parameterization == 'endpoint':
@@ -365,6 +373,7 @@ class FlowMol:
             raise NotImplementedError("resample with per-molecule start_step / n_timesteps: dfm_type 'gat' is not supported")
         x1, n_atoms = self._given_molecules(molecules)
         B = int(n_atoms.numel())
+        keep = _keep_atoms(keep, n_atoms)
         ks = [int(start_step)] * B if ks is None else ks
         Ts = [int(self.default_n_timesteps if n_timesteps is None else n_timesteps)] * B if Ts is None else Ts
         if len(ks) != B or len(Ts) != B:
@@ -386,6 +395,7 @@ class FlowMol:
         alphas = {(T, k): alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k] for T, k in pairs}
         sizes = n_atoms.tolist()
         given = _split_molecules(x1, sizes)
+        kept = torch.split(keep, sizes) if keep is not None else None
         # ---- the library refuses a NULL previous endpoint with only some groups at t = 0: molecules that start at step 0 run in an engine call of their own
         parts = [[i for i in range(B) if ks[i] == 0], [i for i in range(B) if ks[i] > 0]]
         parts = [p for p in parts if p]
@@ -399,15 +409,18 @@ class FlowMol:
             keys = sorted({(Ts[i], ks[i]) for i in part})
             group = [keys.index((Ts[i], ks[i])) for i in part]
             state = eng.conditional_path(st1, torch.stack([alphas[key] for key in keys]), group if len(keys) > 1 else None, seed=int(seed))
+            spec = eng.inpaint_spec(st1, torch.cat([kept[i] for i in part]), int(seed)) if kept is not None else None
             t0 = time.perf_counter()
             if len(keys) == 1:
                 (T, k), traj, init = keys[0], None, None
                 if visualize:
                     traj, init = eng.new_traj(T - 1), _tokens(state, copy=True)
-                IntegrationRun(eng, state, plans[T], None, traj=traj).run(k, T - 1)
+                IntegrationRun(eng, state, plans[T], None, traj=traj, inpaint=spec).run(k, T - 1)
                 eng.synchronize()
                 if visualize:
                     frames = _frames_of(init, {f: v[k:] for f, v in traj.items()})
+            elif spec is not None:
+                eng.integrate_inpaint(state, [plans[T] for T, _ in keys], group, spec, start=[k for _, k in keys])
             else:
                 eng.integrate_mixed(state, [plans[T] for T, _ in keys], group, start=[k for _, k in keys])
                 eng.synchronize()
@@ -420,6 +433,10 @@ class FlowMol:
         if len(parts) > 1:
             final = {f: torch.cat([results[i][f] for i in range(B)]).contiguous() for f in ('x_t', 'a_t', 'c_t', 'e_t')}
         return self._finish(final, n_atoms, frames if not return_tensors else None, return_tensors, False, xt_traj, ep_traj, t_integrate)
+
+    def inpaint(self, molecules, keep, n_timesteps=None, seed=None, mol_ids=None, **kwargs):
+        """Generate the free atoms of ``molecules`` from the prior around the kept ones: ``resample(molecules, 0, n_timesteps, keep=keep, ...)``."""
+        return self.resample(molecules, 0, n_timesteps, seed=seed, mol_ids=mol_ids, keep=keep, **kwargs)
 
     def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
         """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --
@@ -713,6 +730,34 @@ ALLOWED_KWARGS = {
 
 
 RESAMPLE_KWARGS = {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'}       # resample(): Philox only, so no rng and no noise hooks
+
+
+def _keep_atoms(keep, n_atoms: torch.Tensor) -> Optional[torch.Tensor]:
+    """``keep`` of resample() / submit_from() as one bool tensor over the concatenated atoms, or None when nothing is kept.  ValueError for anything but a
+    bool tensor of N entries or one bool sequence per molecule, each of the molecule's length."""
+    if keep is None:
+        return None
+    sizes = n_atoms.tolist()
+    if torch.is_tensor(keep):
+        if keep.dtype != torch.bool:
+            raise ValueError(f'keep must be a bool tensor, got {keep.dtype}')
+        flat = keep.detach().cpu().reshape(-1)
+    else:
+        rows = list(keep)
+        if len(rows) != len(sizes):
+            raise ValueError(f'keep has {len(rows)} entries for {len(sizes)} molecules (one bool sequence per molecule)')
+        cols = []
+        for i, (r, n) in enumerate(zip(rows, sizes)):
+            r = r.detach().cpu().reshape(-1) if torch.is_tensor(r) else torch.as_tensor(list(r))
+            if r.numel() != n:
+                raise ValueError(f'keep[{i}] has {r.numel()} entries, molecule {i} has {n} atoms')
+            if r.dtype != torch.bool:
+                raise ValueError(f'keep[{i}] must hold bools, got {r.dtype}')
+            cols.append(r)
+        flat = torch.cat(cols)
+    if flat.numel() != sum(sizes):
+        raise ValueError(f'keep has {flat.numel()} entries, the molecules have {sum(sizes)} atoms')
+    return flat if bool(flat.any()) else None
 
 
 def _split_molecules(state: Dict[str, torch.Tensor], sizes) -> List[Dict[str, torch.Tensor]]:

@@ -14,15 +14,18 @@ import torch
 
 from . import _lib
 from .engine import IntegrationRun, alpha_tables, make_step_plan
+from .model import _keep_atoms
 
 
 class _Request:
-    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev', 'given')
+    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev', 'given', 'keep', 'spec')
 
-    def __init__(self, ticket, n, T, mol_id, start=0, given=None):
+    def __init__(self, ticket, n, T, mol_id, start=0, given=None, keep=None):
         self.ticket, self.n, self.T, self.mol_id = ticket, n, T, mol_id
         self.pos = start      # the step it takes next: steps taken, or where a given molecule (submit_from) enters its schedule
         self.given = given    # submit_from: the molecule to corrupt {'x_t', 'a_t', 'c_t', 'e_t'} (CPU); None: start from the prior
+        self.keep = keep      # submit_from(keep=...): (n,) bool, the atoms that stay as given; None: nothing frozen
+        self.spec = None      # its rows of Engine.inpaint_spec, on the device, from admission on
         self.state = None     # {'x_t', 'a_t', 'c_t', 'e_t'}: this molecule's rows, on the device
         self.prev = None      # {'x', 'a', 'c', 'e'}: its previous endpoint prediction
 
@@ -61,13 +64,16 @@ class SamplingQueue:
             tickets.append(t)
         return tickets
 
-    def submit_from(self, molecules, start_step, n_timesteps=None, mol_ids=None) -> List[int]:
+    def submit_from(self, molecules, start_step, n_timesteps=None, mol_ids=None, keep=None) -> List[int]:
         """Queue given molecules for resampling (``FlowMol.resample``): molecule *i* is corrupted to time point ``start_step[i]`` of its
         ``n_timesteps[i]``-point schedule at admission and joins the running batch from there; ``start_step >= n_timesteps - 1`` retires at once with the
         corrupted state.  ``molecules`` / ``start_step`` / ``n_timesteps`` / ``mol_ids`` as in ``resample`` (ids default to the ticket numbers).  Every
-        molecule is, bit for bit, ``model.resample([mol], start_step, n_timesteps, seed, mol_ids=[id])``."""
+        molecule is, bit for bit, ``model.resample([mol], start_step, n_timesteps, seed, mol_ids=[id])``.  ``keep``: the atoms that stay as given, as in
+        ``resample`` -- such molecules are admitted into the running batch like any other and are, bit for bit, their ``resample(..., keep=...)`` run alone."""
         x1, n_atoms = self.model._given_molecules(molecules)
         sizes = n_atoms.tolist()
+        keep = _keep_atoms(keep, n_atoms)
+        kept = torch.split(keep, sizes) if keep is not None else [None] * len(sizes)
         B = len(sizes)
         per = lambda v, default: ([int(default if v is None else v)] * B if v is None or isinstance(v, int) or (torch.is_tensor(v) and v.dim() == 0)
                                   else [int(x) for x in v])
@@ -83,7 +89,8 @@ class SamplingQueue:
         for i in range(B):
             t = self._next_ticket
             self._next_ticket += 1
-            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1}))
+            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1},
+                                          kept[i] if kept[i] is not None and bool(kept[i].any()) else None))
             tickets.append(t)
         return tickets
 
@@ -108,6 +115,25 @@ class SamplingQueue:
         cols = {k: torch.split(v, pairs if k == pair_key else sizes) for k, v in d.items()}
         return [{k: cols[k][i] for k in d} for i in range(len(sizes))]
 
+    @staticmethod
+    def _split_spec(spec, sizes):
+        """The per-molecule rows of an ``Engine.inpaint_spec`` dict (views)."""
+        pairs = [n * (n - 1) // 2 for n in sizes]
+        cols = {k: torch.split(v, pairs if k in ('keep_pair', 'e1', 'u_e') else sizes) for k, v in spec.items()}
+        return [{k: cols[k][i] for k in spec} for i in range(len(sizes))]
+
+    def _batch_spec(self, run):
+        """The running batch's spec from its molecules' rows; a molecule without frozen atoms contributes zero flags (its other rows are never read)."""
+        if all(r.spec is None for r in run):
+            return None
+        dev = self.model.engine.device
+        shapes = {'keep_atom': (torch.uint8, lambda n, u: (n,)), 'keep_pair': (torch.uint8, lambda n, u: (u,)), 'x0': (torch.float32, lambda n, u: (n, 3)),
+                  'x1c': (torch.float32, lambda n, u: (n, 3)), 'a1': (torch.int32, lambda n, u: (n,)), 'c1': (torch.int32, lambda n, u: (n,)),
+                  'e1': (torch.int32, lambda n, u: (u,)), 'u_a': (torch.float32, lambda n, u: (n,)), 'u_c': (torch.float32, lambda n, u: (n,)),
+                  'u_e': (torch.float32, lambda n, u: (u,))}
+        return {k: torch.cat([r.spec[k] if r.spec is not None else torch.zeros(shp(r.n, r.n * (r.n - 1) // 2), dtype=dt, device=dev) for r in run]).contiguous()
+                for k, (dt, shp) in shapes.items()}
+
     def _admit(self):
         """Newcomers, grouped by schedule and entry step, take their first step through fm_integrate on a bind of their own -- from the prior (step 0:
         bootstrap evaluation, first step) or, for given molecules, from their conditional path (step k, no previous endpoint) -- then they join the
@@ -126,24 +152,28 @@ class SamplingQueue:
             by_key.setdefault((r.T, r.pos, r.given is not None), []).append(r)
         self._pending = keep
         for (T, k, given), reqs in by_key.items():
-            sizes = [r.n for r in reqs]
+            sizes, spec = [r.n for r in reqs], None
             eng.bind(torch.tensor(sizes))
             eng.set_molecule_ids(torch.tensor([r.mol_id for r in reqs]))
             if given:
                 x1 = {f: torch.cat([r.given[f] for r in reqs]) for f in ('x_t', 'a_t', 'c_t', 'e_t')}
                 alpha = alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k]
-                state = eng.conditional_path(eng.make_state(x1['x_t'], x1['a_t'], x1['c_t'], x1['e_t']), alpha, seed=self.seed)
+                st1 = eng.make_state(x1['x_t'], x1['a_t'], x1['c_t'], x1['e_t'])
+                state = eng.conditional_path(st1, alpha, seed=self.seed)
+                if any(r.keep is not None for r in reqs):
+                    spec = eng.inpaint_spec(st1, torch.cat([r.keep if r.keep is not None else torch.zeros(r.n, dtype=torch.bool) for r in reqs]), self.seed)
             else:
                 state = eng.prior_state(eng.prior_philox(self.seed))
             prev = None
             if k < T - 1:
-                run = IntegrationRun(eng, state, self._plan(T), None)
+                run = IntegrationRun(eng, state, self._plan(T), None, inpaint=spec)
                 run.run(k, k + 1)
                 prev = run.last_dst()
             eng.synchronize()
             st, pv = self._split(state, sizes, 'e_t'), (self._split(prev, sizes, 'e') if prev is not None else [None] * len(reqs))
-            for r, s_, p_ in zip(reqs, st, pv):
-                r.state, r.prev, r.pos, r.given = s_, p_, min(k + 1, T - 1), None
+            sp = self._split_spec(spec, sizes) if spec is not None else [None] * len(reqs)
+            for r, s_, p_, q_ in zip(reqs, st, pv, sp):
+                r.state, r.prev, r.pos, r.given, r.spec = s_, p_, min(k + 1, T - 1), None, (q_ if r.keep is not None else None)
                 (self._running if r.pos < T - 1 else self._done).append(r)
 
     def _retire(self, reqs):
@@ -174,8 +204,12 @@ class SamplingQueue:
         keys = sorted({(r.T, r.pos) for r in run})
         state = {f: torch.cat([r.state[f] for r in run]).contiguous() for f in ('x_t', 'a_t', 'c_t', 'e_t')}
         prev = {f: torch.cat([r.prev[f] for r in run]).contiguous() for f in 'xace'}
-        dst = eng.integrate_mixed(state, [self._plan(T) for T, _ in keys], [keys.index((r.T, r.pos)) for r in run],
-                                  start=[pos for _, pos in keys], n_steps=k, prev=prev)
+        spec = self._batch_spec(run)
+        plans, group, start = [self._plan(T) for T, _ in keys], [keys.index((r.T, r.pos)) for r in run], [pos for _, pos in keys]
+        if spec is not None:
+            dst = eng.integrate_inpaint(state, plans, group, spec, start=start, n_steps=k, prev=prev)
+        else:
+            dst = eng.integrate_mixed(state, plans, group, start=start, n_steps=k, prev=prev)
         still = []
         for r, s_, p_ in zip(run, self._split(state, sizes, 'e_t'), self._split(dst, sizes, 'e')):
             r.state, r.prev, r.pos = s_, p_, min(r.pos + k, r.T - 1)

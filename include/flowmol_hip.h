@@ -26,6 +26,8 @@
  *   fm_denoising_loss   the part of FlowMol.forward after sample_conditional_path, flowmol/models/flowmol.py:339-413: one evaluation on logits
  *                       (vector_field.py:217 apply_softmax=False, remove_com=False), CrossEntropyLoss / MSELoss row terms, per-molecule sums
  *   fm_distort_philox   the geometry distortion of FlowMol.forward, flowmol.py:333-337, from the per-molecule counter-based streams
+ *   fm_ctmc_step_inpaint, fm_integrate_inpaint   fm_ctmc_step / fm_integrate / fm_integrate_mixed with frozen atoms (replacement conditioning; no reference entry
+ *                       point): after every step the kept rows are put back onto sample_conditional_path (ctmc_vector_field.py:97-143) of the given molecule
  *
  * Conventions
  *   - every function returns 0 on success or a negative fm_status; the message is available from
@@ -58,7 +60,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 11
+#define FM_ABI_VERSION 12
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -382,6 +384,46 @@ int fm_denoising_loss(fm_ctx* ctx, void* stream, const fm_state* xt, const fm_st
 typedef struct fm_distort_tape { float* z; float* u; } fm_distort_tape;
 int fm_distort_philox(fm_ctx* ctx, void* stream, uint64_t seed, float p, int n_groups, const int32_t* mol_group,
                       const int32_t* group_on /* DEVICE (n_groups) */, float* x, const fm_distort_tape* tape);
+
+/* --- ABI 12: frozen atoms (replacement conditioning) -- keep a scaffold or fragment of a given molecule exactly as given and let the model regenerate the rest.
+ * A step of the calls below is EXACTLY the step of fm_ctmc_step / fm_integrate / fm_integrate_mixed on all rows: frozen rows take part in the purity counts like
+ * any row, the sampled endpoint tokens (fm_sampled, the sink's a1 / c1 / e1 / x1 frames) and every draw are those of the plain step.  Then, inside the store
+ * that writes the new state, every frozen row is set to the conditional path of the given molecule at the step's NEW time point:
+ *   an atom row (x, a, c) is frozen iff keep_atom[atom] != 0; a pair row (e, upper-triangle order) iff BOTH its atoms are kept; a pair with one free atom is free;
+ *   positions   x = (1 - ax) x0 + ax x1c, the three operations rounded separately (fm_conditional_path's arithmetic)
+ *   tokens      tok = u < 1 - alpha ? mask token : tok1
+ *   alpha_next = alpha_t of x, a, c, e at the time the step ARRIVES at (alpha_tables(linspace(0, 1, T))[0][i + 1] for step i of a T-point schedule).
+ * x0, x1c, a1 / c1 / e1 and u_a / u_c / u_e are INPUTS: what fm_conditional_path(seed, x1, ..., tape) consumed (tape.x0, tape.u_*), x1's tokens, and x1's positions
+ * after fm_remove_com.  The step kernels draw nothing new, so after step i the frozen rows equal the frozen rows of fm_conditional_path at alpha_next -- a monotone
+ * unmasking, u being fixed per row -- and with alpha(1) = 1 the frozen atoms of the result are x1c bit for bit: the result is NOT re-centred, its frame is the given
+ * molecule's.  The sink's frame of the new state (x, a, c, e) shows the overwritten rows.  With no atom kept the calls give the bits of the plain entry points.
+ * keep_pair is caller-owned scratch of U bytes that every call fills from keep_atom with one small launch; everything else of the struct is only read.
+ * Neither call synchronises or allocates, and no workspace beyond the bind's is needed.  FM_ERR_INVALID, with a message and before anything is enqueued, for an
+ * endpoint model, a NULL member (keep_pair / e1 / u_e may be NULL only in a batch without pairs), and a member equal to a pointer of state, dst / dst_a / dst_b,
+ * sampled or the sink. */
+typedef struct fm_inpaint {
+    const uint8_t* keep_atom;     /* (N) one flag per atom of the bound batch, fake atoms included */
+    uint8_t* keep_pair;           /* (U) filled by the call */
+    const float* x0;              /* (N,3) position prior of the path (fm_cond_tape.x0) */
+    const float* x1c;             /* (N,3) given positions minus the whole molecule's mean (fm_remove_com) */
+    const int32_t* a1; const int32_t* c1;      /* (N) given tokens, real categories */
+    const int32_t* e1;            /* (U) */
+    const float* u_a; const float* u_c;        /* (N) uniforms of the path (fm_cond_tape.u_a / u_c) */
+    const float* u_e;             /* (U) */
+} fm_inpaint;
+/* fm_ctmc_step with frozen rows: one step, campbell or gat, either noise mode.  alpha_next: HOST, 4 floats. */
+int fm_ctmc_step_inpaint(fm_ctx* ctx, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
+                         const fm_sampled* sampled, const fm_inpaint* inp, const float* alpha_next);
+/* fm_integrate_mixed with frozen rows; alpha_next / alpha_next_dev: the (n_steps, n_groups, 4) alpha_next of every call-step and group on the HOST and in DEVICE
+ * memory (the per-molecule-time kernel reads its group's row like the step scalars; an inactive group is skipped altogether, the overwrite included).
+ * n_groups == 1 is fm_integrate with frozen rows instead: gat steps, FM_NOISE_TENSORS (noise: host array of n_steps fm_step_noise, else NULL) and a trajectory
+ * sink are accepted, the single-schedule step kernels run, and steps_dev / active / active_dev / mol_group / alpha_next_dev are not read (may be NULL).
+ * n_groups > 1 keeps fm_integrate_mixed's refusals (gat, tensor noise, a sink, prev0 == NULL with only some groups at t = 0) and does not read noise.
+ * FM_ERR_INVALID also for n_groups outside 1..32. */
+int fm_integrate_inpaint(fm_ctx* ctx, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                         const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                         const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                         const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
