@@ -9,6 +9,7 @@
 
 #include "../../include/flowmol_hip.h"      // fm_step_scalars: the mixed CTMC kernel reads the caller's per-(step, group) array as it is
 #include "fm_device.h"
+#include "fm_tile_desc.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch descriptor (all device pointers; built by fm_k_batch_setup from the per-molecule offsets)
@@ -29,7 +30,8 @@ struct FmBatch {
     int* p_e1;               // [U]  internal edge id of (src=b -> dst=a)        ("lower" edge)
     int* pair_mol;           // [U]
     const int* mol_tile_off; // [B+1] first edge-message tile of every molecule (host-computed: sum of ceil(n (n - 1) / tile_rows))
-    int4* tile_desc;         // [n_tiles] {first edge row, rows that exist (1 .. tile_rows), the molecule's first edge row, molecule}
+    int4* tile_desc;         // [n_tiles] packed FmTile (fm_tile_desc.h): first edge row, rows that exist (1 .. tile_rows), and the molecule's first edge row, atom count,
+                             // first node and the destination of the tile's first row -- all a row needs to know its endpoints
 };
 
 // CANONICAL AGGREGATION ORDER (round 6).  In the reference a molecule's result is a function of the molecule and its noise rows only: every reduction is per
@@ -76,7 +78,10 @@ static __global__ void __launch_bounds__(256) fm_k_batch_setup(FmBatch b) {
         const int moff = b.mol_edge_off[lo];
         const int e0 = moff + (gid - b.mol_tile_off[lo]) * b.tile_rows;
         const int left = b.mol_edge_off[lo + 1] - e0;
-        b.tile_desc[gid] = make_int4(e0, left < b.tile_rows ? left : b.tile_rows, moff, lo);
+        const int noff = b.mol_node_off[lo], n = b.mol_node_off[lo + 1] - noff;
+        int4 d;
+        fm_tile_encode(FmTile{e0, left < b.tile_rows ? left : b.tile_rows, moff, n, noff, (e0 - moff) / (n - 1)}, d.x, d.y, d.z, d.w);
+        b.tile_desc[gid] = d;
     }
 }
 
@@ -739,8 +744,14 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
     // into one L2 instead of all eight.
     const int tile = a.xcd_chunk > 0 ? (int)(blockIdx.x & 7) * a.xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (tile >= a.b.n_tiles) return;  // padding workgroups of the chunked grid (uniform exit, before any barrier)
-    const int4 td = a.b.tile_desc[tile];      // wave-uniform: one scalar load
-    const int e0 = td.x, left = td.y, moff = td.z;      // first row, rows that exist, the molecule's first row (e0 - moff is a multiple of TM)
+    const int4 tdp = a.b.tile_desc[tile];     // wave-uniform: one scalar load
+    const FmTile td = fm_tile_decode(tdp.x, tdp.y, tdp.z, tdp.w);
+    [[maybe_unused]] const int e0 = td.e0, left = td.left, moff = td.moff;      // first row, rows that exist, the molecule's first row (e0 - moff is a multiple of TM)
+    // ENTRY (f32 tiles of 16 / 32 rows): a thread fills ONE row of the tile, r = (tid / 16) % TM, and computes that row's endpoints from the descriptor
+    // (fm_tile_row: the edge order is closed-form), so its x / PV gathers leave right behind the descriptor load instead of behind the e_src / e_dst loads
+    // of wave 0, an LDS round trip and a barrier that waited for all of them.  Every value is formed by the expression the other instances use.
+    // The 64-row tiles (two rows per thread, one workgroup per CU: A/B only) and the split-precision instances (opt-in) keep the indexed start-up.
+    constexpr bool ENTRY = SP == 0 && TM <= 32 && NTH == 512;
     FM_MARK_DECL
     // (A) the edge-feature rows depend only on the tile index: request them before anything else (HBM latency)
     constexpr int NEF = PQ ? 1 : TM * 32 / NTH;
@@ -751,18 +762,56 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
         for (int k = 0; k < NEF; ++k) efv[k] = (FM_ABLATE & 16) ? make_float4(0.1f, 0.2f, 0.3f, 0.4f) : fm_buf_f32x4(rs, tid * 16 + k * NTH * 16, 0);
     }
     // (B) endpoints and geometry of the tile's edges
+    constexpr int QN = NTH / 16;             // 16-lane groups of the workgroup
+    const int q = tid >> 4, j = tid & 15;
+    [[maybe_unused]] const int er_row = q % TM;                                                            // ENTRY: this thread's row
+    [[maybe_unused]] const int er_half = ENTRY && QN > TM ? __builtin_amdgcn_readfirstlane(q / TM) : 0;    // ... and which of the QN / TM groups that share it (wave-uniform)
+    [[maybe_unused]] const float er_inv = __builtin_amdgcn_rcpf((float)(td.n - 1));
+    [[maybe_unused]] const bool er_live = er_row < left;
+    [[maybe_unused]] FmTileRow er{-1, -1, 0, 0};
+    if constexpr (ENTRY) er = fm_tile_row(td, er_inv, er_row);
     if (PQ && tid < 64) {
         // PQ: byte offsets of the rows' pairs in Q, relative to the tile's smallest pair id (a wave-wide min: the tile's pairs lie within a few
         // molecules, so the relative offsets stay far below the 31-bit limit of a buffer offset however large the batch's Q table is)
-        const int e = e0 + tid;
-        const int pr = tid < left ? a.b.e_pair[e] : 0x7fffffff;
+        [[maybe_unused]] const int e = e0 + tid;
+        int pr = 0x7fffffff;
+        if constexpr (ENTRY) { const int t = fm_tile_row(td, er_inv, tid).pair; pr = tid < left ? t : pr; }
+        else if (tid < left) pr = a.b.e_pair[e];
         int mn = pr;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_xor(mn, o); mn = t < mn ? t : mn; }
         if (tid < TM) m_doff[tid] = pr != 0x7fffffff ? (pr - mn) * 1024 : FM_BUF_OOB;
         if (tid == 0) m_doff[TM] = mn;
     }
-    if (tid < TM) {
+    // ENTRY: the thread's own requests, all behind the one scalar load: x[src], x[dst], PV[src] (+ PVd[dst]) of its row and its columns of w0
+    typedef FmGvpTile<V, TM, HX> TT;
+    constexpr int PVW_ = TT::PVW, CB_ = PVW_ / 16, NCH_ = 3 * CB_ * TM, NP_ = ENTRY ? (NCH_ + QN - 1) / QN : 1;
+    [[maybe_unused]] float e_pv[NP_], e_w0[NP_], e_xs[3], e_xd[3];
+    if constexpr (ENTRY) {
+        static_assert(QN % TM == 0, "every 16-lane group fills one row");
+        const auto rx = fm_buf(a.x, (unsigned)a.b.N * 12u);
+        const int xs = er_live ? er.src * 12 : FM_BUF_OOB, xd = er_live ? er.dst * 12 : FM_BUF_OOB;      // rows without an edge read 0
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { e_xs[c] = fm_buf_f32(rx, xs, c * 4); e_xd[c] = fm_buf_f32(rx, xd, c * 4); }
+        const auto rs = fm_buf(a.PV, (unsigned)a.b.N * (unsigned)(3 * PVW_ * 4));
+        const auto rsd = fm_buf(HX > 0 ? a.PVd : a.PV, (unsigned)a.b.N * (unsigned)(3 * PVW_ * 4));
+        const int svo = er_live ? er.src * (3 * PVW_ * 4) + j * 4 : FM_BUF_OOB, dvo = er_live ? er.dst * (3 * PVW_ * 4) + j * 4 : FM_BUF_OOB;
+#pragma unroll
+        for (int p_ = 0; p_ < NP_; ++p_) {
+            const int ccb = er_half + p_ * (QN / TM), c = ccb / CB_, cb = ccb % CB_;      // chunk = (xyz c, 16-column block cb) of the row; wave-uniform
+            const bool in = NCH_ % QN == 0 || ccb < 3 * CB_;
+            e_pv[p_] = (FM_ABLATE & 16) ? 0.5f : fm_buf_f32(rs, in ? svo : FM_BUF_OOB, (c * PVW_ + cb * 16) * 4);
+            if (HX > 0) e_pv[p_] += fm_buf_f32(rsd, in ? dvo : FM_BUF_OOB, (c * PVW_ + cb * 16) * 4);      // v_dst_msg[dst] * Wh / Wcp rows of the destination vectors, hoisted per node like PV
+            e_w0[p_] = a.w0[cb * 16 + j];
+        }
+        // one lane per row publishes what other threads need of it: the Ps / Q gathers below (row map of the accumulators), the aggregation, the debug taps
+        // (m_geo stays unwritten here: the geometry never leaves the thread's registers)
+        if (j == 0 && q < TM) {
+            m_src[q] = er_live ? er.src : -1; m_dst[q] = er_live ? er.dst : -1; m_piece[q] = er_live ? er.piece : 0;
+            m_soff[q] = er_live ? er.src * 1024 : FM_BUF_OOB;
+            if (!PQ) m_doff[q] = er_live ? er.dst * 1024 : FM_BUF_OOB;
+        }
+    } else if (tid < TM) {
         const int e = e0 + tid;
         int s = -1, d = -1, piece = 0;
         float gx = 0.f, gy = 0.f, gz = 0.f, dist = 0.f;
@@ -780,9 +829,10 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
         if (!PQ) m_doff[tid] = d >= 0 ? d * 1024 : FM_BUF_OOB;
         m_geo[4 * tid] = gx; m_geo[4 * tid + 1] = gy; m_geo[4 * tid + 2] = gz; m_geo[4 * tid + 3] = dist;
     }
+    // ENTRY: this barrier waits for LDS stores of values computed from the descriptor alone -- no memory request stands in front of it
     __syncthreads();
     FM_MARK(0);
-    // (C) the hoisted per-source scalar term of GVP0 is only consumed after its scalar GEMM: request it now so that its
+    // (C) the hoisted per-source scalar term of GVP0 (rows in the accumulators' map, hence offsets from LDS) is only consumed after its scalar GEMM: request it now so that its
     //     L2 latency overlaps the fill below and the first phases of the GVP (VMEM returns in order, so a request
     //     placed right before the GEMM would stall the GEMM's first weight fragments behind it)
     float pre[TM / 16][1024 / NTH][4];
@@ -807,11 +857,25 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
     // (D) X[:, 0..31] = rbf(d), X[:, 32..159] = ef; hidden vectors of GVP0: Vh[c*TM+r][:] = PV[src][c][:] + xhat[r][c]*w0[:]
     //     All gathers of a thread are issued back to back (unconditional loads from a clamped index, select afterwards):
     //     a branchy load-use-store loop serialises one L2 round trip per iteration (profiles/r01d: 37k cycles here).
-    {
+    //     ENTRY: the gathers left in (B); what follows waits for them only (the Ps / Q requests of (C) stand behind them in the queue).
+    [[maybe_unused]] float e_dist = 0.f;
+    if constexpr (ENTRY) {
+        // the row's geometry from the thread's own registers: x_diff = x[src] - x[dst]; d = sqrt(max(|.|^2,1e-8)) + 1e-8; xhat = x_diff / d  (vector_field.py:381-383)
+        const float dx = e_xs[0] - e_xd[0], dy = e_xs[1] - e_xd[1], dz = e_xs[2] - e_xd[2];
+        const float dist = fm_norm3(dx, dy, dz) + 1e-8f;
+        const float inv_d = __builtin_amdgcn_rcpf(dist);
+        const float g[3] = {dx * inv_d, dy * inv_d, dz * inv_d};      // rows without an edge: 0 * rcp = 0
+        e_dist = er_live ? dist : 0.f;
+#pragma unroll
+        for (int p_ = 0; p_ < NP_; ++p_) {
+            const int ccb = er_half + p_ * (QN / TM), c = ccb / CB_, cb = ccb % CB_;
+            if (NCH_ % QN == 0 || ccb < 3 * CB_)
+                Vh[(c * TM + er_row) * T::LDVH + cb * 16 + j] = fm_fma(c == 0 ? g[0] : c == 1 ? g[1] : g[2], e_w0[p_], e_pv[p_]);      // rows without an edge: 0 + 0 * w0 (range-checked gather, zero geometry)
+        }
+    } else {
         // thread -> (row chunk q, column j of a 16-wide block); chunk = (xyz c, block cb, row r).  With TM*16 == NTH the
         // chunk's (c, cb) is the unrolled loop index and r = q, so every address is one VGPR + an immediate.
-        constexpr int PVW = T::PVW, CB = PVW / 16, NCH = 3 * CB * TM, QN = NTH / 16, NP = (NCH + QN - 1) / QN;
-        const int q = tid >> 4, j = tid & 15;
+        constexpr int PVW = T::PVW, CB = PVW / 16, NCH = 3 * CB * TM, NP = (NCH + QN - 1) / QN;
         const auto rs = fm_buf(a.PV, (unsigned)a.b.N * (unsigned)(3 * PVW * 4));
         const auto rsd = fm_buf(HX > 0 ? a.PVd : a.PV, (unsigned)a.b.N * (unsigned)(3 * PVW * 4));
         float pv[NP], w0v[NP];
@@ -860,6 +924,13 @@ __global__ void __launch_bounds__(NTH) fm_k_edge_message(FmMsgArgs a) {
             }
         }
     } else if constexpr (!PQ) {
+    if constexpr (ENTRY) {       // the 16-lane group of a row writes its 32 radial basis functions from the distance it holds (two groups share a row of a 16-row tile)
+#pragma unroll
+        for (int k0 = 0; k0 < 32; k0 += 16 * (QN / TM)) {
+            const int k = k0 + 16 * er_half + j;
+            X[er_row * FM_LDX + k] = fm_rbf(e_dist, k, a.rbf_mu_step, a.rbf_inv_sigma);
+        }
+    } else
     for (int idx = tid; idx < TM * 32; idx += NTH) {
         const int r = idx >> 5, k = idx & 31;
         X[r * FM_LDX + k] = fm_rbf(m_geo[4 * r + 3], k, a.rbf_mu_step, a.rbf_inv_sigma);      // rows without an edge hold finite junk that is never aggregated
