@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 12
+FM_ABI_VERSION = 13
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
@@ -112,6 +112,10 @@ class fm_inpaint(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('keep_atom', 'keep_pair', 'x0', 'x1c', 'a1', 'c1', 'e1', 'u_a', 'u_c', 'u_e')]
 
 
+class fm_freeze(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('keep_x', 'keep_a', 'keep_c', 'keep_e', 'x0', 'x1c', 'a1', 'c1', 'e1', 'u_a', 'u_c', 'u_e')]
+
+
 class FlowMolHipError(RuntimeError):
     pass
 
@@ -157,6 +161,13 @@ _EXPORTS = {
     'fm_integrate_inpaint': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_int, C.c_int, C.POINTER(fm_step_scalars), C.c_void_p,
                                        C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_step_noise), C.POINTER(fm_dst), C.POINTER(fm_dst),
                                        C.POINTER(fm_dst), C.POINTER(fm_traj_sink), C.POINTER(C.c_int), C.POINTER(fm_inpaint), C.POINTER(C.c_float), C.c_void_p]),
+    # ABI 13: frozen rows per modality, aligned RMSD
+    'fm_ctmc_step_freeze': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.POINTER(fm_dst), C.POINTER(fm_step_noise), C.POINTER(fm_step_scalars),
+                                      C.POINTER(fm_sampled), C.POINTER(fm_freeze), C.POINTER(C.c_float)]),
+    'fm_integrate_freeze': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(fm_state), C.c_int, C.c_int, C.POINTER(fm_step_scalars), C.c_void_p,
+                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_step_noise), C.POINTER(fm_dst), C.POINTER(fm_dst),
+                                      C.POINTER(fm_dst), C.POINTER(fm_traj_sink), C.POINTER(C.c_int), C.POINTER(fm_freeze), C.POINTER(C.c_float), C.c_void_p]),
+    'fm_align_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

@@ -566,7 +566,7 @@ int ctmc_impl(fm_ctx* c, hipStream_t st, const Modality (&md)[3], const fm_state
     if (sc->dfm_type == FM_DFM_GAT) {      // tensor noise: the Euler step and one flat kernel per modality
         if (!nz->q_a) return fail(c, FM_ERR_INVALID, "%s", missing);
         if (keep) L("x_step_keep", fm_k_x_step_keep, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3,
-                    FmKeepX{keep->k.keep[0], keep->k.x0, keep->k.x1c, keep->k.alpha[0]});
+                    FmKeepX{keep->k.keep_x, keep->k.x0, keep->k.x1c, keep->k.alpha[0]});
         else L("x_step", fm_k_x_step, dim3((b.N * 3 + 255) / 256), dim3(256), 0, state->x_t, (const float*)dst->x, sc->x_coef, sc->dt, sc->x_scale, b.N * 3);
         for (int m = 0; m < 3; ++m) {
             if (md[m].rows == 0) continue;
@@ -1407,8 +1407,8 @@ int fm_integrate_mixed(fm_ctx* c, void* stream, const fm_state* state, int n_ste
         return i == 0 ? boot0 : 0; });
 }
 
-// What both frozen-row entry points refuse, before anything is enqueued, and the kernels' view of the caller's struct.  others: every pointer the call writes
-// through or reads as the evolving state (state, endpoint buffers, sampled tokens, sink).
+// What the frozen-row entry points of ABI 12 refuse, before anything is enqueued, and the kernels' view of the caller's struct.  others: every pointer the call
+// writes through or reads as the evolving state (state, endpoint buffers, sampled tokens, sink).
 static int inpaint_check(fm_ctx* c, const char* fn, const fm_inpaint* inp, std::initializer_list<const void*> others, FmKeepArgs& k) {
     if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) have no masked conditional path to freeze rows on", fn);
     const bool pairs = c->ws.b.U > 0;
@@ -1420,19 +1420,50 @@ static int inpaint_check(fm_ctx* c, const char* fn, const fm_inpaint* inp, std::
         for (const void* o : others) if (mem[i] && o == mem[i]) return fail(c, FM_ERR_INVALID, "%s: fm_inpaint.%s aliases the state, an endpoint buffer or the sink", fn, tag[i]);
     }
     k = FmKeepArgs{};
-    k.keep[0] = k.keep[1] = inp->keep_atom; k.keep[2] = inp->keep_pair;
+    k.keep_x = k.keep[0] = k.keep[1] = inp->keep_atom; k.keep[2] = inp->keep_pair;
     k.tok1[0] = inp->a1; k.tok1[1] = inp->c1; k.tok1[2] = inp->e1;
     k.u[0] = inp->u_a; k.u[1] = inp->u_c; k.u[2] = inp->u_e;
     k.x0 = inp->x0; k.x1c = inp->x1c;
     return FM_OK;
 }
-// keep_pair of the caller's struct from keep_atom: one launch per call, ahead of the steps
+// The same for ABI 13's fm_freeze: four independent keep arrays, all inputs.  A modality whose keep pointer is NULL is free, and its path inputs are not read (the kernels
+// branch around its select); a modality whose keep pointer is given needs its path inputs -- the pair modality only in a batch that has pairs.
+static int freeze_check(fm_ctx* c, const char* fn, const fm_freeze* fz, std::initializer_list<const void*> others, FmKeepArgs& k) {
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) have no masked conditional path to freeze rows on", fn);
+    const void* const mem[] = {fz->keep_x, fz->keep_a, fz->keep_c, fz->keep_e, fz->x0, fz->x1c, fz->a1, fz->c1, fz->e1, fz->u_a, fz->u_c, fz->u_e};
+    static const char* const tag[] = {"keep_x", "keep_a", "keep_c", "keep_e", "x0", "x1c", "a1", "c1", "e1", "u_a", "u_c", "u_e"};
+    static const int owner[] = {0, 1, 2, 3, 0, 0, 1, 2, 3, 1, 2, 3};      // the keep array (mem[0..3]) a member belongs to
+    for (int i = 0; i < 12; ++i) {
+        if (!mem[i] && mem[owner[i]] && (owner[i] != 3 || c->ws.b.U > 0))
+            return fail(c, FM_ERR_INVALID, "%s: fm_freeze.%s is NULL while fm_freeze.%s is given", fn, tag[i], tag[owner[i]]);
+        for (const void* o : others) if (mem[i] && o == mem[i]) return fail(c, FM_ERR_INVALID, "%s: fm_freeze.%s aliases the state, an endpoint buffer or the sink", fn, tag[i]);
+    }
+    k = FmKeepArgs{};
+    k.keep_x = fz->keep_x; k.keep[0] = fz->keep_a; k.keep[1] = fz->keep_c; k.keep[2] = c->ws.b.U > 0 ? fz->keep_e : nullptr;
+    k.tok1[0] = fz->a1; k.tok1[1] = fz->c1; k.tok1[2] = fz->e1;
+    k.u[0] = fz->u_a; k.u[1] = fz->u_c; k.u[2] = fz->u_e;
+    k.x0 = fz->x0; k.x1c = fz->x1c;
+    return FM_OK;
+}
+// keep_pair of fm_inpaint from keep_atom: one launch per call, ahead of the steps
 static int keep_pairs(fm_ctx* c, hipStream_t st, const fm_inpaint* inp) {
     const FmBatch& b = c->ws.b;
     Launch L{c, st};
     L("keep_pairs", fm_k_keep_pairs, dim3((b.U + 255) / 256), dim3(256), 0, (const unsigned char*)inp->keep_atom, (unsigned char*)inp->keep_pair,
       (const int*)b.p_e0, (const int*)b.e_src, (const int*)b.e_dst, b.U);
     return L.rc;
+}
+
+// One step with frozen rows, behind the entry point's argument checks: ks.k holds the four keep pointers and the path inputs.  inp: fm_ctmc_step_inpaint's struct, whose
+// keep_pair is filled first; NULL for fm_ctmc_step_freeze, which brings its pair flags.
+static int step_keep(fm_ctx* c, const char* fn, hipStream_t st, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
+                     const fm_sampled* sampled, KeepStep& ks, const float* alpha_next, const fm_inpaint* inp) {
+    if (sc->dfm_type != FM_DFM_CAMPBELL && sc->dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "%s: unknown dfm_type %d", fn, sc->dfm_type);
+    if (sc->noise_mode != FM_NOISE_PHILOX && !noise) return fail(c, FM_ERR_INVALID, "%s: noise tensors missing (noise_mode FM_NOISE_TENSORS)", fn);
+    for (int k = 0; k < 4; ++k) ks.k.alpha[k] = alpha_next[k];
+    if (inp) if (const int rc = keep_pairs(c, st, inp)) return rc;
+    const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
+    return ctmc_impl(c, st, md, state, dst, noise, sc, sampled, nullptr, nullptr, nullptr, &ks);
 }
 
 int fm_ctmc_step_inpaint(fm_ctx* c, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
@@ -1442,29 +1473,25 @@ int fm_ctmc_step_inpaint(fm_ctx* c, void* stream, const fm_state* state, const f
     KeepStep ks{};
     if (const int rc = inpaint_check(c, fn, inp, {state->x_t, state->a_t, state->c_t, state->e_t, dst->x, dst->a, dst->c, dst->e,
                                                   sampled ? sampled->a1 : nullptr, sampled ? sampled->c1 : nullptr, sampled ? sampled->e1 : nullptr}, ks.k)) return rc;
-    if (sc->dfm_type != FM_DFM_CAMPBELL && sc->dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "%s: unknown dfm_type %d", fn, sc->dfm_type);
-    if (sc->noise_mode != FM_NOISE_PHILOX && !noise) return fail(c, FM_ERR_INVALID, "%s: noise tensors missing (noise_mode FM_NOISE_TENSORS)", fn);
-    for (int k = 0; k < 4; ++k) ks.k.alpha[k] = alpha_next[k];
-    if (const int rc = keep_pairs(c, (hipStream_t)stream, inp)) return rc;
-    const Modality md[3] = {modality(c, 0, state), modality(c, 1, state), modality(c, 2, state)};
-    return ctmc_impl(c, (hipStream_t)stream, md, state, dst, noise, sc, sampled, nullptr, nullptr, nullptr, &ks);
+    return step_keep(c, fn, (hipStream_t)stream, state, dst, noise, sc, sampled, ks, alpha_next, inp);
 }
 
-int fm_integrate_inpaint(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
-                         const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
-                         const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
-                         const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev) {
-    const char* const fn = "fm_integrate_inpaint";
+int fm_ctmc_step_freeze(fm_ctx* c, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
+                        const fm_sampled* sampled, const fm_freeze* fz, const float* alpha_next) {
+    const char* const fn = "fm_ctmc_step_freeze";
+    if (const int rc = bound_check(c, fn, state && dst && sc && fz && alpha_next)) return rc;
+    KeepStep ks{};
+    if (const int rc = freeze_check(c, fn, fz, {state->x_t, state->a_t, state->c_t, state->e_t, dst->x, dst->a, dst->c, dst->e,
+                                                sampled ? sampled->a1 : nullptr, sampled ? sampled->c1 : nullptr, sampled ? sampled->e1 : nullptr}, ks.k)) return rc;
+    return step_keep(c, fn, (hipStream_t)stream, state, dst, noise, sc, sampled, ks, alpha_next, nullptr);
+}
+
+// fm_integrate_inpaint / fm_integrate_freeze behind their argument checks (k0: the keep pointers and path inputs; inp as in step_keep)
+static int integrate_keep(fm_ctx* c, const char* fn, hipStream_t st, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                          const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                          const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                          const FmKeepArgs& k0, const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev) {
     const bool one = n_groups == 1;
-    const bool args_ok = state && steps && temb && dst_a && dst_b && inp && alpha_next && (one || (steps_dev && active && active_dev && mol_group && alpha_next_dev));
-    if (const int rc = bound_check(c, fn, args_ok)) return rc;
-    if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
-    static const fm_traj_sink no_sink{};
-    const fm_traj_sink& sk = sink ? *sink : no_sink;
-    FmKeepArgs k0{};
-    if (const int rc = inpaint_check(c, fn, inp, {state->x_t, state->a_t, state->c_t, state->e_t, dst_a->x, dst_a->a, dst_a->c, dst_a->e, dst_b->x, dst_b->a, dst_b->c, dst_b->e,
-                                                  sk.x, sk.a, sk.c, sk.e, sk.x1, sk.a1, sk.c1, sk.e1}, k0)) return rc;
-    const hipStream_t st = (hipStream_t)stream;
     std::vector<KeepStep> ks((size_t)std::max(n_steps, 0));
     for (int i = 0; i < n_steps; ++i) {
         ks[i].k = k0;
@@ -1477,7 +1504,7 @@ int fm_integrate_inpaint(fm_ctx* c, void* stream, const fm_state* state, int n_s
             if (steps[i].dfm_type != FM_DFM_CAMPBELL && steps[i].dfm_type != FM_DFM_GAT) return fail(c, FM_ERR_INVALID, "%s: unknown dfm_type %d (step %d)", fn, steps[i].dfm_type, i);
             if (steps[i].noise_mode != FM_NOISE_PHILOX && !noise) return fail(c, FM_ERR_INVALID, "%s: noise tensors missing (noise_mode FM_NOISE_TENSORS, step %d)", fn, i);
         }
-        if (const int rc = keep_pairs(c, st, inp)) return rc;
+        if (inp) if (const int rc = keep_pairs(c, st, inp)) return rc;
         return step_driver(c, st, state, n_steps, 1, nullptr, temb, prev0, dst_a, dst_b, sink, final_dst,
                            [&](int i, const fm_dst* prev, const fm_step_scalars*& sc, const fm_step_noise*& nz, MixedStep&) {
             sc = &steps[i]; nz = noise ? &noise[i] : nullptr;
@@ -1497,12 +1524,66 @@ int fm_integrate_inpaint(fm_ctx* c, void* stream, const fm_state* state, int n_s
         if (at0 && later) return fail(c, FM_ERR_INVALID, "%s: prev0 is NULL and only %d of %d active groups are at t = 0: start the groups at t = 0 in a call of their own", fn, at0, at0 + later);
         boot0 = at0 ? 1 : 0;
     }
-    if (const int rc = keep_pairs(c, st, inp)) return rc;
+    if (inp) if (const int rc = keep_pairs(c, st, inp)) return rc;
     static const fm_step_scalars philox_step = [] { fm_step_scalars s{}; s.dfm_type = FM_DFM_CAMPBELL; s.noise_mode = FM_NOISE_PHILOX; return s; }();
     return step_driver(c, st, state, n_steps, n_groups, mol_group, temb, prev0, dst_a, dst_b, nullptr, final_dst,
                        [&](int i, const fm_dst*, const fm_step_scalars*& sc, const fm_step_noise*&, MixedStep& mixed) {
         sc = &philox_step; mixed = {steps_dev + (size_t)i * n_groups, active_dev + (size_t)i * n_groups, mol_group};
         return i == 0 ? boot0 : 0; }, keep_of);
+}
+
+// the argument checks fm_integrate_inpaint and fm_integrate_freeze share, up to their struct's own (check: inpaint_check / freeze_check on the pointers of the call)
+static int integrate_keep_entry(fm_ctx* c, const char* fn, const fm_state* state, int n_groups, const fm_step_scalars* steps, const fm_step_scalars* steps_dev,
+                                const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb, const fm_dst* dst_a, const fm_dst* dst_b,
+                                const fm_traj_sink* sink, const void* spec, const float* alpha_next, const float* alpha_next_dev,
+                                const std::function<int(std::initializer_list<const void*>)>& check) {
+    const bool one = n_groups == 1;
+    const bool args_ok = state && steps && temb && dst_a && dst_b && spec && alpha_next && (one || (steps_dev && active && active_dev && mol_group && alpha_next_dev));
+    if (const int rc = bound_check(c, fn, args_ok)) return rc;
+    if (n_groups < 1 || n_groups > FM_TAB_SLOTS) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d outside 1..%d (FM_TAB_SLOTS embedding tables per bound batch)", fn, n_groups, FM_TAB_SLOTS);
+    static const fm_traj_sink no_sink{};
+    const fm_traj_sink& sk = sink ? *sink : no_sink;
+    return check({state->x_t, state->a_t, state->c_t, state->e_t, dst_a->x, dst_a->a, dst_a->c, dst_a->e, dst_b->x, dst_b->a, dst_b->c, dst_b->e,
+                  sk.x, sk.a, sk.c, sk.e, sk.x1, sk.a1, sk.c1, sk.e1});
+}
+
+int fm_integrate_inpaint(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                         const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                         const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                         const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev) {
+    const char* const fn = "fm_integrate_inpaint";
+    FmKeepArgs k0{};
+    if (const int rc = integrate_keep_entry(c, fn, state, n_groups, steps, steps_dev, active, active_dev, mol_group, temb, dst_a, dst_b, sink, inp, alpha_next, alpha_next_dev,
+                                            [&](std::initializer_list<const void*> others) { return inpaint_check(c, fn, inp, others, k0); })) return rc;
+    return integrate_keep(c, fn, (hipStream_t)stream, state, n_steps, n_groups, steps, steps_dev, active, active_dev, mol_group, temb, noise, prev0, dst_a, dst_b, sink,
+                          final_dst, k0, inp, alpha_next, alpha_next_dev);
+}
+
+int fm_integrate_freeze(fm_ctx* c, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                        const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                        const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                        const fm_freeze* fz, const float* alpha_next, const float* alpha_next_dev) {
+    const char* const fn = "fm_integrate_freeze";
+    FmKeepArgs k0{};
+    if (const int rc = integrate_keep_entry(c, fn, state, n_groups, steps, steps_dev, active, active_dev, mol_group, temb, dst_a, dst_b, sink, fz, alpha_next, alpha_next_dev,
+                                            [&](std::initializer_list<const void*> others) { return freeze_check(c, fn, fz, others, k0); })) return rc;
+    return integrate_keep(c, fn, (hipStream_t)stream, state, n_steps, n_groups, steps, steps_dev, active, active_dev, mol_group, temb, noise, prev0, dst_a, dst_b, sink,
+                          final_dst, k0, nullptr, alpha_next, alpha_next_dev);
+}
+
+// Aligned RMSD of two coordinate sets of the bound batch, molecule by molecule (fm_k_align_rmsd: one wave per molecule, everything on the device)
+int fm_align_rmsd(fm_ctx* c, void* stream, const float* xa, const float* xb, const uint8_t* select, float* out, float* xa_aligned) {
+    const char* const fn = "fm_align_rmsd";
+    if (const int rc = bound_check(c, fn, xa && xb && out)) return rc;
+    const void* const in[] = {xa, xb, select};
+    for (const void* p : in) {
+        if (p && p == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: out aliases an input", fn);
+        if (p && xa_aligned && p == (const void*)xa_aligned) return fail(c, FM_ERR_INVALID, "%s: xa_aligned aliases an input", fn);
+    }
+    if (xa_aligned && (const void*)xa_aligned == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: xa_aligned aliases out", fn);
+    Launch L{c, (hipStream_t)stream};
+    L("align_rmsd", fm_k_align_rmsd, dim3(c->ws.b.B), dim3(64), 0, xa, xb, (const unsigned char*)select, (const int*)c->ws.b.mol_node_off, out, xa_aligned);
+    return L.rc;
 }
 
 int fm_set_tap(fm_ctx* c, const char* name, void* dst) {

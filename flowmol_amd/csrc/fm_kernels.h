@@ -1791,25 +1791,27 @@ struct FmCtmcFusedArgs {
 // on that call's own tape: nothing is drawn here).  FmNoKeep: the instances of fm_ctmc_step / fm_integrate / fm_integrate_mixed, whose code is untouched.
 //   FmKeepMod (jobs 0..2)   tok = u < thr ? mask : tok1, thr = 1 - alpha_next of the modality; keep: per atom (a, c) or per pair (e: both atoms kept)
 //   FmKeepX (job 3)         x = (1 - ax) x0 + ax x1c, separately rounded; keep: per atom
-// alpha_next is workgroup-uniform; flags and path inputs are plain per-row loads behind the flag.
+// alpha_next is workgroup-uniform; flags and path inputs are plain per-row loads behind the flag.  A null keep pointer (fm_*_freeze: that modality is free) is a
+// uniform branch around the select.
 struct FmNoKeep { static constexpr bool on = false; };
 struct FmKeepMod { static constexpr bool on = true; const unsigned char* keep; const int* tok1; const float* u; float thr; };
 struct FmKeepX { static constexpr bool on = true; const unsigned char* keep; const float* x0; const float* x1c; float ax; };
-struct FmKeepArgs {                 // a, c, e: keep[0] == keep[1] == the caller's keep_atom, keep[2] == keep_pair
+struct FmKeepArgs {                 // one keep pointer per modality: keep[0..2] = a, c, e, keep_x = positions; null = nothing of that modality is frozen and its
+                                    // path inputs are not read (fm_*_inpaint: keep_x == keep[0] == keep[1] == the caller's keep_atom, keep[2] == keep_pair)
     const unsigned char* keep[3]; const int* tok1[3]; const float* u[3];
-    const float* x0; const float* x1c;
+    const unsigned char* keep_x; const float* x0; const float* x1c;
     float alpha[4];                 // alpha_next of x, a, c, e (single-schedule kernels; the mixed kernel reads its group's row from memory)
 };
 __device__ __forceinline__ FmKeepMod fm_keep_mod(const FmKeepArgs& k, int job, float alpha) { return {k.keep[job], k.tok1[job], k.u[job], fm_sub_rn(1.0f, alpha)}; }
-__device__ __forceinline__ FmKeepX fm_keep_x(const FmKeepArgs& k, float ax) { return {k.keep[0], k.x0, k.x1c, ax}; }
+__device__ __forceinline__ FmKeepX fm_keep_x(const FmKeepArgs& k, float ax) { return {k.keep_x, k.x0, k.x1c, ax}; }
 template <class KX>
 __device__ __forceinline__ float fm_keep_x_select(const KX& kx, int i, float xn) {
-    if constexpr (KX::on) { if (kx.keep[i / 3]) xn = fm_add_rn(fm_mul_rn(fm_sub_rn(1.0f, kx.ax), kx.x0[i]), fm_mul_rn(kx.ax, kx.x1c[i])); }
+    if constexpr (KX::on) { if (kx.keep && kx.keep[i / 3]) xn = fm_add_rn(fm_mul_rn(fm_sub_rn(1.0f, kx.ax), kx.x0[i]), fm_mul_rn(kx.ax, kx.x1c[i])); }
     return xn;
 }
 template <class KP>
 __device__ __forceinline__ int fm_keep_tok_select(const KP& kp, int i, int K, int nt) {
-    if constexpr (KP::on) { if (kp.keep[i]) nt = kp.u[i] < kp.thr ? K : kp.tok1[i]; }
+    if constexpr (KP::on) { if (kp.keep && kp.keep[i]) nt = kp.u[i] < kp.thr ? K : kp.tok1[i]; }
     return nt;
 }
 
@@ -2442,6 +2444,126 @@ static __global__ void __launch_bounds__(64) fm_k_denoise_reduce(FmLossReduceArg
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) a.out[mol * 8 + k] = r[k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Aligned RMSD of two coordinate sets, molecule by molecule (fm_align_rmsd): out[m] = {selected atoms, rmsd after centring both sets on the selected atoms, rmsd
+// after the optimal PROPER rotation of xa onto xb, 0}; xa_al (may be null) = all atoms of xa under the fitted transform R (xa - mean_a) + mean_b.
+// One wave per molecule.  SUMMATION ORDER (canonical: a function of the molecule alone): lane l adds its atoms n0 + l, n0 + l + 64, ... in order from +0 -- an
+// unselected atom adds nothing --, then the 64 lane sums meet in the xor tree 32, 16, .. 1, which leaves the same bits in every lane.  Three rounds of sums:
+//   1  the count and the means, of coordinates taken relative to the molecule's FIRST atom (a cloud far from the origin keeps its digits; the subtraction is
+//      exact for atoms within a factor two of it and harmless otherwise)
+//   2  the 3x3 cross-covariance S[i][j] = sum a_i b_j of the centred coordinates and sum |a - b|^2
+//   3  sum |R a - b|^2 from the explicit residuals -- not Ga + Gb - 2 lambda, which cancels for near-identical conformers
+// Between 2 and 3 lane 0 finds the rotation: the eigenvector of the largest eigenvalue of Horn's symmetric 4x4 matrix N(S) (Horn 1987, eq. 25; a unit quaternion,
+// so det R = +1 by construction, and any vector of a degenerate top eigenspace -- collinear atoms -- gives the same rmsd) by FM_ALIGN_SWEEPS cyclic Jacobi sweeps in
+// f32 (a 4x4 symmetric matrix is diagonal to rounding after 5; no convergence test, so the work and the bits do not depend on anything but the molecule).
+// Every product that feeds a sum is separately rounded (fm_*_rn): the emulation and the device agree.
+// ------------------------------------------------------------------------------------------------
+#define FM_ALIGN_SWEEPS 8
+__device__ __forceinline__ float fm_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fm_add_rn(v, __shfl_xor(v, o));
+    return v;
+}
+// the rotation of the unit quaternion that maximises q^T N(S) q, row-major in R
+__device__ __forceinline__ void fm_horn_rotation(const float (&S)[3][3], float (&R)[9]) {
+    float A[4][4], V[4][4];
+    A[0][0] = fm_add_rn(fm_add_rn(S[0][0], S[1][1]), S[2][2]);
+    A[1][1] = fm_sub_rn(fm_sub_rn(S[0][0], S[1][1]), S[2][2]);
+    A[2][2] = fm_sub_rn(fm_sub_rn(S[1][1], S[0][0]), S[2][2]);
+    A[3][3] = fm_sub_rn(fm_sub_rn(S[2][2], S[0][0]), S[1][1]);
+    A[0][1] = A[1][0] = fm_sub_rn(S[1][2], S[2][1]);
+    A[0][2] = A[2][0] = fm_sub_rn(S[2][0], S[0][2]);
+    A[0][3] = A[3][0] = fm_sub_rn(S[0][1], S[1][0]);
+    A[1][2] = A[2][1] = fm_add_rn(S[0][1], S[1][0]);
+    A[1][3] = A[3][1] = fm_add_rn(S[2][0], S[0][2]);
+    A[2][3] = A[3][2] = fm_add_rn(S[1][2], S[2][1]);
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.f : 0.f;
+    for (int sweep = 0; sweep < FM_ALIGN_SWEEPS; ++sweep) {
+        for (int p = 0; p < 3; ++p) {
+            for (int q = p + 1; q < 4; ++q) {
+                const float apq = A[p][q];
+                if (apq == 0.f) continue;
+                // the rotation that zeroes A[p][q]: t = tan of the smaller root; a huge theta gives t = 0, never a NaN
+                const float theta = fm_div_rn(fm_sub_rn(A[q][q], A[p][p]), fm_mul_rn(2.f, apq));
+                const float t = fm_div_rn(theta < 0.f ? -1.f : 1.f, fm_add_rn(fabsf(theta), sqrtf(fm_add_rn(fm_mul_rn(theta, theta), 1.f))));
+                const float c = fm_div_rn(1.f, sqrtf(fm_add_rn(fm_mul_rn(t, t), 1.f))), s = fm_mul_rn(t, c);
+                A[p][p] = fm_sub_rn(A[p][p], fm_mul_rn(t, apq));
+                A[q][q] = fm_add_rn(A[q][q], fm_mul_rn(t, apq));
+                A[p][q] = A[q][p] = 0.f;
+                for (int r = 0; r < 4; ++r) {
+                    if (r != p && r != q) {
+                        const float arp = A[r][p], arq = A[r][q];
+                        A[r][p] = A[p][r] = fm_sub_rn(fm_mul_rn(c, arp), fm_mul_rn(s, arq));
+                        A[r][q] = A[q][r] = fm_add_rn(fm_mul_rn(s, arp), fm_mul_rn(c, arq));
+                    }
+                    const float vrp = V[r][p], vrq = V[r][q];
+                    V[r][p] = fm_sub_rn(fm_mul_rn(c, vrp), fm_mul_rn(s, vrq));
+                    V[r][q] = fm_add_rn(fm_mul_rn(s, vrp), fm_mul_rn(c, vrq));
+                }
+            }
+        }
+    }
+    int best = 0;
+    for (int i = 1; i < 4; ++i) if (A[i][i] > A[best][best]) best = i;
+    float w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
+    const float nrm = sqrtf(fm_add_rn(fm_add_rn(fm_mul_rn(w, w), fm_mul_rn(x, x)), fm_add_rn(fm_mul_rn(y, y), fm_mul_rn(z, z))));
+    w = fm_div_rn(w, nrm); x = fm_div_rn(x, nrm); y = fm_div_rn(y, nrm); z = fm_div_rn(z, nrm);
+    const float ww = fm_mul_rn(w, w), xx = fm_mul_rn(x, x), yy = fm_mul_rn(y, y), zz = fm_mul_rn(z, z);
+    const float xy = fm_mul_rn(x, y), xz = fm_mul_rn(x, z), yz = fm_mul_rn(y, z), wx = fm_mul_rn(w, x), wy = fm_mul_rn(w, y), wz = fm_mul_rn(w, z);
+    R[0] = fm_sub_rn(fm_add_rn(ww, xx), fm_add_rn(yy, zz)); R[1] = fm_mul_rn(2.f, fm_sub_rn(xy, wz)); R[2] = fm_mul_rn(2.f, fm_add_rn(xz, wy));
+    R[3] = fm_mul_rn(2.f, fm_add_rn(xy, wz)); R[4] = fm_sub_rn(fm_add_rn(ww, yy), fm_add_rn(xx, zz)); R[5] = fm_mul_rn(2.f, fm_sub_rn(yz, wx));
+    R[6] = fm_mul_rn(2.f, fm_sub_rn(xz, wy)); R[7] = fm_mul_rn(2.f, fm_add_rn(yz, wx)); R[8] = fm_sub_rn(fm_add_rn(ww, zz), fm_add_rn(xx, yy));
+}
+static __global__ void __launch_bounds__(64) fm_k_align_rmsd(const float* __restrict__ xa, const float* __restrict__ xb, const unsigned char* __restrict__ sel,
+                                                             const int* __restrict__ node_off, float* __restrict__ out, float* __restrict__ xa_al) {
+    const int mol = blockIdx.x, lane = threadIdx.x;
+    const int n0 = node_off[mol], n1 = node_off[mol + 1];
+    float oa[3] = {0.f, 0.f, 0.f}, ob[3] = {0.f, 0.f, 0.f};      // the molecule's first atom: the origin of every sum
+    if (n1 > n0) for (int k = 0; k < 3; ++k) { oa[k] = xa[n0 * 3 + k]; ob[k] = xb[n0 * 3 + k]; }
+    float cnt = 0.f, ma[3] = {0.f, 0.f, 0.f}, mb[3] = {0.f, 0.f, 0.f};
+    for (int n = n0 + lane; n < n1; n += 64) {
+        if (sel && !sel[n]) continue;
+        cnt += 1.f;
+        for (int k = 0; k < 3; ++k) { ma[k] = fm_add_rn(ma[k], fm_sub_rn(xa[n * 3 + k], oa[k])); mb[k] = fm_add_rn(mb[k], fm_sub_rn(xb[n * 3 + k], ob[k])); }
+    }
+    cnt = fm_wave_sum(cnt);
+    if (cnt == 0.f) {      // wave-uniform: nothing selected
+        if (lane < 4) out[mol * 4 + lane] = 0.f;
+        if (xa_al) for (int i = n0 * 3 + lane; i < n1 * 3; i += 64) xa_al[i] = xa[i];
+        return;
+    }
+    for (int k = 0; k < 3; ++k) { ma[k] = fm_div_rn(fm_wave_sum(ma[k]), cnt); mb[k] = fm_div_rn(fm_wave_sum(mb[k]), cnt); }
+    float S[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, d0 = 0.f;
+    for (int n = n0 + lane; n < n1; n += 64) {
+        if (sel && !sel[n]) continue;
+        float a[3], b[3];
+        for (int k = 0; k < 3; ++k) { a[k] = fm_sub_rn(fm_sub_rn(xa[n * 3 + k], oa[k]), ma[k]); b[k] = fm_sub_rn(fm_sub_rn(xb[n * 3 + k], ob[k]), mb[k]); }
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = fm_add_rn(S[i][j], fm_mul_rn(a[i], b[j]));
+        for (int k = 0; k < 3; ++k) { const float d = fm_sub_rn(a[k], b[k]); d0 = fm_add_rn(d0, fm_mul_rn(d, d)); }
+    }
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = fm_wave_sum(S[i][j]);
+    d0 = fm_wave_sum(d0);
+    float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    if (lane == 0) fm_horn_rotation(S, R);
+    for (int k = 0; k < 9; ++k) R[k] = __shfl(R[k], 0);
+    float d1 = 0.f;
+    for (int n = n0 + lane; n < n1; n += 64) {
+        float a[3], r[3];
+        for (int k = 0; k < 3; ++k) a[k] = fm_sub_rn(fm_sub_rn(xa[n * 3 + k], oa[k]), ma[k]);
+        for (int k = 0; k < 3; ++k) r[k] = fm_add_rn(fm_add_rn(fm_mul_rn(R[k * 3], a[0]), fm_mul_rn(R[k * 3 + 1], a[1])), fm_mul_rn(R[k * 3 + 2], a[2]));
+        if (xa_al) for (int k = 0; k < 3; ++k) xa_al[n * 3 + k] = fm_add_rn(fm_add_rn(r[k], mb[k]), ob[k]);
+        if (sel && !sel[n]) continue;
+        for (int k = 0; k < 3; ++k) {
+            const float d = fm_sub_rn(r[k], fm_sub_rn(fm_sub_rn(xb[n * 3 + k], ob[k]), mb[k]));
+            d1 = fm_add_rn(d1, fm_mul_rn(d, d));
+        }
+    }
+    d1 = fm_wave_sum(d1);
+    if (lane == 0) {
+        out[mol * 4] = cnt; out[mol * 4 + 1] = sqrtf(fm_div_rn(d0, cnt)); out[mol * 4 + 2] = sqrtf(fm_div_rn(d1, cnt)); out[mol * 4 + 3] = 0.f;
     }
 }
 

@@ -801,21 +801,66 @@ class Engine:
             setattr(s, name, _ptr(spec[name]) if spec[name].numel() else None)      # a batch without pairs: empty pair tensors travel as NULL
         return s
 
+    def freeze_spec(self, x1_state, keep: Dict[str, torch.Tensor], seed: int) -> Dict[str, Optional[torch.Tensor]]:
+        """The tensors of an ``fm_freeze`` struct for the bound batch (and its molecule ids): frozen rows per modality.  ``keep``: a dict with any of the
+        keys 'x', 'a', 'c' ((N,) bool: positions, atom types, charges) and 'e' ((U,) bool, the pair order of ``e_t``); a missing key -- or None -- leaves
+        that modality free: its keep array and its path inputs stay None and travel as NULL.  The other members are those of ``inpaint_spec``, of which
+        this is the general form: 'x': k, 'a': k, 'c': k, 'e': both atoms in k gives the bits of ``inpaint_spec(x1_state, k, seed)``."""
+        unknown = set(keep) - set('xace')
+        if unknown:
+            raise ValueError(f"keep has unknown keys {sorted(unknown)}: 'x', 'a', 'c' (atoms) and 'e' (pairs) are the modalities")
+        d, flags = self.device, {}
+        for f in 'xace':
+            k = keep.get(f)
+            if k is None:
+                continue
+            k = torch.as_tensor(k).detach().reshape(-1)
+            rows = self.U if f == 'e' else self.N
+            if k.shape[0] != rows:
+                raise ValueError(f"keep['{f}'] has {k.shape[0]} entries, the bound batch {rows} {'pairs' if f == 'e' else 'atoms'}")
+            flags[f] = (k != 0).to(torch.uint8).to(d).contiguous()
+        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True)
+        spec = {name: None for name, _ in _lib.fm_freeze._fields_}
+        if 'x' in flags:
+            spec.update(keep_x=flags['x'], x0=tape['x0'], x1c=self.remove_com(x1_state['x_t'].detach().to(d, torch.float32).contiguous().clone()))
+        for f in 'ace':
+            if f in flags:
+                spec.update({f'keep_{f}': flags[f], f'{f}1': x1_state[f'{f}_t'].detach().to(d, torch.int32).contiguous().clone(), f'u_{f}': tape[f'u_{f}']})
+        return spec
+
+    @staticmethod
+    def _freeze_struct(spec) -> "_lib.fm_freeze":
+        s = _lib.fm_freeze()
+        for name, _ in _lib.fm_freeze._fields_:
+            setattr(s, name, _ptr(spec[name]) if spec[name] is not None and spec[name].numel() else None)
+        return s
+
+    def _keep_struct(self, spec):
+        """(the C struct, the entry points' suffix) of either kind of spec: ``inpaint_spec`` (fm_*_inpaint) or ``freeze_spec`` (fm_*_freeze)."""
+        return (self._inpaint_struct(spec), 'inpaint') if 'keep_atom' in spec else (self._freeze_struct(spec), 'freeze')
+
     def ctmc_step_inpaint(self, state, dst, noise: Optional[StepNoise], sc: fm_step_scalars, spec, alpha_next, sampled: Optional[Dict[str, torch.Tensor]] = None):
         """``ctmc_step`` with the frozen rows of ``spec`` (``inpaint_spec``) put back onto the given molecule's conditional path at ``alpha_next``
         (4 values: alpha_t of x, a, c, e at the time the step arrives at) inside the step kernel (fm_ctmc_step_inpaint)."""
-        st, d, ip = self._state_struct(state), self._dst_struct(dst), self._inpaint_struct(spec)
+        (ip, kind), st, d = self._keep_struct(spec), self._state_struct(state), self._dst_struct(dst)
         nz = noise.c_struct() if noise is not None else None
         smp = fm_sampled()
         if sampled is not None:
             smp.a1, smp.c1, smp.e1 = _ptr(sampled['a1']), _ptr(sampled['c1']), _ptr(sampled['e1'])
         al = (C.c_float * 4)(*[float(v) for v in torch.as_tensor(alpha_next, dtype=torch.float32).reshape(-1).tolist()])
         with self._dev():
-            rc = self.lib.fm_ctmc_step_inpaint(self._ctx, self._stream(), C.byref(st), C.byref(d), C.byref(nz) if nz is not None else None, C.byref(sc),
-                                               C.byref(smp), C.byref(ip), al)
-        self._check(rc, 'fm_ctmc_step_inpaint')
+            rc = getattr(self.lib, f'fm_ctmc_step_{kind}')(self._ctx, self._stream(), C.byref(st), C.byref(d), C.byref(nz) if nz is not None else None, C.byref(sc),
+                                                           C.byref(smp), C.byref(ip), al)
+        self._check(rc, f'fm_ctmc_step_{kind}')
         self._keep = [state, dst, noise, sampled, spec]
         return state
+
+    def ctmc_step_freeze(self, state, dst, noise: Optional[StepNoise], sc: fm_step_scalars, spec, alpha_next, sampled: Optional[Dict[str, torch.Tensor]] = None):
+        """``ctmc_step`` with the rows ``spec`` (``freeze_spec``) flags, modality by modality, put back onto the given molecule's conditional path at
+        ``alpha_next`` inside the step kernel (fm_ctmc_step_freeze)."""
+        if 'keep_atom' in spec:
+            raise ValueError('ctmc_step_freeze takes the spec of freeze_spec')
+        return self.ctmc_step_inpaint(state, dst, noise, sc, spec, alpha_next, sampled)
 
     def plan_alphas(self, plan: StepPlan) -> torch.Tensor:
         """alpha_t (T, 4: x, a, c, e) at the time points of ``plan``: row i + 1 is the ``alpha_next`` of its step i."""
@@ -851,17 +896,47 @@ class Engine:
         temb, group, al_dev = temb.to(d).contiguous(), group.to(d), al.to(d)
         dst = [self.new_dst(), self.new_dst()]
         ds = [self._dst_struct(dst[0]), self._dst_struct(dst[1])]
-        st, ip = self._state_struct(state), self._inpaint_struct(spec)
+        (ip, kind), st = self._keep_struct(spec), self._state_struct(state)
         p = self._dst_struct(prev) if prev is not None else None
         final = C.c_int(0)
         with self._dev():
-            rc = self.lib.fm_integrate_inpaint(self._ctx, self._stream(), C.byref(st), n, G, scal, _ptr(scal_dev), act, _ptr(act_dev), _ptr(group), _ptr(temb), None,
-                                               C.byref(p) if p is not None else None, C.byref(ds[0]), C.byref(ds[1]), None, C.byref(final), C.byref(ip),
-                                               C.cast(C.c_void_p(al.data_ptr()), C.POINTER(C.c_float)), _ptr(al_dev))
-        self._check(rc, 'fm_integrate_inpaint')
+            rc = getattr(self.lib, f'fm_integrate_{kind}')(self._ctx, self._stream(), C.byref(st), n, G, scal, _ptr(scal_dev), act, _ptr(act_dev), _ptr(group), _ptr(temb),
+                                                           None, C.byref(p) if p is not None else None, C.byref(ds[0]), C.byref(ds[1]), None, C.byref(final), C.byref(ip),
+                                                           C.cast(C.c_void_p(al.data_ptr()), C.POINTER(C.c_float)), _ptr(al_dev))
+        self._check(rc, f'fm_integrate_{kind}')
         self.synchronize()
         self._keep = [state, prev, dst, spec]
         return dst[final.value]
+
+    def integrate_freeze(self, state, plans: Sequence[StepPlan], mol_group, spec, start: Optional[Sequence[int]] = None, n_steps: Optional[int] = None, prev=None):
+        """``integrate_inpaint`` with the per-modality frozen rows of ``spec`` (``freeze_spec``): fm_integrate_freeze, same arguments and return value."""
+        if 'keep_atom' in spec:
+            raise ValueError('integrate_freeze takes the spec of freeze_spec')
+        return self.integrate_inpaint(state, plans, mol_group, spec, start=start, n_steps=n_steps, prev=prev)
+
+    # ------------------------------------------------------------------ aligned RMSD
+    def align_rmsd(self, xa: torch.Tensor, xb: torch.Tensor, select=None, aligned: bool = False):
+        """RMSD of the coordinate sets ``xa`` and ``xb`` ((N,3) each, the bound batch's atoms) molecule by molecule, on the device (fm_align_rmsd): returns
+        (B,4) float32 = {selected atoms, rmsd after centring both on the selected atoms, rmsd after the optimal proper rotation of xa onto xb, 0}.
+        ``select`` ((N,) bool, None = all): the atoms the fit and the rmsd run over; a molecule without one gives zeros.  ``aligned``: also return (N,3),
+        all atoms of ``xa`` moved by the transform fitted on the selected ones.  Does not synchronise."""
+        d = self.device
+        xa, xb = (v.detach().to(d, torch.float32).contiguous() for v in (xa, xb))
+        if tuple(xa.shape) != (self.N, 3) or tuple(xb.shape) != (self.N, 3):
+            raise ValueError(f'xa and xb must be ({self.N}, 3): the atoms of the bound batch')
+        sel = None
+        if select is not None:
+            sel = torch.as_tensor(select).detach().reshape(-1)
+            if sel.shape[0] != self.N:
+                raise ValueError(f'select has {sel.shape[0]} entries, the bound batch {self.N} atoms')
+            sel = (sel != 0).to(torch.uint8).to(d).contiguous()
+        out = torch.empty(self.B, 4, device=d)
+        moved = torch.empty(self.N, 3, device=d) if aligned else None
+        with self._dev():
+            rc = self.lib.fm_align_rmsd(self._ctx, self._stream(), _ptr(xa), _ptr(xb), _ptr(sel), _ptr(out), _ptr(moved))
+        self._check(rc, 'fm_align_rmsd')
+        self._keep = [xa, xb, sel, out, moved]
+        return (out, moved) if aligned else out
 
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):
@@ -879,11 +954,11 @@ class IntegrationRun:
     window of steps; Engine.integrate runs them all)."""
 
     def __init__(self, eng: Engine, state, plan: StepPlan, noise_for_step, traj=None, inpaint=None):
-        """``inpaint``: the spec of ``Engine.inpaint_spec`` -- every step then freezes its rows (fm_integrate_inpaint with one group, which keeps
-        the trajectory sink and the noise callback); None: fm_integrate."""
+        """``inpaint``: the spec of ``Engine.inpaint_spec`` or ``Engine.freeze_spec`` -- every step then freezes its rows (fm_integrate_inpaint /
+        fm_integrate_freeze with one group, which keep the trajectory sink and the noise callback); None: fm_integrate."""
         self.eng, self.state, self.plan, self.noise_for_step, self.traj = eng, state, plan, noise_for_step, traj
         self.inpaint = inpaint
-        self._ip = eng._inpaint_struct(inpaint) if inpaint is not None else None
+        self._ip, self._kind = eng._keep_struct(inpaint) if inpaint is not None else (None, None)
         self._alphas = eng.plan_alphas(plan) if inpaint is not None else None
         tt = eng.cfg.time_embedding_dim
         self.temb_all = (torch.stack([time_embedding_host(sc.t, tt) for sc in plan.scalars]) if plan.scalars
@@ -937,10 +1012,10 @@ class IntegrationRun:
                                               C.byref(sink) if sink is not None else None, C.byref(final))
                 else:
                     al = (C.c_float * (4 * k))(*self._alphas[a + 1:b + 1].reshape(-1).tolist())
-                    rc = eng.lib.fm_integrate_inpaint(eng._ctx, eng._stream(), C.byref(self._st), k, 1, scal, None, None, None, None, _ptr(self.temb_all[a:]), nzs, prev,
-                                                      C.byref(self._dsts[0]), C.byref(self._dsts[1]),
-                                                      C.byref(sink) if sink is not None else None, C.byref(final), C.byref(self._ip), al, None)
-            eng._check(rc, 'fm_integrate' if self._ip is None else 'fm_integrate_inpaint')
+                    rc = getattr(eng.lib, f'fm_integrate_{self._kind}')(eng._ctx, eng._stream(), C.byref(self._st), k, 1, scal, None, None, None, None,
+                                                                        _ptr(self.temb_all[a:]), nzs, prev, C.byref(self._dsts[0]), C.byref(self._dsts[1]),
+                                                                        C.byref(sink) if sink is not None else None, C.byref(final), C.byref(self._ip), al, None)
+            eng._check(rc, 'fm_integrate' if self._ip is None else f'fm_integrate_{self._kind}')
             self.prev_idx = final.value
             # bound the noise kept alive: a chunk's tensors are released once the GPU has passed the event recorded behind it.  The host waits for
             # the chunk BEFORE the previous one only, so two chunks stay enqueued and the device never idles (a device-wide synchronise here

@@ -353,7 +353,13 @@ class FlowMol:
         onto the given molecule's conditional path at the new time, inside the step kernel, so the network always sees the kept part at the noise level it
         was trained on.  On models with alpha(1) = 1 the kept rows of the result are the CENTRED input rows bit for bit; the result is not re-centred:
         its frame is that of the given molecule.  A bond with one free atom is free.  ``None`` or all-False is the call without ``keep``.  Sharding
-        across ranks and the command line do not take ``keep``."""
+        across ranks and the command line do not take ``keep``.
+
+        ``keep`` per modality: a dict with any of the keys 'x', 'a', 'c' (positions, atom types, charges: given like the whole-atom form) and 'e'
+        (bonds: a bool tensor over the concatenated unordered pairs, or one sequence of n (n - 1) / 2 entries per molecule in upper-triangle order, the
+        order of ``e``).  The four are independent -- every type, charge and bond frozen with the positions free gives conformers of the given graph
+        (``conformers``), 'x' alone fixes a pose and lets the chemistry run, a bond may be frozen between two free atoms -- and a missing key leaves
+        that modality free.  {'x': k, 'a': k, 'c': k, 'e': both atoms in k} is ``keep=k`` bit for bit; an all-False dict is the call without ``keep``."""
         cfg = self.cfg
         # ---- arguments: every refusal before the bind and before anything is enqueued; no generator is touched
         if cfg.parameterization == 'endpoint':
@@ -373,7 +379,7 @@ class FlowMol:
             raise NotImplementedError("resample with per-molecule start_step / n_timesteps: dfm_type 'gat' is not supported")
         x1, n_atoms = self._given_molecules(molecules)
         B = int(n_atoms.numel())
-        keep = _keep_atoms(keep, n_atoms)
+        keep = _keep_rows(keep, n_atoms)
         ks = [int(start_step)] * B if ks is None else ks
         Ts = [int(self.default_n_timesteps if n_timesteps is None else n_timesteps)] * B if Ts is None else Ts
         if len(ks) != B or len(Ts) != B:
@@ -395,7 +401,11 @@ class FlowMol:
         alphas = {(T, k): alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k] for T, k in pairs}
         sizes = n_atoms.tolist()
         given = _split_molecules(x1, sizes)
-        kept = torch.split(keep, sizes) if keep is not None else None
+        n_pairs = [n * (n - 1) // 2 for n in sizes]
+        if isinstance(keep, dict):          # per modality: {modality: one block of rows per molecule}
+            kept = {f: torch.split(v, n_pairs if f == 'e' else sizes) for f, v in keep.items()}
+        else:
+            kept = torch.split(keep, sizes) if keep is not None else None
         # ---- the library refuses a NULL previous endpoint with only some groups at t = 0: molecules that start at step 0 run in an engine call of their own
         parts = [[i for i in range(B) if ks[i] == 0], [i for i in range(B) if ks[i] > 0]]
         parts = [p for p in parts if p]
@@ -409,7 +419,11 @@ class FlowMol:
             keys = sorted({(Ts[i], ks[i]) for i in part})
             group = [keys.index((Ts[i], ks[i])) for i in part]
             state = eng.conditional_path(st1, torch.stack([alphas[key] for key in keys]), group if len(keys) > 1 else None, seed=int(seed))
-            spec = eng.inpaint_spec(st1, torch.cat([kept[i] for i in part]), int(seed)) if kept is not None else None
+            spec = None
+            if isinstance(kept, dict):
+                spec = eng.freeze_spec(st1, {f: torch.cat([blocks[i] for i in part]) for f, blocks in kept.items()}, int(seed))
+            elif kept is not None:
+                spec = eng.inpaint_spec(st1, torch.cat([kept[i] for i in part]), int(seed))
             t0 = time.perf_counter()
             if len(keys) == 1:
                 (T, k), traj, init = keys[0], None, None
@@ -437,6 +451,49 @@ class FlowMol:
     def inpaint(self, molecules, keep, n_timesteps=None, seed=None, mol_ids=None, **kwargs):
         """Generate the free atoms of ``molecules`` from the prior around the kept ones: ``resample(molecules, 0, n_timesteps, keep=keep, ...)``."""
         return self.resample(molecules, 0, n_timesteps, seed=seed, mol_ids=mol_ids, keep=keep, **kwargs)
+
+    def conformers(self, molecules, n_conformers=1, n_timesteps=None, seed=None, mol_ids=None, start_step=0, **kwargs):
+        """3D conformers of given molecular graphs: every molecule is repeated ``n_conformers`` times, molecule-major, every atom's type and charge and
+        every pair's bond order are frozen and the positions are left free -- ``resample(repeated molecules, start_step, n_timesteps, seed=seed,
+        mol_ids=mol_ids, keep={'a': all, 'c': all, 'e': all})``, whose other arguments and refusals it takes.  ``mol_ids`` (B * n_conformers entries,
+        default 0 .. B * n_conformers - 1) name the Philox streams: two conformers of a molecule differ because their streams do.  Returns the flat list of
+        B * n_conformers molecules (``return_tensors`` as in ``resample``); on models with alpha(1) = 1 the tokens of every result are the input's."""
+        if self.cfg.parameterization == 'endpoint':          # resample's refusal, before the molecules are read as tokens of a CTMC model
+            raise NotImplementedError('conformers: endpoint models are not supported (they have no masked conditional path)')
+        K = int(n_conformers)
+        if K < 1:
+            raise ValueError('n_conformers must be >= 1')
+        x1, n_atoms = self._given_molecules(molecules)
+        sizes = n_atoms.tolist()
+        given = _split_molecules(x1, sizes)
+        rep = [i for i in range(len(sizes)) for _ in range(K)]
+        tensors = {k: torch.cat([given[i][f'{k}_t'] for i in rep]) for k in 'xace'}
+        n_rep = n_atoms[rep]
+        N, U = int(n_rep.sum()), int((n_rep * (n_rep - 1) // 2).sum())
+        keep = {'a': torch.ones(N, dtype=torch.bool), 'c': torch.ones(N, dtype=torch.bool), 'e': torch.ones(U, dtype=torch.bool)}
+        return self.resample((tensors, n_rep), start_step, n_timesteps, seed=seed, mol_ids=mol_ids, keep=keep, **kwargs)
+
+    @torch.no_grad()
+    def rmsd(self, molecules_a, molecules_b, select=None, heavy=False) -> torch.Tensor:
+        """Aligned RMSD of ``molecules_a`` onto ``molecules_b``, molecule by molecule, in one launch on the device (``Engine.align_rmsd``): a (B,) float32
+        tensor on the CPU, the rmsd after centring and the optimal proper rotation (no reflection) over the selected atoms.  ``molecules_*`` as in
+        ``resample``; the sizes must match molecule by molecule (ValueError).  ``select``: a bool tensor over the concatenated atoms or one bool sequence
+        per molecule (None = all atoms); ``heavy``: only atoms whose type in ``molecules_b`` is neither 'H' nor the fake-atom token.  A molecule
+        without a selected atom gives 0.  With ``conformers``: ``model.rmsd(confs, [m for m in mols for _ in range(K)], heavy=True)``."""
+        xa, na = self._given_molecules(molecules_a)
+        xb, nb = self._given_molecules(molecules_b)
+        if na.tolist() != nb.tolist():
+            raise ValueError(f'rmsd: the molecules must match in size one by one, got {na.tolist()} and {nb.tolist()}')
+        sel = torch.ones(int(nb.sum()), dtype=torch.bool) if select is None else _keep_flat(select, nb.tolist(), 'select', 'atoms')
+        if heavy:
+            amap = list(self.cfg.atom_type_map)
+            light = [i for i, sym in enumerate(amap) if sym == 'H'] + [len(amap)]          # the fake atom's token follows the real types
+            sel = sel & ~torch.isin(xb['a_t'], torch.tensor(light))
+        eng = self.engine
+        eng.bind(nb)
+        out = eng.align_rmsd(xa['x_t'], xb['x_t'], None if select is None and not heavy else sel)
+        eng.synchronize()
+        return out[:, 2].cpu()
 
     def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
         """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --
@@ -732,32 +789,61 @@ ALLOWED_KWARGS = {
 RESAMPLE_KWARGS = {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'}       # resample(): Philox only, so no rng and no noise hooks
 
 
-def _keep_atoms(keep, n_atoms: torch.Tensor) -> Optional[torch.Tensor]:
-    """``keep`` of resample() / submit_from() as one bool tensor over the concatenated atoms, or None when nothing is kept.  ValueError for anything but a
-    bool tensor of N entries or one bool sequence per molecule, each of the molecule's length."""
-    if keep is None:
-        return None
-    sizes = n_atoms.tolist()
+def _keep_flat(keep, sizes, name: str, what: str) -> torch.Tensor:
+    """One ``keep`` entry as a bool tensor over the concatenated rows: ``keep`` is a bool tensor of sum(sizes) entries or one bool sequence per molecule,
+    molecule i's of sizes[i] entries (``what``: 'atoms' or 'pairs').  ValueError for anything else."""
     if torch.is_tensor(keep):
         if keep.dtype != torch.bool:
-            raise ValueError(f'keep must be a bool tensor, got {keep.dtype}')
+            raise ValueError(f'{name} must be a bool tensor, got {keep.dtype}')
         flat = keep.detach().cpu().reshape(-1)
     else:
         rows = list(keep)
         if len(rows) != len(sizes):
-            raise ValueError(f'keep has {len(rows)} entries for {len(sizes)} molecules (one bool sequence per molecule)')
+            raise ValueError(f'{name} has {len(rows)} entries for {len(sizes)} molecules (one bool sequence per molecule)')
         cols = []
         for i, (r, n) in enumerate(zip(rows, sizes)):
             r = r.detach().cpu().reshape(-1) if torch.is_tensor(r) else torch.as_tensor(list(r))
             if r.numel() != n:
-                raise ValueError(f'keep[{i}] has {r.numel()} entries, molecule {i} has {n} atoms')
-            if r.dtype != torch.bool:
-                raise ValueError(f'keep[{i}] must hold bools, got {r.dtype}')
-            cols.append(r)
-        flat = torch.cat(cols)
+                raise ValueError(f'{name}[{i}] has {r.numel()} entries, molecule {i} has {n} {what}')
+            if n and r.dtype != torch.bool:
+                raise ValueError(f'{name}[{i}] must hold bools, got {r.dtype}')
+            cols.append(r.to(torch.bool))
+        flat = torch.cat(cols) if cols else torch.zeros(0, dtype=torch.bool)
     if flat.numel() != sum(sizes):
-        raise ValueError(f'keep has {flat.numel()} entries, the molecules have {sum(sizes)} atoms')
+        raise ValueError(f'{name} has {flat.numel()} entries, the molecules have {sum(sizes)} {what}')
+    return flat
+
+
+def _keep_atoms(keep, n_atoms: torch.Tensor) -> Optional[torch.Tensor]:
+    """The whole-atom ``keep`` of resample() / submit_from() as one bool tensor over the concatenated atoms, or None when nothing is kept.  ValueError for
+    anything but a bool tensor of N entries or one bool sequence per molecule, each of the molecule's length."""
+    if keep is None:
+        return None
+    flat = _keep_flat(keep, n_atoms.tolist(), 'keep', 'atoms')
     return flat if bool(flat.any()) else None
+
+
+def _keep_rows(keep, n_atoms: torch.Tensor):
+    """``keep`` of resample() / submit_from() in either form: None when nothing is kept; a bool tensor over the concatenated atoms (the whole-atom form,
+    ``_keep_atoms``); or, for a dict {'x', 'a', 'c': atoms, 'e': unordered pairs}, a dict of bool tensors over the concatenated rows that holds the
+    modalities with a frozen row.  ValueError for an unknown key, a wrong length and a dtype other than bool."""
+    if not isinstance(keep, dict):
+        return _keep_atoms(keep, n_atoms)
+    unknown = [k for k in keep if k not in ('x', 'a', 'c', 'e')]
+    if unknown:
+        raise ValueError(f"keep has unknown keys {sorted(map(str, unknown))}: 'x', 'a', 'c' (per atom) and 'e' (per unordered pair) are the modalities")
+    sizes = n_atoms.tolist()
+    pairs = [n * (n - 1) // 2 for n in sizes]
+    rows = {f: _keep_flat(keep[f], pairs if f == 'e' else sizes, f"keep['{f}']", 'pairs' if f == 'e' else 'atoms') for f in 'xace' if keep.get(f) is not None}
+    rows = {f: v for f, v in rows.items() if bool(v.any())}
+    return rows or None
+
+
+def _pairs_of_atoms(keep_atom: torch.Tensor) -> torch.Tensor:
+    """One molecule's whole-atom keep as its pair flags, upper-triangle order: a pair is kept iff both its atoms are (the rule of fm_inpaint)."""
+    n = int(keep_atom.shape[0])
+    i, j = torch.triu_indices(n, n, 1)
+    return keep_atom[i] & keep_atom[j]
 
 
 def _split_molecules(state: Dict[str, torch.Tensor], sizes) -> List[Dict[str, torch.Tensor]]:

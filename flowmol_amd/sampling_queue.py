@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .engine import IntegrationRun, alpha_tables, make_step_plan
-from .model import _keep_atoms
+from .model import _keep_rows, _pairs_of_atoms
 
 
 class _Request:
@@ -24,8 +24,8 @@ class _Request:
         self.ticket, self.n, self.T, self.mol_id = ticket, n, T, mol_id
         self.pos = start      # the step it takes next: steps taken, or where a given molecule (submit_from) enters its schedule
         self.given = given    # submit_from: the molecule to corrupt {'x_t', 'a_t', 'c_t', 'e_t'} (CPU); None: start from the prior
-        self.keep = keep      # submit_from(keep=...): (n,) bool, the atoms that stay as given; None: nothing frozen
-        self.spec = None      # its rows of Engine.inpaint_spec, on the device, from admission on
+        self.keep = keep      # submit_from(keep=...): (n,) bool, the atoms that stay as given, or {modality: its rows' bools}; None: nothing frozen
+        self.spec = None      # its rows of Engine.inpaint_spec / freeze_spec, on the device, from admission on
         self.state = None     # {'x_t', 'a_t', 'c_t', 'e_t'}: this molecule's rows, on the device
         self.prev = None      # {'x', 'a', 'c', 'e'}: its previous endpoint prediction
 
@@ -69,12 +69,19 @@ class SamplingQueue:
         ``n_timesteps[i]``-point schedule at admission and joins the running batch from there; ``start_step >= n_timesteps - 1`` retires at once with the
         corrupted state.  ``molecules`` / ``start_step`` / ``n_timesteps`` / ``mol_ids`` as in ``resample`` (ids default to the ticket numbers).  Every
         molecule is, bit for bit, ``model.resample([mol], start_step, n_timesteps, seed, mol_ids=[id])``.  ``keep``: the atoms that stay as given, as in
-        ``resample`` -- such molecules are admitted into the running batch like any other and are, bit for bit, their ``resample(..., keep=...)`` run alone."""
+        ``resample`` -- such molecules are admitted into the running batch like any other and are, bit for bit, their ``resample(..., keep=...)`` run alone.
+        Both forms of ``keep`` are taken; a batch that holds requests of both is served in the per-modality form, of which the whole-atom form is a case."""
         x1, n_atoms = self.model._given_molecules(molecules)
         sizes = n_atoms.tolist()
-        keep = _keep_atoms(keep, n_atoms)
-        kept = torch.split(keep, sizes) if keep is not None else [None] * len(sizes)
         B = len(sizes)
+        n_pairs = [n * (n - 1) // 2 for n in sizes]
+        keep = _keep_rows(keep, n_atoms)
+        if isinstance(keep, dict):          # per modality: every molecule gets the modalities in which it has a frozen row
+            cols = {f: torch.split(v, n_pairs if f == 'e' else sizes) for f, v in keep.items()}
+            kept = [{f: c[i] for f, c in cols.items() if bool(c[i].any())} or None for i in range(B)]
+        else:
+            kept = list(torch.split(keep, sizes)) if keep is not None else [None] * B
+            kept = [k if k is not None and bool(k.any()) else None for k in kept]
         per = lambda v, default: ([int(default if v is None else v)] * B if v is None or isinstance(v, int) or (torch.is_tensor(v) and v.dim() == 0)
                                   else [int(x) for x in v])
         ks, Ts = per(start_step, 0), per(n_timesteps, self.model.default_n_timesteps)
@@ -83,14 +90,12 @@ class SamplingQueue:
             raise ValueError('start_step / n_timesteps / mol_ids must give one entry per molecule')
         if any(T < 1 or k < 0 or k > T - 1 for k, T in zip(ks, Ts)):
             raise ValueError('start_step must lie in 0 .. n_timesteps - 1 (and n_timesteps >= 1)')
-        pairs = [n * (n - 1) // 2 for n in sizes]
-        cols = {f: torch.split(v, pairs if f == 'e_t' else sizes) for f, v in x1.items()}
+        cols = {f: torch.split(v, n_pairs if f == 'e_t' else sizes) for f, v in x1.items()}
         tickets = []
         for i in range(B):
             t = self._next_ticket
             self._next_ticket += 1
-            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1},
-                                          kept[i] if kept[i] is not None and bool(kept[i].any()) else None))
+            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1}, kept[i]))
             tickets.append(t)
         return tickets
 
@@ -117,22 +122,43 @@ class SamplingQueue:
 
     @staticmethod
     def _split_spec(spec, sizes):
-        """The per-molecule rows of an ``Engine.inpaint_spec`` dict (views)."""
+        """The per-molecule rows of an ``Engine.inpaint_spec`` / ``freeze_spec`` dict (views; a modality the spec leaves out stays None)."""
         pairs = [n * (n - 1) // 2 for n in sizes]
-        cols = {k: torch.split(v, pairs if k in ('keep_pair', 'e1', 'u_e') else sizes) for k, v in spec.items()}
-        return [{k: cols[k][i] for k in spec} for i in range(len(sizes))]
+        cols = {k: torch.split(v, pairs if k in ('keep_pair', 'keep_e', 'e1', 'u_e') else sizes) for k, v in spec.items() if v is not None}
+        return [{k: (cols[k][i] if k in cols else None) for k in spec} for i in range(len(sizes))]
+
+    @staticmethod
+    def _modal(keep):
+        """A request's ``keep`` in the per-modality form: the whole-atom form freezes x, a, c of its atoms and the pairs between two of them."""
+        return keep if isinstance(keep, dict) else {'x': keep, 'a': keep, 'c': keep, 'e': _pairs_of_atoms(keep)}
+
+    _SPEC_ROWS = {'x0': (torch.float32, lambda n, u: (n, 3)), 'x1c': (torch.float32, lambda n, u: (n, 3)), 'a1': (torch.int32, lambda n, u: (n,)),
+                  'c1': (torch.int32, lambda n, u: (n,)), 'e1': (torch.int32, lambda n, u: (u,)), 'u_a': (torch.float32, lambda n, u: (n,)),
+                  'u_c': (torch.float32, lambda n, u: (n,)), 'u_e': (torch.float32, lambda n, u: (u,))}
+    _OWNER = {'x0': 'x', 'x1c': 'x', 'a1': 'a', 'c1': 'c', 'e1': 'e', 'u_a': 'a', 'u_c': 'c', 'u_e': 'e'}
 
     def _batch_spec(self, run):
-        """The running batch's spec from its molecules' rows; a molecule without frozen atoms contributes zero flags (its other rows are never read)."""
+        """The running batch's spec from its molecules' rows; a molecule without frozen rows contributes zero flags (its other rows are never read).
+        Whole-atom requests alone give an ``inpaint_spec``; as soon as one request is per modality the batch is a ``freeze_spec``, in which a whole-atom
+        request's rows stand as x = a = c = its atoms, e = the pairs between two of them, and a modality nobody freezes stays None."""
         if all(r.spec is None for r in run):
             return None
         dev = self.model.engine.device
-        shapes = {'keep_atom': (torch.uint8, lambda n, u: (n,)), 'keep_pair': (torch.uint8, lambda n, u: (u,)), 'x0': (torch.float32, lambda n, u: (n, 3)),
-                  'x1c': (torch.float32, lambda n, u: (n, 3)), 'a1': (torch.int32, lambda n, u: (n,)), 'c1': (torch.int32, lambda n, u: (n,)),
-                  'e1': (torch.int32, lambda n, u: (u,)), 'u_a': (torch.float32, lambda n, u: (n,)), 'u_c': (torch.float32, lambda n, u: (n,)),
-                  'u_e': (torch.float32, lambda n, u: (u,))}
-        return {k: torch.cat([r.spec[k] if r.spec is not None else torch.zeros(shp(r.n, r.n * (r.n - 1) // 2), dtype=dt, device=dev) for r in run]).contiguous()
-                for k, (dt, shp) in shapes.items()}
+        zeros = lambda r, dt, shp: torch.zeros(shp(r.n, r.n * (r.n - 1) // 2), dtype=dt, device=dev)
+        u8 = torch.uint8
+        if all('keep_atom' in r.spec for r in run if r.spec is not None):
+            shapes = {'keep_atom': (u8, lambda n, u: (n,)), 'keep_pair': (u8, lambda n, u: (u,)), **self._SPEC_ROWS}
+            return {k: torch.cat([r.spec[k] if r.spec is not None else zeros(r, dt, shp) for r in run]).contiguous() for k, (dt, shp) in shapes.items()}
+        flags = {r.ticket: {f: v.to(u8).to(dev) for f, v in self._modal(r.keep).items()} for r in run if r.spec is not None}
+        live = {f for fl in flags.values() for f in fl}
+        spec = {name: None for name, _ in _lib.fm_freeze._fields_}
+        for f in live:
+            shp = (lambda n, u: (u,)) if f == 'e' else (lambda n, u: (n,))
+            spec[f'keep_{f}'] = torch.cat([flags[r.ticket][f] if r.spec is not None and f in flags[r.ticket] else zeros(r, u8, shp) for r in run]).contiguous()
+        for k, (dt, shp) in self._SPEC_ROWS.items():
+            if self._OWNER[k] in live:
+                spec[k] = torch.cat([r.spec[k] if r.spec is not None and r.spec.get(k) is not None else zeros(r, dt, shp) for r in run]).contiguous()
+        return spec
 
     def _admit(self):
         """Newcomers, grouped by schedule and entry step, take their first step through fm_integrate on a bind of their own -- from the prior (step 0:
@@ -160,7 +186,12 @@ class SamplingQueue:
                 alpha = alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k]
                 st1 = eng.make_state(x1['x_t'], x1['a_t'], x1['c_t'], x1['e_t'])
                 state = eng.conditional_path(st1, alpha, seed=self.seed)
-                if any(r.keep is not None for r in reqs):
+                if any(isinstance(r.keep, dict) for r in reqs):          # one per-modality request: the group's first step runs in that form
+                    none = lambda r, f: torch.zeros(r.n * (r.n - 1) // 2 if f == 'e' else r.n, dtype=torch.bool)
+                    modal = [self._modal(r.keep) if r.keep is not None else {} for r in reqs]
+                    live = [f for f in 'xace' if any(f in m for m in modal)]
+                    spec = eng.freeze_spec(st1, {f: torch.cat([m[f] if f in m else none(r, f) for r, m in zip(reqs, modal)]) for f in live}, self.seed)
+                elif any(r.keep is not None for r in reqs):
                     spec = eng.inpaint_spec(st1, torch.cat([r.keep if r.keep is not None else torch.zeros(r.n, dtype=torch.bool) for r in reqs]), self.seed)
             else:
                 state = eng.prior_state(eng.prior_philox(self.seed))

@@ -60,7 +60,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 12
+#define FM_ABI_VERSION 13
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -424,6 +424,51 @@ int fm_integrate_inpaint(fm_ctx* ctx, void* stream, const fm_state* state, int n
                          const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
                          const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
                          const fm_inpaint* inp, const float* alpha_next, const float* alpha_next_dev);
+
+/* --- ABI 13: frozen rows per modality -- fm_ctmc_step_inpaint / fm_integrate_inpaint with one keep array per modality in place of keep_atom: freeze every type, charge
+ * and bond and let the positions run (conformers of a given graph), fix a pose and let the chemistry run, or freeze a bond between two free atoms.
+ * A step is EXACTLY the step of fm_ctmc_step / fm_integrate / fm_integrate_mixed on all rows: every draw and every sampled endpoint token (fm_sampled, the sink's
+ * a1 / c1 / e1 / x1 frames) is the plain step's.  Then, inside the store that writes the new state, the flagged rows are overwritten:
+ *   a position row with keep_x[atom] != 0      x = (1 - ax) x0 + ax x1c, the three operations rounded separately (fm_conditional_path's arithmetic)
+ *   an a / c / e row with ITS OWN flag set     tok = u < 1 - alpha ? mask token : tok1
+ * The four flags are independent: a bond may be frozen between two free atoms, a type without the charge or the position.  alpha_next and the path inputs x0, x1c,
+ * a1 / c1 / e1, u_a / u_c / u_e are those of fm_inpaint.  Everything in the struct is an INPUT: nothing is written, there is no pair scratch and no setup launch.
+ * A NULL keep_* means nothing of that modality is frozen; that modality's path inputs (x0 and x1c for x, tok1 and u for a, c, e) are then not read and may be NULL too
+ * -- the conformer case passes no x0 and no x1c.
+ * Equivalence with ABI 12: keep_x = keep_a = keep_c = keep_atom and keep_e[u] = both atoms of pair u kept gives the bits of fm_*_inpaint(keep_atom), whose kernels these
+ * are.  With every flag zero, or every keep pointer NULL, the calls give the bits of the plain entry points.
+ * Neither call synchronises or allocates, and no workspace beyond the bind's is needed.  FM_ERR_INVALID, with a message and before anything is enqueued, for an
+ * endpoint model; a member equal to a pointer of state, dst / dst_a / dst_b, sampled or the sink; a modality whose keep pointer is given while one of its path inputs
+ * is NULL (the pair modality only in a batch that has pairs); and, in fm_integrate_freeze, what fm_integrate_inpaint refuses (n_groups outside 1..32; for n_groups > 1
+ * fm_integrate_mixed's refusals). */
+typedef struct fm_freeze {
+    const uint8_t* keep_x; const uint8_t* keep_a; const uint8_t* keep_c;      /* (N) one flag per atom of the bound batch, fake atoms included; NULL = none */
+    const uint8_t* keep_e;        /* (U) one flag per unordered pair, upper-triangle order: the order of e_t; NULL = none */
+    const float* x0;              /* (N,3) position prior of the path (fm_cond_tape.x0) */
+    const float* x1c;             /* (N,3) given positions minus the whole molecule's mean (fm_remove_com) */
+    const int32_t* a1; const int32_t* c1;      /* (N) given tokens, real categories */
+    const int32_t* e1;            /* (U) */
+    const float* u_a; const float* u_c;        /* (N) uniforms of the path (fm_cond_tape.u_a / u_c) */
+    const float* u_e;             /* (U) */
+} fm_freeze;
+/* argument lists of fm_ctmc_step_inpaint / fm_integrate_inpaint, const fm_freeze* in place of const fm_inpaint* */
+int fm_ctmc_step_freeze(fm_ctx* ctx, void* stream, const fm_state* state, const fm_dst* dst, const fm_step_noise* noise, const fm_step_scalars* sc,
+                        const fm_sampled* sampled, const fm_freeze* fz, const float* alpha_next);
+int fm_integrate_freeze(fm_ctx* ctx, void* stream, const fm_state* state, int n_steps, int n_groups, const fm_step_scalars* steps,
+                        const fm_step_scalars* steps_dev, const int32_t* active, const int32_t* active_dev, const int32_t* mol_group, const float* temb,
+                        const fm_step_noise* noise, const fm_dst* prev0, const fm_dst* dst_a, const fm_dst* dst_b, const fm_traj_sink* sink, int* final_dst,
+                        const fm_freeze* fz, const float* alpha_next, const float* alpha_next_dev);
+
+/* Aligned RMSD of two coordinate sets xa, xb (N,3) of the bound batch, molecule by molecule over its selected atoms (select: (N) uint8, NULL = all), on the device:
+ *   out (n_mols, 4) = {count of selected atoms, rmsd after centring both sets on their selected atoms, rmsd after the optimal PROPER rotation of xa onto xb, 0}
+ *   xa_aligned (N,3), may be NULL: ALL atoms of xa moved by the transform fitted on the selected ones, R (xa - mean_a) + mean_b
+ * The rotation maximises the overlap over det = +1 (no reflection: a mirror image is not a conformer): the eigenvector of the largest eigenvalue of Horn's 4x4
+ * quaternion matrix, by a fixed number of cyclic Jacobi sweeps in float32; the aligned rmsd is summed from the explicit residuals R a - b, so near-identical
+ * conformers do not cancel.  One wave per molecule and sums in a fixed per-molecule order: a molecule's bits do not depend on its batch.
+ * A molecule with no selected atom gives {0, 0, 0, 0} and leaves its rows of xa_aligned equal to xa.  Does not synchronise, allocates nothing.
+ * FM_ERR_INVALID if xa_aligned or out aliases an input or each other. */
+int fm_align_rmsd(fm_ctx* ctx, void* stream, const float* xa, const float* xb, const uint8_t* select /* (N), may be NULL = all */, float* out /* (n_mols, 4) */,
+                  float* xa_aligned /* (N,3), may be NULL */);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
