@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 13
+FM_ABI_VERSION = 14
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
@@ -168,6 +168,10 @@ _EXPORTS = {
                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(fm_step_noise), C.POINTER(fm_dst), C.POINTER(fm_dst),
                                       C.POINTER(fm_dst), C.POINTER(fm_traj_sink), C.POINTER(C.c_int), C.POINTER(fm_freeze), C.POINTER(C.c_float), C.c_void_p]),
     'fm_align_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ABI 14: conformer ensembles -- pairwise symmetry-aware RMSD, threshold pruning
+    'fm_pair_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p]),
+    'fm_prune_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

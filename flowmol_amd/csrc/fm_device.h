@@ -112,6 +112,23 @@ __device__ __forceinline__ float fm_div_rn(float a, float b) {
 #pragma clang fp contract(off)
     return a / b;
 }
+// the same in float64 (the residual pass of fm_k_pair_rmsd)
+__device__ __forceinline__ double fm_mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double fm_add_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ double fm_sub_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ double fm_div_rn(double a, double b) {
+#pragma clang fp contract(off)
+    return a / b;
+}
 
 // Gaussian RBF, reference flowmol/utils/embedding.py:19-34: mu_k = k*Dmax/(R-1), sigma = Dmax/R
 __device__ __forceinline__ float fm_rbf(float d, int k, float mu_step, float inv_sigma) {

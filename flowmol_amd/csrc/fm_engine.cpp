@@ -1167,6 +1167,7 @@ int fm_batch_bind(fm_ctx* c, void* stream, const int32_t* n_atoms, int B, void* 
         if (rc) return rc;
     }
     c->ws = w;
+    c->node_off_h.assign(no, no + B1);
     c->s_tab = w.s_tab_base;
     c->tab_slot_floats = (size_t)align_up(c->tab_rows, FM_TM) * 256;
     Launch L{c, st};
@@ -1583,6 +1584,54 @@ int fm_align_rmsd(fm_ctx* c, void* stream, const float* xa, const float* xb, con
     if (xa_aligned && (const void*)xa_aligned == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: xa_aligned aliases out", fn);
     Launch L{c, (hipStream_t)stream};
     L("align_rmsd", fm_k_align_rmsd, dim3(c->ws.b.B), dim3(64), 0, xa, xb, (const unsigned char*)select, (const int*)c->ws.b.mol_node_off, out, xa_aligned);
+    return L.rc;
+}
+
+// Symmetry-aware aligned RMSD of pairs of molecules of the bound batch (fm_k_pair_rmsd: one wave per pair, one lane per permutation row).  pairs_host is read
+// here, for the refusals; the kernel reads the device copy.
+int fm_pair_rmsd(fm_ctx* c, void* stream, const float* x, int n_pairs, const int32_t* pairs_host, const int32_t* pairs, const uint8_t* select,
+                 const int32_t* perm_set, const int32_t* set_off, const int32_t* perms, int n_sets, float* out, int32_t* best_perm) {
+    const char* const fn = "fm_pair_rmsd";
+    if (const int rc = bound_check(c, fn, x && out && (n_pairs <= 0 || (pairs_host && pairs)))) return rc;
+    if (n_pairs < 0) return fail(c, FM_ERR_INVALID, "%s: n_pairs = %d", fn, n_pairs);
+    const bool table = perm_set || set_off || perms;
+    if (table && !(perm_set && set_off && perms && n_sets >= 1))
+        return fail(c, FM_ERR_INVALID, "%s: perm_set, set_off and perms come together with n_sets >= 1, or all NULL with n_sets = 0 (the identity only)", fn);
+    if (!table && n_sets != 0) return fail(c, FM_ERR_INVALID, "%s: n_sets = %d without a permutation table", fn, n_sets);
+    const void* const in[] = {x, pairs, select, perm_set, set_off, perms};
+    for (const void* p : in) {
+        if (p && p == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: out aliases an input", fn);
+        if (p && best_perm && p == (const void*)best_perm) return fail(c, FM_ERR_INVALID, "%s: best_perm aliases an input", fn);
+    }
+    if (best_perm && (const void*)best_perm == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: best_perm aliases out", fn);
+    const int B = c->ws.b.B;
+    const std::vector<int32_t>& off = c->node_off_h;
+    for (int p = 0; p < n_pairs; ++p) {
+        const int a = pairs_host[2 * p], b = pairs_host[2 * p + 1];
+        if (a < 0 || a >= B || b < 0 || b >= B) return fail(c, FM_ERR_INVALID, "%s: pair %d = (%d, %d) names a molecule outside 0..%d", fn, p, a, b, B - 1);
+        if (off[a + 1] - off[a] != off[b + 1] - off[b])
+            return fail(c, FM_ERR_INVALID, "%s: pair %d = (%d, %d): molecules of unequal size, %d and %d atoms", fn, p, a, b, off[a + 1] - off[a], off[b + 1] - off[b]);
+    }
+    Launch L{c, (hipStream_t)stream};
+    FmPairRmsdArgs g{};
+    g.x = x; g.node_off = c->ws.b.mol_node_off; g.pairs = pairs; g.sel = select; g.perm_set = perm_set; g.set_off = set_off; g.perms = perms; g.n_sets = n_sets;
+    g.out = out; g.best = best_perm;
+    L("pair_rmsd", fm_k_pair_rmsd, dim3(n_pairs), dim3(64), 0, g);
+    return L.rc;
+}
+
+// Greedy RMSD-threshold pruning of conformer groups (fm_k_prune_rmsd: one wave per group).  Needs no bound batch: every array is the caller's.
+int fm_prune_rmsd(fm_ctx* c, void* stream, int n_groups, const int32_t* group_off, const float* d, const int32_t* tri_off, float threshold, uint8_t* keep,
+                  int32_t* rep) {
+    const char* const fn = "fm_prune_rmsd";
+    if (!c || !group_off || !tri_off || !keep || !rep) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    if (n_groups < 0) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d", fn, n_groups);
+    const void* const in[] = {group_off, d, tri_off};
+    for (const void* p : in)
+        if (p && (p == (const void*)keep || p == (const void*)rep)) return fail(c, FM_ERR_INVALID, "%s: keep or rep aliases an input", fn);
+    if ((const void*)keep == (const void*)rep) return fail(c, FM_ERR_INVALID, "%s: keep aliases rep", fn);
+    Launch L{c, (hipStream_t)stream};
+    L("prune_rmsd", fm_k_prune_rmsd, dim3(n_groups), dim3(64), 0, group_off, d, tri_off, threshold, (unsigned char*)keep, rep);
     return L.rc;
 }
 

@@ -123,6 +123,7 @@ struct fm_ctx {
     bool bound = false;
     BatchPlan plan{};         // the bound batch's launch choices (plan_batch)
     Workspace ws{};           // the bound batch's pointers into the caller's workspace (ws_carve)
+    std::vector<int32_t> node_off_h;      // [B+1] host copy of ws.b.mol_node_off: what fm_pair_rmsd checks its molecule indices against
     float* s_tab = nullptr; size_t tab_slot_floats = 0;      // the current step's embedding table, one of the FM_TAB_SLOTS at ws.s_tab_base; floats per slot
     const int* tab_slot = nullptr;      // per-molecule time: the caller's device (n_mols) table slot of every molecule, counted from s_tab; null = one table (set with s_tab)
     // ---- pinned host staging of the per-molecule descriptor arrays (fm_batch_bind / fm_set_molecule_ids: 16 B per molecule).  The copies

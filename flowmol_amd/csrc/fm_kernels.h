@@ -2568,6 +2568,139 @@ static __global__ void __launch_bounds__(64) fm_k_align_rmsd(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// Symmetry-aware aligned RMSD of pairs of molecules of ONE coordinate set (fm_pair_rmsd): pair p = (ma, mb), two molecules of the same size n ->
+// out[p] = {selected atoms, min over the permutation rows q of the rmsd after centring and the optimal PROPER rotation of a[i] onto b[q[i]]}, best[p] = the
+// lowest row index that attains the minimum.  sel is read at the rows of ma.  The rows of a pair are those of the set perm_set[ma] (elements set_off[s] ..
+// set_off[s + 1] of perms, n local atom indices each); no table, a set id outside 0 .. n_sets - 1 or an empty set: the identity alone.  A row is a permutation
+// that maps selected atoms onto selected atoms and is the identity on the rest (precondition; an entry outside 0 .. n - 1 is read as i, so nothing is read out
+// of the molecule).
+// One wave per pair.  SUMMATION ORDER (canonical: a function of the two molecules, the selection and the SET of rows):
+//   1  the count and the two means as in fm_k_align_rmsd round 1 -- lane-strided from +0, xor tree, relative to each molecule's first atom; b's mean runs over
+//      the selected local indices, which every row maps onto themselves, so it does not depend on the row
+//   2  lane l takes the rows l, l + 64, ... and runs a whole alignment for each, alone: S[i][j] = sum a_i b_j over the selected atoms in ascending atom order
+//      from +0, fm_horn_rotation, then sum |R a - b[q]|^2 from the explicit residuals in the same order -- this last pass in float64 (the float32 inputs, means
+//      and R widened exactly): a residual is a small difference of coordinate-sized numbers, and rounding it in float32 costs several ulp of a small rmsd
+//   3  the smallest residual sum (ties: the lowest row) through the xor tree, which every lane enters whatever its row count; a NaN sum gives a NaN rmsd
+// Every product is separately rounded, in either precision.  With the identity alone lane 0 works and 63 lanes wait.
+// ------------------------------------------------------------------------------------------------
+struct FmPairRmsdArgs {
+    const float* x; const int* node_off; const int* pairs; const unsigned char* sel;
+    const int* perm_set; const int* set_off; const int* perms; int n_sets;
+    float* out; int* best;
+};
+static __global__ void __launch_bounds__(64) fm_k_pair_rmsd(FmPairRmsdArgs g) {
+    const int pr = blockIdx.x, lane = threadIdx.x;
+    const int mol_a = g.pairs[pr * 2], mol_b = g.pairs[pr * 2 + 1];
+    const int a0 = g.node_off[mol_a], n = g.node_off[mol_a + 1] - a0, b0 = g.node_off[mol_b];
+    const float* const xa = g.x + (size_t)a0 * 3;
+    const float* const xb = g.x + (size_t)b0 * 3;
+    const unsigned char* const sel = g.sel ? g.sel + a0 : nullptr;
+    float oa[3] = {0.f, 0.f, 0.f}, ob[3] = {0.f, 0.f, 0.f};
+    if (n > 0) for (int k = 0; k < 3; ++k) { oa[k] = xa[k]; ob[k] = xb[k]; }
+    float cnt = 0.f, ma[3] = {0.f, 0.f, 0.f}, mb[3] = {0.f, 0.f, 0.f};
+    for (int i = lane; i < n; i += 64) {
+        if (sel && !sel[i]) continue;
+        cnt += 1.f;
+        for (int k = 0; k < 3; ++k) { ma[k] = fm_add_rn(ma[k], fm_sub_rn(xa[i * 3 + k], oa[k])); mb[k] = fm_add_rn(mb[k], fm_sub_rn(xb[i * 3 + k], ob[k])); }
+    }
+    cnt = fm_wave_sum(cnt);
+    if (cnt == 0.f) {      // wave-uniform: nothing selected
+        if (lane < 2) g.out[pr * 2 + lane] = 0.f;
+        if (lane == 0 && g.best) g.best[pr] = 0;
+        return;
+    }
+    for (int k = 0; k < 3; ++k) { ma[k] = fm_div_rn(fm_wave_sum(ma[k]), cnt); mb[k] = fm_div_rn(fm_wave_sum(mb[k]), cnt); }
+    int n_rows = 1;
+    const int* rows = nullptr;
+    if (g.perms) {
+        const int s = g.perm_set[mol_a];
+        if (s >= 0 && s < g.n_sets) {
+            const int e0 = g.set_off[s], cnt_rows = (g.set_off[s + 1] - e0) / n;
+            if (cnt_rows > 0) { n_rows = cnt_rows; rows = g.perms + e0; }
+        }
+    }
+    double best_d = __builtin_huge_val();
+    int best_q = 0x7fffffff, bad = 0;
+    for (int q = lane; q < n_rows; q += 64) {      // lanes hold different row counts: nothing in here crosses lanes
+        const int* const row = rows ? rows + (size_t)q * n : nullptr;
+        float S[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+        for (int i = 0; i < n; ++i) {
+            if (sel && !sel[i]) continue;
+            int j = row ? row[i] : i;
+            j = (unsigned)j < (unsigned)n ? j : i;
+            float a[3], b[3];
+            for (int k = 0; k < 3; ++k) { a[k] = fm_sub_rn(fm_sub_rn(xa[i * 3 + k], oa[k]), ma[k]); b[k] = fm_sub_rn(fm_sub_rn(xb[j * 3 + k], ob[k]), mb[k]); }
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) S[r][c] = fm_add_rn(S[r][c], fm_mul_rn(a[r], b[c]));
+        }
+        float R[9];
+        fm_horn_rotation(S, R);
+        double d = 0.0;      // the residual pass in float64: e ~ 0.1 is a difference of numbers ~ 2, and its float32 rounding alone is a few ulp of the rmsd
+        for (int i = 0; i < n; ++i) {
+            if (sel && !sel[i]) continue;
+            int j = row ? row[i] : i;
+            j = (unsigned)j < (unsigned)n ? j : i;
+            double a[3];
+            for (int k = 0; k < 3; ++k) a[k] = fm_sub_rn(fm_sub_rn((double)xa[i * 3 + k], (double)oa[k]), (double)ma[k]);
+            for (int k = 0; k < 3; ++k) {
+                const double r = fm_add_rn(fm_add_rn(fm_mul_rn((double)R[k * 3], a[0]), fm_mul_rn((double)R[k * 3 + 1], a[1])), fm_mul_rn((double)R[k * 3 + 2], a[2]));
+                const double e = fm_sub_rn(r, fm_sub_rn(fm_sub_rn((double)xb[j * 3 + k], (double)ob[k]), (double)mb[k]));
+                d = fm_add_rn(d, fm_mul_rn(e, e));
+            }
+        }
+        if (d != d) bad = 1;
+        if (d < best_d) { best_d = d; best_q = q; }      // rows in ascending order per lane: a tie keeps the lower row
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {      // all 64 lanes, whatever their row counts; the float64 sum travels as its two halves
+        const unsigned long long u = __builtin_bit_cast(unsigned long long, best_d);
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(u & 0xffffffffull), o), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), o);
+        const double od = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+        const int oq = __shfl_xor(best_q, o);
+        if (od < best_d || (od == best_d && oq < best_q)) { best_d = od; best_q = oq; }
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (lane == 0) {
+        g.out[pr * 2] = cnt;
+        g.out[pr * 2 + 1] = any_bad ? __builtin_nanf("") : sqrtf((float)fm_div_rn(best_d, (double)cnt));
+        if (g.best) g.best[pr] = any_bad || best_q == 0x7fffffff ? 0 : best_q;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Greedy RMSD-threshold pruning of conformer groups (fm_prune_rmsd; the rule of RDKit's pruneRmsThresh with the representative recorded).  Group g = the
+// conformers group_off[g] .. group_off[g + 1] - 1, K of them; d + tri_off[g] = its strict upper triangle, row-major (i < j).  For i = 0, 1, ... in order: among
+// the KEPT j < i the one with the smallest d(j, i), ties to the lowest j; d < thr drops i (keep 0, rep = j), anything else -- a NaN included -- keeps it (keep 1,
+// rep = i); rep holds indices of the concatenated conformers, group_off[g] + j.  One wave per group; comparisons only.  Lane l scans j = l, l + 64, ... in ascending order; lane (i & 63) owns conformer i: it stores i's flag and
+// is the only lane that reads it back, so no store is read by another lane.
+// ------------------------------------------------------------------------------------------------
+static __global__ void __launch_bounds__(64) fm_k_prune_rmsd(const int* __restrict__ group_off, const float* __restrict__ d, const int* __restrict__ tri_off,
+                                                             float thr, unsigned char* keep, int* __restrict__ rep) {
+    const int grp = blockIdx.x, lane = threadIdx.x;
+    const int m0 = group_off[grp], K = group_off[grp + 1] - m0;
+    const float* const tri = d + tri_off[grp];
+    for (int i = 0; i < K; ++i) {      // wave-uniform: every lane takes every i
+        float best = __builtin_huge_valf();
+        int best_j = 0x7fffffff;
+        for (int j = lane; j < i; j += 64) {
+            if (!keep[m0 + j]) continue;
+            const float v = tri[(size_t)j * (size_t)(2 * K - j - 1) / 2 + (size_t)(i - j - 1)];
+            if (v < best) { best = v; best_j = j; }
+        }
+        bool drop = false;
+        if (__ballot(best < thr) != 0ull) {      // wave-uniform: some kept conformer is nearer than the threshold
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(best, o);
+                const int oj = __shfl_xor(best_j, o);
+                if (ov < best || (ov == best && oj < best_j)) { best = ov; best_j = oj; }
+            }
+            drop = true;
+        }
+        if (lane == (i & 63)) { keep[m0 + i] = drop ? 0 : 1; rep[m0 + i] = m0 + (drop ? best_j : i); }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Valence stability + connectivity of the sampled molecules straight from the final tokens (reference
 // flowmol/analysis/metrics.py:96-117,333-363 with molecule_builder.py:138-157,217-265: fake atoms removed,
 // mask bond token = no bond, valency = sum of bond orders with aromatic = 1.5).  One workgroup per molecule.

@@ -938,6 +938,113 @@ class Engine:
         self._keep = [xa, xb, sel, out, moved]
         return (out, moved) if aligned else out
 
+    # ------------------------------------------------------------------ conformer ensembles: pairwise RMSD, pruning
+    def pair_rmsd(self, x: torch.Tensor, pairs, select=None, perm_sets=None, best: bool = False):
+        """Symmetry-aware aligned RMSD of pairs of molecules of the bound batch, one launch on the device (fm_pair_rmsd): ``x`` (N,3) the batch's atoms,
+        ``pairs`` (P,2) molecule indices, each pair of equal size.  Returns (P,2) float32 on the device = {selected atoms, the smallest rmsd over the
+        permutation rows after centring and the optimal proper rotation of a[i] onto b[row[i]]}; with ``best`` also (P,) int32, the lowest row index that
+        attains it.  ``select`` ((N,) bool, None = all): the atoms the fit runs over, read at the first molecule of a pair -- both molecules of a pair
+        must carry the same flags.  ``perm_sets`` = (perm_set (B,) set id per molecule or -1, [rows (P_s, n) per set]) or None for the identity only: the
+        rows of a pair are those of its first molecule's set; a row must be a permutation of 0..n-1 that maps selected atoms onto selected atoms and is
+        the identity on the rest.  ValueError, before the call, for anything else.  The two numbers of a pair do not depend on the rest of the batch, on
+        the pair's place in ``pairs`` or on the order of the rows; the row index does depend on that order.  Does not synchronise."""
+        d = self.device
+        x = x.detach().to(d, torch.float32).contiguous()
+        if tuple(x.shape) != (self.N, 3):
+            raise ValueError(f'x must be ({self.N}, 3): the atoms of the bound batch')
+        pr = torch.as_tensor(pairs).detach().to('cpu', torch.int32).reshape(-1, 2).contiguous()
+        P = int(pr.shape[0])
+        sizes = self.n_atoms
+        off = torch.zeros(self.B + 1, dtype=torch.int64)
+        off[1:] = torch.cumsum(sizes, 0)
+        if P and (int(pr.min()) < 0 or int(pr.max()) >= self.B):
+            raise ValueError(f'pairs must name molecules 0 .. {self.B - 1} of the bound batch')
+        pa, pb = pr[:, 0].long(), pr[:, 1].long()
+        if P and not torch.equal(sizes[pa], sizes[pb]):
+            k = int((sizes[pa] != sizes[pb]).nonzero()[0])
+            raise ValueError(f'pair {k} = ({int(pa[k])}, {int(pb[k])}): the sizes of a pair differ, {int(sizes[pa[k]])} and {int(sizes[pb[k]])} atoms')
+        sel_h = None
+        if select is not None:
+            sel_h = torch.as_tensor(select).detach().cpu().reshape(-1) != 0
+            if sel_h.shape[0] != self.N:
+                raise ValueError(f'select has {sel_h.shape[0]} entries, the bound batch {self.N} atoms')
+            if P:
+                n_p = sizes[pa]
+                local = torch.arange(int(n_p.sum())) - torch.repeat_interleave(torch.cumsum(n_p, 0) - n_p, n_p)
+                ia, ib = torch.repeat_interleave(off[pa], n_p) + local, torch.repeat_interleave(off[pb], n_p) + local
+                if not torch.equal(sel_h[ia], sel_h[ib]):
+                    raise ValueError('select must flag the same atoms in both molecules of a pair')
+        table = (None, None, None)
+        n_sets = 0
+        if perm_sets is not None:
+            ps, rows = perm_sets
+            ps = torch.as_tensor(ps).detach().to('cpu', torch.int32).reshape(-1)
+            rows = [torch.as_tensor(r).detach().to('cpu', torch.int64) for r in rows]
+            n_sets = len(rows)
+            if ps.shape[0] != self.B or (self.B and (int(ps.min()) < -1 or int(ps.max()) >= n_sets)):
+                raise ValueError(f'perm_set must hold one set id in -1 .. {n_sets - 1} per bound molecule')
+            for s, r in enumerate(rows):
+                if r.dim() != 2 or r.shape[0] < 1:
+                    raise ValueError(f'permutation set {s} must be a (rows, n) tensor with at least one row')
+                n = int(r.shape[1])
+                if not torch.equal(torch.sort(r, dim=1).values, torch.arange(n).expand_as(r)):
+                    raise ValueError(f'permutation set {s}: a row is not a permutation of 0 .. {n - 1}')
+                mols = (ps == s).nonzero().reshape(-1)
+                if bool((sizes[mols] != n).any()):
+                    m = int(mols[(sizes[mols] != n).nonzero()[0]])
+                    raise ValueError(f'permutation set {s} has rows of {n} entries, molecule {m} has {int(sizes[m])} atoms')
+                if sel_h is not None and mols.numel():
+                    flags = torch.unique(sel_h[off[mols][:, None] + torch.arange(n)], dim=0)          # the distinct selections of the set's molecules
+                    for sm in flags:
+                        if not bool(sm[r][:, sm].all()) or not torch.equal(r[:, ~sm], torch.arange(n)[~sm].expand(r.shape[0], -1)):
+                            raise ValueError(f'permutation set {s}: a row moves a selected atom onto an unselected one, or moves an unselected atom')
+            if n_sets:
+                set_off = torch.zeros(n_sets + 1, dtype=torch.int32)
+                set_off[1:] = torch.cumsum(torch.tensor([r.numel() for r in rows]), 0).to(torch.int32)
+                table = (ps.to(d).contiguous(), set_off.to(d), torch.cat([r.reshape(-1) for r in rows]).to(torch.int32).to(d).contiguous())
+        sel = None if sel_h is None else sel_h.to(torch.uint8).to(d).contiguous()
+        pr_dev = pr.to(d)
+        out = torch.empty(P, 2, device=d)
+        best_perm = torch.empty(P, dtype=torch.int32, device=d) if best else None
+        if P == 0:          # nothing to launch, and an empty tensor has no pointer to pass
+            return (out, best_perm) if best else out
+        with self._dev():
+            rc = self.lib.fm_pair_rmsd(self._ctx, self._stream(), _ptr(x), P, _ptr(pr), _ptr(pr_dev), _ptr(sel), _ptr(table[0]),
+                                       _ptr(table[1]), _ptr(table[2]), n_sets, _ptr(out), _ptr(best_perm))
+        self._check(rc, 'fm_pair_rmsd')
+        self._keep = [x, pr, pr_dev, sel, table, out, best_perm]
+        return (out, best_perm) if best else out
+
+    def prune_rmsd(self, d: torch.Tensor, group_sizes, threshold: float):
+        """Greedy RMSD-threshold pruning of conformer groups on the device (fm_prune_rmsd): ``group_sizes`` the conformers per group, ``d`` the groups'
+        strict upper triangles (row-major, i < j), concatenated -- the layout ``pair_rmsd`` gives for the pairs in that order.  In each group, for
+        i = 0, 1, ...: the nearest KEPT j < i (ties: the lowest j) drops i when d(j, i) < ``threshold``.  Returns (keep (M,) bool, rep (M,) int64) on the
+        device over the concatenated conformers: rep[i] = i for a kept conformer, else the index of the one it was dropped for.  A NaN drops nothing.
+        Needs no bound batch; does not synchronise."""
+        dev = self.device
+        gs = torch.as_tensor(group_sizes).detach().to('cpu', torch.int64).reshape(-1)
+        if gs.numel() and int(gs.min()) < 0:
+            raise ValueError('group_sizes must not be negative')
+        G, M = int(gs.numel()), int(gs.sum())
+        tri = gs * (gs - 1) // 2
+        if M >= 2 ** 31 or int(tri.sum()) >= 2 ** 31:
+            raise ValueError('prune_rmsd: the conformers or the triangles exceed int32 offsets')
+        dd = torch.as_tensor(d).detach().to(dev, torch.float32).reshape(-1).contiguous()
+        if dd.numel() != int(tri.sum()):
+            raise ValueError(f'd has {dd.numel()} values, the groups have {int(tri.sum())} pairs (K (K - 1) / 2 per group)')
+        if M == 0:
+            return torch.zeros(0, dtype=torch.bool, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+        group_off, tri_off = torch.zeros(G + 1, dtype=torch.int32), torch.zeros(G + 1, dtype=torch.int32)
+        group_off[1:], tri_off[1:] = torch.cumsum(gs, 0).to(torch.int32), torch.cumsum(tri, 0).to(torch.int32)
+        group_off, tri_off = group_off.to(dev), tri_off.to(dev)
+        keep, rep = torch.empty(M, dtype=torch.uint8, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
+        with self._dev():
+            rc = self.lib.fm_prune_rmsd(self._ctx, self._stream(), G, _ptr(group_off), _ptr(dd) if dd.numel() else None, _ptr(tri_off), float(threshold),
+                                        _ptr(keep), _ptr(rep))
+        self._check(rc, 'fm_prune_rmsd')
+        self._keep = [group_off, tri_off, dd, keep, rep]
+        return keep != 0, rep.long()
+
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):
         self._check(self.lib.fm_profile_enable(self._ctx, int(on)), 'fm_profile_enable')

@@ -28,6 +28,7 @@ from .engine import Engine, IntegrationRun, StepNoise, alpha_tables, cat_temp_sc
 from .molecule import SampledMolecule
 from .priors import (adapt_prior, categorical_prior, default_marginals, draw_categorical_priors,          # noqa: F401  (re-exported)
                      load_marginal_dists, simplex_projection)
+from .symmetry import automorphisms
 from .weights import synth_state_dict
 
 PKG = Path(__file__).resolve().parent
@@ -484,16 +485,132 @@ class FlowMol:
         xb, nb = self._given_molecules(molecules_b)
         if na.tolist() != nb.tolist():
             raise ValueError(f'rmsd: the molecules must match in size one by one, got {na.tolist()} and {nb.tolist()}')
-        sel = torch.ones(int(nb.sum()), dtype=torch.bool) if select is None else _keep_flat(select, nb.tolist(), 'select', 'atoms')
+        sel = self._selection(xb['a_t'], nb.tolist(), select, heavy)
+        eng = self.engine
+        eng.bind(nb)
+        out = eng.align_rmsd(xa['x_t'], xb['x_t'], sel)
+        eng.synchronize()
+        return out[:, 2].cpu()
+
+    def _selection(self, a_tok: torch.Tensor, sizes, select, heavy: bool) -> Optional[torch.Tensor]:
+        """``select`` / ``heavy`` of ``rmsd`` and ``rmsd_matrix`` as one bool tensor over the concatenated atoms, or None for all atoms: ``select`` a bool
+        tensor over the atoms or one bool sequence per molecule; ``heavy`` drops the atoms whose type in ``a_tok`` is 'H' or the fake-atom token."""
+        if select is None and not heavy:
+            return None
+        sel = torch.ones(int(sum(sizes)), dtype=torch.bool) if select is None else _keep_flat(select, list(sizes), 'select', 'atoms')
         if heavy:
             amap = list(self.cfg.atom_type_map)
             light = [i for i, sym in enumerate(amap) if sym == 'H'] + [len(amap)]          # the fake atom's token follows the real types
-            sel = sel & ~torch.isin(xb['a_t'], torch.tensor(light))
+            sel = sel & ~torch.isin(a_tok, torch.tensor(light))
+        return sel
+
+    # ------------------------------------------------------------------ conformer ensembles
+    def _conformer_groups(self, n_mols: int, n_conformers, groups) -> List[int]:
+        if groups is not None:
+            sizes = [int(g) for g in groups]
+            if any(g < 0 for g in sizes) or sum(sizes) != n_mols:
+                raise ValueError(f'groups must hold non-negative sizes that add up to the {n_mols} molecules given, got {sizes}')
+            return sizes
+        if n_conformers is None:
+            raise ValueError('give n_conformers (the K of conformers()) or groups=[sizes]')
+        K = int(n_conformers)
+        if K < 1 or n_mols % K:
+            raise ValueError(f'{n_mols} molecules are not a whole number of groups of n_conformers = {K}')
+        return [K] * (n_mols // K)
+
+    def _rmsd_triangles(self, x, tok, n_atoms, group_sizes, select, heavy, symmetry, max_perms):
+        """The strict upper triangles (row-major, i < j) of every group's RMSD matrix, concatenated, as one float32 tensor on the engine's device: one
+        bind, one ``Engine.pair_rmsd`` launch.  ``x`` (N,3) on any device; ``tok`` {'a_t', 'c_t', 'e_t'} on the CPU; ``n_atoms`` (M,) the molecules' sizes."""
+        sizes = [int(v) for v in n_atoms.tolist()]
+        n_pairs = [n * (n - 1) // 2 for n in sizes]
+        sel = self._selection(tok['a_t'], sizes, select, heavy)
+        a_m, c_m, e_m = torch.split(tok['a_t'], sizes), torch.split(tok['c_t'], sizes), torch.split(tok['e_t'], n_pairs)
+        s_m = torch.split(sel, sizes) if sel is not None else None
+        pairs, perm_set, rows, m0 = [], [-1] * len(sizes), [], 0
+        for g, K in enumerate(group_sizes):
+            for k in range(1, K):
+                if sizes[m0 + k] != sizes[m0]:
+                    raise ValueError(f'group {g}: the conformers differ in size ({sizes[m0]} and {sizes[m0 + k]} atoms)')
+                if s_m is not None and not torch.equal(s_m[m0 + k], s_m[m0]):
+                    raise ValueError(f'group {g}: select / heavy flag different atoms in its conformers')
+                if symmetry and not (torch.equal(a_m[m0 + k], a_m[m0]) and torch.equal(c_m[m0 + k], c_m[m0]) and torch.equal(e_m[m0 + k], e_m[m0])):
+                    raise ValueError(f'group {g}: symmetry=True needs conformers of ONE graph, conformer {k} differs from conformer 0 in a token')
+            if symmetry and K > 1:
+                rows.append(automorphisms(a_m[m0], c_m[m0], e_m[m0], None if s_m is None else s_m[m0], max_perms=max_perms, mask_token=self.cfg.n_bond_types))
+                perm_set[m0:m0 + K] = [len(rows) - 1] * K
+            pairs += [(m0 + i, m0 + j) for i in range(K) for j in range(i + 1, K)]
+            m0 += K
         eng = self.engine
-        eng.bind(nb)
-        out = eng.align_rmsd(xa['x_t'], xb['x_t'], None if select is None and not heavy else sel)
-        eng.synchronize()
-        return out[:, 2].cpu()
+        eng.bind(n_atoms)
+        if not pairs:
+            return torch.zeros(0, device=eng.device)
+        out = eng.pair_rmsd(x, torch.tensor(pairs, dtype=torch.int32), sel, (torch.tensor(perm_set, dtype=torch.int32), rows) if rows else None)
+        return out[:, 1].contiguous()
+
+    @torch.no_grad()
+    def rmsd_matrix(self, molecules, n_conformers=None, select=None, heavy=False, symmetry=False, max_perms=256, groups=None) -> List[torch.Tensor]:
+        """The aligned-RMSD matrix of every group of conformers, in one bind and one launch on the device (``Engine.pair_rmsd``): a list of symmetric
+        (K, K) float32 CPU tensors with a zero diagonal -- the upper triangle is computed and mirrored.  ``molecules``: the flat, molecule-major list that
+        ``conformers`` returns (or its ``(tensors, n_atoms)`` pair), cut into groups of ``n_conformers``, or into ``groups=[sizes]``.  ``select`` and
+        ``heavy`` as in ``rmsd``.  ``symmetry``: the rmsd of a pair is the smallest over the automorphisms of the group's first conformer
+        (``symmetry.automorphisms`` of its selected atoms, computed once per group and shared by its members; more than ``max_perms`` is its ValueError),
+        so a flipped phenyl or a rotated methyl is the same conformer; the identity is among them, hence never larger than without.  ValueError when the
+        conformers of a group differ in size, in their selected atoms or, with ``symmetry``, in any token."""
+        x1, n_atoms = self._given_molecules(molecules)
+        gs = self._conformer_groups(int(n_atoms.numel()), n_conformers, groups)
+        tri = self._rmsd_triangles(x1['x_t'], x1, n_atoms, gs, select, heavy, symmetry, max_perms)
+        self.engine.synchronize()
+        mats = []
+        for K, t in zip(gs, torch.split(tri.cpu(), [K * (K - 1) // 2 for K in gs])):
+            m = torch.zeros(K, K)
+            i, j = torch.triu_indices(K, K, 1)
+            m[i, j] = t
+            mats.append(m + m.T)
+        return mats
+
+    @torch.no_grad()
+    def prune_conformers(self, molecules, n_conformers=None, threshold=0.5, heavy=True, symmetry=True, select=None, max_perms=256, groups=None):
+        """Greedy RMSD-threshold pruning of conformer groups, on the device (``rmsd_matrix``'s launch, then ``Engine.prune_rmsd``): in every group, for
+        i = 0, 1, ... conformer i is dropped when the nearest KEPT earlier conformer (ties: the first) is closer than ``threshold`` -- the rule of RDKit's
+        pruneRmsThresh.  Returns ``(kept, keep, rep)``: ``kept`` one list per group with its kept molecules (the objects given; for the
+        ``(tensors, n_atoms)`` form their indices in the flat list), ``keep`` (M,) bool and ``rep`` (M,) int64 over the flat list -- rep[i] = i for a
+        kept conformer, else the index of the kept one it was dropped for, so cluster populations are ``torch.bincount(rep)``.  Arguments and refusals of
+        ``rmsd_matrix``; the molecules are never altered."""
+        x1, n_atoms = self._given_molecules(molecules)
+        gs = self._conformer_groups(int(n_atoms.numel()), n_conformers, groups)
+        tri = self._rmsd_triangles(x1['x_t'], x1, n_atoms, gs, select, heavy, symmetry, max_perms)
+        keep, rep = self.engine.prune_rmsd(tri, gs, threshold)
+        self.engine.synchronize()
+        keep, rep = keep.cpu(), rep.cpu()
+        items = list(range(int(n_atoms.numel()))) if isinstance(molecules[0], dict) else list(molecules)
+        return _grouped([m for m, k in zip(items, keep.tolist()) if k], [int(k.sum()) for k in torch.split(keep, gs)]), keep, rep
+
+    @torch.no_grad()
+    def conformer_ensembles(self, molecules, n_conformers=1, n_timesteps=None, seed=None, prune_rmsd=None, heavy=True, symmetry=True, max_perms=256,
+                            **conformers_kwargs):
+        """Conformer ensembles of given molecular graphs: ``conformers(molecules, n_conformers, n_timesteps, seed, ...)``, then, with ``prune_rmsd`` a
+        threshold, the symmetry-aware RMSD matrices and the greedy pruning of ``prune_conformers`` on the device, the coordinates going from the sampler
+        to the RMSD launch as one device tensor.  Returns one list of molecules per input molecule; ``prune_rmsd=None`` returns all ``n_conformers``.
+        Pruning selects and never alters: the kept molecules are bit for bit those ``conformers`` returns.  ``return_tensors`` together with
+        ``prune_rmsd`` is a ValueError.  Not covered: sharding across ranks, the command line."""
+        K = int(n_conformers)
+        if prune_rmsd is None:
+            out = self.conformers(molecules, K, n_timesteps, seed=seed, **conformers_kwargs)
+            if conformers_kwargs.get('return_tensors'):
+                return out
+            return _grouped(out, [K] * (len(out) // K))
+        if conformers_kwargs.get('return_tensors'):
+            raise ValueError('conformer_ensembles: return_tensors together with prune_rmsd is not supported (pruning returns lists of molecules)')
+        if conformers_kwargs.get('xt_traj') or conformers_kwargs.get('ep_traj'):
+            raise ValueError('conformer_ensembles: trajectories together with prune_rmsd are not supported')
+        dev_out, n_atoms = self.conformers(molecules, K, n_timesteps, seed=seed, return_tensors='device', **conformers_kwargs)
+        gs = [K] * (int(n_atoms.numel()) // K)
+        tok = {f'{k}_t': dev_out[k].to('cpu', torch.int64) for k in 'ace'}
+        tri = self._rmsd_triangles(dev_out['x'], tok, n_atoms, gs, None, heavy, symmetry, max_perms)
+        keep, _ = self.engine.prune_rmsd(tri, gs, prune_rmsd)
+        keep = keep.cpu()
+        mols = self._package(_to_host(dev_out), n_atoms, None, False, False)
+        return _grouped([m for m, k in zip(mols, keep.tolist()) if k], [int(k.sum()) for k in torch.split(keep, gs)])
 
     def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
         """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --
@@ -844,6 +961,15 @@ def _pairs_of_atoms(keep_atom: torch.Tensor) -> torch.Tensor:
     n = int(keep_atom.shape[0])
     i, j = torch.triu_indices(n, n, 1)
     return keep_atom[i] & keep_atom[j]
+
+
+def _grouped(items: list, counts) -> List[list]:
+    """A flat list cut into consecutive lists of ``counts`` items."""
+    out, k = [], 0
+    for n in counts:
+        out.append(items[k:k + n])
+        k += n
+    return out
 
 
 def _split_molecules(state: Dict[str, torch.Tensor], sizes) -> List[Dict[str, torch.Tensor]]:

@@ -60,7 +60,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 13
+#define FM_ABI_VERSION 14
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -469,6 +469,34 @@ int fm_integrate_freeze(fm_ctx* ctx, void* stream, const fm_state* state, int n_
  * FM_ERR_INVALID if xa_aligned or out aliases an input or each other. */
 int fm_align_rmsd(fm_ctx* ctx, void* stream, const float* xa, const float* xb, const uint8_t* select /* (N), may be NULL = all */, float* out /* (n_mols, 4) */,
                   float* xa_aligned /* (N,3), may be NULL */);
+
+/* --- ABI 14: conformer ensembles -- the symmetry-aware RMSD of pairs of molecules of ONE coordinate set, and the greedy threshold pruning that consumes it.
+ *
+ * fm_pair_rmsd: x (N,3) of the bound batch; pair p = (ma, mb) names two of its molecules, of equal size n.
+ *   n_pairs, pairs_host: HOST (n_pairs,2) int32, read here for the refusals only; pairs: the same array in DEVICE memory, read by the kernel
+ *   select: DEVICE (N) uint8 or NULL = all atoms, read at the rows of the FIRST molecule of each pair (the caller gives both molecules of a pair the same flags)
+ *   the permutation table, or three NULLs and n_sets = 0 for the identity only: perm_set DEVICE (n_mols) int32, a set id per molecule or -1 (identity);
+ *     set_off DEVICE (n_sets + 1) int32 element offsets into perms; perms DEVICE int32, set s = the rows of n local atom indices between set_off[s] and
+ *     set_off[s + 1].  The set of a pair is that of its first molecule; an empty set is the identity.  PRECONDITION (device data, not checked here): every
+ *     row is a permutation of 0..n-1 that maps selected atoms onto selected atoms and is the identity on the rest.
+ *   out DEVICE (n_pairs,2) float32 = {count of selected atoms, min over the rows q of rmsd_q}, rmsd_q after centring both molecules on the selected atoms and
+ *     the optimal PROPER rotation (fm_align_rmsd's: no reflection) of a[i] onto b[q[i]], summed from the explicit residuals in float64 (the fit itself is float32)
+ *   best_perm DEVICE (n_pairs) int32, may be NULL: the lowest row index, within the set, that attains the minimum
+ * A pair without a selected atom gives {0, 0} and best_perm 0; n_pairs = 0 is legal.  One wave per pair, one lane per row, sums in ascending atom order: the two
+ * numbers of a pair are a function of the two molecules, the selection and the SET of rows -- the same bits whatever else the batch holds, wherever the pair stands
+ * and in whatever order the rows are given; only best_perm depends on that order.  Not bit-equal to fm_align_rmsd (another summation order).
+ * Does not synchronise, allocates nothing.  FM_ERR_INVALID, before anything is enqueued, for an index outside the batch, a pair of unequal sizes, a partial
+ * permutation table, and an output that aliases an input or the other output.
+ *
+ * fm_prune_rmsd: group g = the conformers group_off[g] .. group_off[g + 1] - 1 (DEVICE (n_groups + 1) int32), K of them; d + tri_off[g] (DEVICE float32, DEVICE
+ * (n_groups + 1) int32) = its strict upper triangle, row-major (i < j), K (K - 1) / 2 values.  For i = 0, 1, ... in order: among the KEPT j < i the one with the
+ * smallest d(j, i), ties to the lowest j; d < threshold drops i (keep[i] = 0, rep[i] = j), otherwise i is kept (keep[i] = 1, rep[i] = i) -- conformer 0 always, and
+ * a NaN compares false and drops nothing.  keep DEVICE (group_off[n_groups]) uint8, rep the same in int32, both indexed like the conformers; rep holds
+ * indices of the concatenated conformers (group_off[g] + j).  Groups of 0 or 1 conformers are legal.  Needs no bound batch; does not synchronise, allocates nothing; FM_ERR_INVALID for an output that aliases. */
+int fm_pair_rmsd(fm_ctx* ctx, void* stream, const float* x, int n_pairs, const int32_t* pairs_host, const int32_t* pairs, const uint8_t* select,
+                 const int32_t* perm_set, const int32_t* set_off, const int32_t* perms, int n_sets, float* out, int32_t* best_perm);
+int fm_prune_rmsd(fm_ctx* ctx, void* stream, int n_groups, const int32_t* group_off, const float* d, const int32_t* tri_off, float threshold, uint8_t* keep,
+                  int32_t* rep);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
