@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 14
+FM_ABI_VERSION = 15
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
@@ -172,6 +172,9 @@ _EXPORTS = {
     'fm_pair_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                C.c_void_p, C.c_void_p]),
     'fm_prune_rmsd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    # ABI 15: the stereo check of conformers against their input
+    'fm_stereo': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

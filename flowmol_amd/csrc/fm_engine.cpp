@@ -1587,6 +1587,35 @@ int fm_align_rmsd(fm_ctx* c, void* stream, const float* xa, const float* xb, con
     return L.rc;
 }
 
+// Stereo check of two coordinate sets of the bound batch, molecule by molecule (fm_k_stereo: one wave per molecule, lanes strided over its element rows)
+int fm_stereo(fm_ctx* c, void* stream, const float* x, const float* x_ref, const int32_t* elem_set, const int32_t* set_off, const int32_t* elems, int n_sets,
+              float flat_tol, int32_t* out, const int32_t* val_off, float* values, float* x_out) {
+    const char* const fn = "fm_stereo";
+    if (!c || !x || !x_ref || !out) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    if (!c->bound) return fail(c, FM_ERR_INVALID, "%s: no batch bound", fn);
+    const bool table = elem_set || set_off || elems;
+    if (table && !(elem_set && set_off && elems && n_sets >= 1))
+        return fail(c, FM_ERR_INVALID, "%s: elem_set, set_off and elems come together with n_sets >= 1, or all NULL with n_sets = 0 (no element)", fn);
+    if (!table && n_sets != 0) return fail(c, FM_ERR_INVALID, "%s: n_sets = %d without an element table", fn, n_sets);
+    if (!(flat_tol >= 0.f)) return fail(c, FM_ERR_INVALID, "%s: flat_tol = %g must be a number >= 0", fn, (double)flat_tol);
+    if (values && !val_off) return fail(c, FM_ERR_INVALID, "%s: values without val_off", fn);
+    const void* const in[] = {x, x_ref, elem_set, set_off, elems, val_off};
+    const void* const outs[] = {out, values, x_out};
+    for (int a = 0; a < 3; ++a) {
+        if (!outs[a]) continue;
+        for (const void* p : in)
+            if (p && p == outs[a]) return fail(c, FM_ERR_INVALID, "%s: an output aliases an input", fn);
+        for (int b = a + 1; b < 3; ++b)
+            if (outs[b] == outs[a]) return fail(c, FM_ERR_INVALID, "%s: an output aliases another output", fn);
+    }
+    Launch L{c, (hipStream_t)stream};
+    FmStereoArgs g{};
+    g.x = x; g.x_ref = x_ref; g.node_off = c->ws.b.mol_node_off; g.elem_set = elem_set; g.set_off = set_off; g.elems = elems; g.n_sets = n_sets;
+    g.flat_tol = flat_tol; g.out = out; g.val_off = values ? val_off : nullptr; g.vals = values; g.x_out = x_out;
+    L("stereo", fm_k_stereo, dim3(c->ws.b.B), dim3(64), 0, g);
+    return L.rc;
+}
+
 // Symmetry-aware aligned RMSD of pairs of molecules of the bound batch (fm_k_pair_rmsd: one wave per pair, one lane per permutation row).  pairs_host is read
 // here, for the refusals; the kernel reads the device copy.
 int fm_pair_rmsd(fm_ctx* c, void* stream, const float* x, int n_pairs, const int32_t* pairs_host, const int32_t* pairs, const uint8_t* select,

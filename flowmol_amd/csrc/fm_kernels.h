@@ -2568,6 +2568,109 @@ static __global__ void __launch_bounds__(64) fm_k_align_rmsd(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
+// Stereo check of two coordinate sets, molecule by molecule (fm_stereo): the signs of a molecule's stereo elements in x against those in x_ref.  The elements
+// of molecule m are the rows set_off[s] .. set_off[s + 1] - 1 of elems, s = elem_set[m]; a row is {kind, i0, i1, i2, i3} with local atom indices.  No table, a
+// set id outside 0 .. n_sets - 1 or an empty set: no element.  PRECONDITION on the rows (device data): kind 0 or 1 -- anything else is read as 1 --, indices
+// inside the molecule -- an index outside 0 .. n - 1 is read as 0, so nothing is read out of the molecule.
+// VALUE of an element, every operation separately rounded (fm_*_rn, sqrtf and the division correctly rounded: the emulation and the device agree):
+//   kind 0  (u1 x u2) . u3, u_k = (x[i_k] - x[i0]) / |x[i_k] - x[i0]|: the signed volume of the three unit bond vectors
+//   kind 1  n1 . n2, n1 = b1 x b2 and n2 = b2 x b3 normalised, b1 = x[i1] - x[i0], b2 = x[i2] - x[i1], b3 = x[i3] - x[i2]: the cosine of the dihedral
+// a vector or a normal of length zero (or one that is not a number) gives +0; a zero result is +0.  An element is DEFINED in a set when |value| >= flat_tol and
+// MISMATCHES when it is defined in both sets with different signs.
+// out[m] = {kind-0 elements, of them defined in both, of them mismatches, kind-1 elements, defined in both, mismatches, match, mirror}: match = every element
+// defined in both and none mismatches; mirror = at least one kind-0 element, every element defined in both, every kind-0 element mismatches, no kind-1 does.
+// vals (may be null) + val_off[m] receives the values of x in row order; x_out (may be null) receives -x for the atoms of a mirror molecule and x otherwise.
+// One wave per molecule, lane l takes the rows l, l + 64, ...; the counts are integer sums through the xor tree, so everything is a function of the molecule,
+// its rows and flat_tol alone.
+// ------------------------------------------------------------------------------------------------
+struct FmStereoArgs {
+    const float* x; const float* x_ref; const int* node_off;
+    const int* elem_set; const int* set_off; const int* elems; int n_sets; float flat_tol;
+    int* out; const int* val_off; float* vals; float* x_out;
+};
+__device__ __forceinline__ void fm_cross_rn(const float (&a)[3], const float (&b)[3], float (&c)[3]) {
+    c[0] = fm_sub_rn(fm_mul_rn(a[1], b[2]), fm_mul_rn(a[2], b[1]));
+    c[1] = fm_sub_rn(fm_mul_rn(a[2], b[0]), fm_mul_rn(a[0], b[2]));
+    c[2] = fm_sub_rn(fm_mul_rn(a[0], b[1]), fm_mul_rn(a[1], b[0]));
+}
+__device__ __forceinline__ float fm_dot_rn(const float (&a)[3], const float (&b)[3]) {
+    return fm_add_rn(fm_add_rn(fm_mul_rn(a[0], b[0]), fm_mul_rn(a[1], b[1])), fm_mul_rn(a[2], b[2]));
+}
+// v / |v| in place; false, v untouched, when the length is zero or not a number
+__device__ __forceinline__ bool fm_unit_rn(float (&v)[3]) {
+    const float l = sqrtf(fm_dot_rn(v, v));
+    if (!(l > 0.f)) return false;
+    for (int k = 0; k < 3; ++k) v[k] = fm_div_rn(v[k], l);
+    return true;
+}
+// x = the molecule's first atom; i = the row's four local indices, already inside the molecule
+__device__ __forceinline__ float fm_stereo_value(const float* x, int kind, const int (&i)[4]) {
+    float p[4][3];
+    for (int a = 0; a < 4; ++a) for (int k = 0; k < 3; ++k) p[a][k] = x[i[a] * 3 + k];
+    float u[3][3], v;
+    if (kind == 0) {
+        for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) u[a][k] = fm_sub_rn(p[a + 1][k], p[0][k]);
+        if (!(fm_unit_rn(u[0]) && fm_unit_rn(u[1]) && fm_unit_rn(u[2]))) return 0.f;
+        float c[3];
+        fm_cross_rn(u[0], u[1], c);
+        v = fm_dot_rn(c, u[2]);
+    } else {
+        for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) u[a][k] = fm_sub_rn(p[a + 1][k], p[a][k]);
+        float n1[3], n2[3];
+        fm_cross_rn(u[0], u[1], n1);
+        fm_cross_rn(u[1], u[2], n2);
+        if (!(fm_unit_rn(n1) && fm_unit_rn(n2))) return 0.f;
+        v = fm_dot_rn(n1, n2);
+    }
+    return v == v ? fm_add_rn(v, 0.f) : 0.f;      // -0 + 0 = +0
+}
+static __global__ void __launch_bounds__(64) fm_k_stereo(FmStereoArgs g) {
+    const int mol = blockIdx.x, lane = threadIdx.x;
+    const int n0 = g.node_off[mol], n = g.node_off[mol + 1] - n0;
+    const float* const xa = g.x + (size_t)n0 * 3;
+    const float* const xb = g.x_ref + (size_t)n0 * 3;
+    int n_rows = 0;
+    const int* rows = nullptr;
+    if (g.elems && n > 0) {
+        const int s = g.elem_set[mol];
+        if (s >= 0 && s < g.n_sets) {
+            const int e0 = g.set_off[s], cnt_rows = g.set_off[s + 1] - e0;
+            if (cnt_rows > 0) { n_rows = cnt_rows; rows = g.elems + (size_t)e0 * 5; }
+        }
+    }
+    float* const vals = g.vals ? g.vals + g.val_off[mol] : nullptr;
+    int cnt[6] = {0, 0, 0, 0, 0, 0};
+    for (int q = lane; q < n_rows; q += 64) {      // lanes hold different row counts: nothing in here crosses lanes
+        const int* const row = rows + (size_t)q * 5;
+        const int kind = row[0] != 0 ? 1 : 0;
+        int idx[4];
+        for (int k = 0; k < 4; ++k) { const int j = row[1 + k]; idx[k] = (unsigned)j < (unsigned)n ? j : 0; }
+        const float va = fm_stereo_value(xa, kind, idx), vb = fm_stereo_value(xb, kind, idx);
+        const bool both = fabsf(va) >= g.flat_tol && fabsf(vb) >= g.flat_tol;
+        const int defined = both ? 1 : 0, differs = both && (va < 0.f) != (vb < 0.f) ? 1 : 0, tetra = 1 - kind;      // constant indices: the counts stay in registers
+        cnt[0] += tetra; cnt[1] += tetra * defined; cnt[2] += tetra * differs;
+        cnt[3] += kind; cnt[4] += kind * defined; cnt[5] += kind * differs;
+        if (vals) vals[q] = va;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o);
+    }
+    const bool all_defined = cnt[1] == cnt[0] && cnt[4] == cnt[3];
+    const bool match = all_defined && cnt[2] == 0 && cnt[5] == 0;
+    const bool mirror = cnt[0] > 0 && all_defined && cnt[2] == cnt[0] && cnt[5] == 0;
+    int mine = lane == 6 ? (match ? 1 : 0) : (mirror ? 1 : 0);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mine = lane == k ? cnt[k] : mine;
+    if (lane < 8) g.out[mol * 8 + lane] = mine;
+    if (g.x_out) {
+        float* const xo = g.x_out + (size_t)n0 * 3;
+        for (int i = lane; i < n * 3; i += 64) xo[i] = mirror ? -xa[i] : xa[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Symmetry-aware aligned RMSD of pairs of molecules of ONE coordinate set (fm_pair_rmsd): pair p = (ma, mb), two molecules of the same size n ->
 // out[p] = {selected atoms, min over the permutation rows q of the rmsd after centring and the optimal PROPER rotation of a[i] onto b[q[i]]}, best[p] = the
 // lowest row index that attains the minimum.  sel is read at the rows of ma.  The rows of a pair are those of the set perm_set[ma] (elements set_off[s] ..

@@ -938,6 +938,67 @@ class Engine:
         self._keep = [xa, xb, sel, out, moved]
         return (out, moved) if aligned else out
 
+    # ------------------------------------------------------------------ stereo check
+    def stereo(self, x: torch.Tensor, x_ref: torch.Tensor, elem_sets, flat_tol: float = 0.05, values: bool = False, fixed: bool = False):
+        """The stereo state of ``x`` against that of ``x_ref`` ((N,3) each, the bound batch's atoms) molecule by molecule, one launch on the device
+        (fm_stereo).  ``elem_sets`` = (elem_set (B,) set id per molecule or -1 for none, [rows (Q_s, 5) per set]) or None: a row is ``[kind, i0, i1, i2, i3]``
+        with local atom indices as ``stereo.stereo_elements`` gives them -- kind 0 a tetrahedral centre i0 with neighbours i1..i3, valued
+        (u1 x u2) . u3 over the unit bond vectors; kind 1 a double bond i1 = i2, valued cos of the dihedral i0-i1-i2-i3.  An element is defined in a
+        coordinate set when |value| >= ``flat_tol`` and mismatches when it is defined in both with different signs.  ``flat_tol`` = 0.05 is the
+        DEFINITION of a flat element here (a centre within about 3 degrees of planar, a dihedral within 3 degrees of perpendicular), not a measured tolerance.
+        Returns (B,8) int32 on the device = {kind-0 elements, defined in both, mismatches, kind-1 elements, defined in both, mismatches, match, mirror}
+        (fm_stereo in include/flowmol_hip.h); with ``values`` also (the float32 values of ``x``, concatenated in row order, and their (B+1,) CPU
+        offsets); with ``fixed`` also (N,3): ``-x`` for the molecules flagged mirror, ``x`` for the rest.  ValueError, before the call, for what the
+        library cannot check: a set whose rows are not (Q,5), a kind outside {0, 1}, an index outside a molecule that names the set, an index repeated
+        within a row.  A molecule's results do not depend on the rest of the batch.  Does not synchronise."""
+        d = self.device
+        x, x_ref = (v.detach().to(d, torch.float32).contiguous() for v in (x, x_ref))
+        if tuple(x.shape) != (self.N, 3) or tuple(x_ref.shape) != (self.N, 3):
+            raise ValueError(f'x and x_ref must be ({self.N}, 3): the atoms of the bound batch')
+        tol = float(flat_tol)
+        if not tol >= 0.0:
+            raise ValueError(f'flat_tol = {flat_tol} must be a number >= 0')
+        sizes = self.n_atoms
+        table, n_sets, n_rows = (None, None, None), 0, torch.zeros(self.B, dtype=torch.int64)
+        if elem_sets is not None:
+            es, rows = elem_sets
+            es = torch.as_tensor(es).detach().to('cpu', torch.int32).reshape(-1)
+            rows = [torch.as_tensor(r).detach().to('cpu', torch.int64) for r in rows]
+            if es.shape[0] != self.B or (self.B and (int(es.min()) < -1 or int(es.max()) >= len(rows))):
+                raise ValueError(f'elem_set must hold one set id in -1 .. {len(rows) - 1} per bound molecule')
+            for s, r in enumerate(rows):
+                if r.dim() != 2 or r.shape[1] != 5:
+                    raise ValueError(f'element set {s} must be a (rows, 5) tensor of [kind, i0, i1, i2, i3]')
+                if not r.shape[0]:
+                    continue
+                if bool(((r[:, 0] != 0) & (r[:, 0] != 1)).any()):
+                    raise ValueError(f'element set {s}: a kind outside {{0, 1}}')
+                if bool((torch.sort(r[:, 1:], dim=1).values.diff(dim=1) == 0).any()):
+                    raise ValueError(f'element set {s}: a row names an atom twice')
+                mols = (es == s).nonzero().reshape(-1)
+                if mols.numel() and (int(r[:, 1:].min()) < 0 or int(r[:, 1:].max()) >= int(sizes[mols].min())):
+                    raise ValueError(f'element set {s}: an index outside 0 .. {int(sizes[mols].min()) - 1}, the atoms of the smallest molecule that names the set')
+            per_set = torch.tensor([r.shape[0] for r in rows], dtype=torch.int64)
+            if int(per_set.sum()):          # with no row at all there is no table, and an empty tensor has no pointer to pass
+                n_sets = len(rows)
+                set_off = torch.zeros(n_sets + 1, dtype=torch.int32)
+                set_off[1:] = torch.cumsum(per_set, 0).to(torch.int32)
+                table = (es.to(d).contiguous(), set_off.to(d), torch.cat([r.reshape(-1) for r in rows]).to(torch.int32).to(d).contiguous())
+                n_rows = torch.where(es >= 0, per_set[es.long().clamp(min=0)], torch.zeros((), dtype=torch.int64))
+        out = torch.empty(self.B, 8, dtype=torch.int32, device=d)
+        val_off = torch.zeros(self.B + 1, dtype=torch.int64)
+        val_off[1:] = torch.cumsum(n_rows, 0)
+        vals = torch.empty(int(val_off[-1]), device=d) if values else None
+        voff = val_off.to(torch.int32).to(d) if values and vals.numel() else None
+        x_out = torch.empty(self.N, 3, device=d) if fixed else None
+        with self._dev():
+            rc = self.lib.fm_stereo(self._ctx, self._stream(), _ptr(x), _ptr(x_ref), _ptr(table[0]), _ptr(table[1]), _ptr(table[2]), n_sets, tol, _ptr(out),
+                                    _ptr(voff), _ptr(vals) if voff is not None else None, _ptr(x_out))
+        self._check(rc, 'fm_stereo')
+        self._keep = [x, x_ref, table, out, voff, vals, x_out]
+        res = (out,) + (((vals, val_off),) if values else ()) + ((x_out,) if fixed else ())
+        return res if len(res) > 1 else out
+
     # ------------------------------------------------------------------ conformer ensembles: pairwise RMSD, pruning
     def pair_rmsd(self, x: torch.Tensor, pairs, select=None, perm_sets=None, best: bool = False):
         """Symmetry-aware aligned RMSD of pairs of molecules of the bound batch, one launch on the device (fm_pair_rmsd): ``x`` (N,3) the batch's atoms,

@@ -28,6 +28,7 @@ from .engine import Engine, IntegrationRun, StepNoise, alpha_tables, cat_temp_sc
 from .molecule import SampledMolecule
 from .priors import (adapt_prior, categorical_prior, default_marginals, draw_categorical_priors,          # noqa: F401  (re-exported)
                      load_marginal_dists, simplex_projection)
+from .stereo import stereo_elements
 from .symmetry import automorphisms
 from .weights import synth_state_dict
 
@@ -587,14 +588,27 @@ class FlowMol:
 
     @torch.no_grad()
     def conformer_ensembles(self, molecules, n_conformers=1, n_timesteps=None, seed=None, prune_rmsd=None, heavy=True, symmetry=True, max_perms=256,
-                            **conformers_kwargs):
+                            stereo=None, flat_tol=0.05, **conformers_kwargs):
         """Conformer ensembles of given molecular graphs: ``conformers(molecules, n_conformers, n_timesteps, seed, ...)``, then, with ``prune_rmsd`` a
         threshold, the symmetry-aware RMSD matrices and the greedy pruning of ``prune_conformers`` on the device, the coordinates going from the sampler
         to the RMSD launch as one device tensor.  Returns one list of molecules per input molecule; ``prune_rmsd=None`` returns all ``n_conformers``.
         Pruning selects and never alters: the kept molecules are bit for bit those ``conformers`` returns.  ``return_tensors`` together with
-        ``prune_rmsd`` is a ValueError.  Not covered: sharding across ranks, the command line."""
+        ``prune_rmsd`` is a ValueError.
+
+        ``stereo`` (None | 'match' | 'mirror'; ``flat_tol`` as in ``match_stereo``): the frozen tokens carry no stereo information, so a conformer may
+        come back with a stereocentre inverted or a double bond flipped -- a different compound.  'match' drops, before any pruning, every conformer
+        whose stereo state (``match_stereo`` against the input's own coordinates, one launch on the device between the sampler and the RMSD launch) is
+        not the input's; 'mirror' first point-inverts the exact mirror images (their coordinates become exactly the negative of what ``conformers``
+        gives) and then drops what still mismatches.  The lists then have between 0 and ``n_conformers`` members; nothing is sampled again to fill them
+        up.  None is the call without the argument.  ``stereo`` together with ``return_tensors`` or trajectories, any other value, and a conformer
+        whose tokens are not the input's (a model with alpha(1) < 1) are a ValueError.
+        Not covered: sharding across ranks, the command line."""
         K = int(n_conformers)
-        if prune_rmsd is None:
+        if stereo not in (None, 'match', 'mirror'):
+            raise ValueError(f"conformer_ensembles: stereo must be None, 'match' or 'mirror', got {stereo!r}")
+        if stereo is not None and conformers_kwargs.get('return_tensors'):
+            raise ValueError('conformer_ensembles: return_tensors together with stereo is not supported (the stereo filter returns lists of molecules)')
+        if prune_rmsd is None and stereo is None:
             out = self.conformers(molecules, K, n_timesteps, seed=seed, **conformers_kwargs)
             if conformers_kwargs.get('return_tensors'):
                 return out
@@ -602,15 +616,94 @@ class FlowMol:
         if conformers_kwargs.get('return_tensors'):
             raise ValueError('conformer_ensembles: return_tensors together with prune_rmsd is not supported (pruning returns lists of molecules)')
         if conformers_kwargs.get('xt_traj') or conformers_kwargs.get('ep_traj'):
-            raise ValueError('conformer_ensembles: trajectories together with prune_rmsd are not supported')
+            raise ValueError('conformer_ensembles: trajectories together with prune_rmsd or stereo are not supported')
         dev_out, n_atoms = self.conformers(molecules, K, n_timesteps, seed=seed, return_tensors='device', **conformers_kwargs)
         gs = [K] * (int(n_atoms.numel()) // K)
         tok = {f'{k}_t': dev_out[k].to('cpu', torch.int64) for k in 'ace'}
+        if stereo is not None:
+            ref, n_ref = self._given_molecules(molecules)
+            rep = [i for i in range(int(n_ref.numel())) for _ in range(K)]
+            given = _split_molecules(ref, n_ref.tolist())
+            ref = {k: torch.cat([given[i][k] for i in rep]) for k in ('x_t', 'a_t', 'c_t', 'e_t')}
+            ok, _, x_fixed = self._stereo_launch(dev_out['x'], tok, n_atoms, ref, n_ref[rep], stereo == 'mirror', flat_tol)
+            atom_keep = torch.repeat_interleave(ok, n_atoms)
+            pair_keep = torch.repeat_interleave(ok, n_atoms * (n_atoms - 1) // 2)
+            gs = [int(k.sum()) for k in torch.split(ok, gs)]
+            n_atoms = n_atoms[ok]
+            if not sum(gs):
+                return [[] for _ in gs]
+            dev = dev_out['x'].device
+            ak, pk = atom_keep.to(dev), pair_keep.to(dev)
+            dev_out = {'x': (x_fixed if x_fixed is not None else dev_out['x'])[ak].contiguous(), 'a': dev_out['a'][ak].contiguous(),
+                       'c': dev_out['c'][ak].contiguous(), 'e': dev_out['e'][pk].contiguous()}
+            tok = {'a_t': tok['a_t'][atom_keep], 'c_t': tok['c_t'][atom_keep], 'e_t': tok['e_t'][pair_keep]}
+        if prune_rmsd is None:
+            return _grouped(self._package(_to_host(dev_out), n_atoms, None, False, False), gs)
         tri = self._rmsd_triangles(dev_out['x'], tok, n_atoms, gs, None, heavy, symmetry, max_perms)
         keep, _ = self.engine.prune_rmsd(tri, gs, prune_rmsd)
         keep = keep.cpu()
         mols = self._package(_to_host(dev_out), n_atoms, None, False, False)
         return _grouped([m for m, k in zip(mols, keep.tolist()) if k], [int(k.sum()) for k in torch.split(keep, gs)])
+
+    # ------------------------------------------------------------------ stereo check
+    def _stereo_launch(self, x, tok, n_atoms, ref, n_ref, mirror: bool, flat_tol):
+        """One bind and one ``Engine.stereo`` launch of the coordinates ``x`` ((N,3), any device) with the CPU tokens ``tok`` against the CPU reference state
+        ``ref`` {'x_t', 'a_t', 'c_t', 'e_t'}: -> (match (B,) bool with the mirror images counted in when ``mirror``, table (B,8) int32, both on the CPU, and
+        with ``mirror`` the (N,3) coordinates on the engine's device with the mirror images inverted, else None).  The stereo elements come from the
+        reference's tokens, once per run of consecutive identical graphs.  ValueError when a molecule and its reference differ in size or in a token."""
+        if n_atoms.tolist() != n_ref.tolist():
+            raise ValueError(f'stereo: a molecule and its reference must match in size one by one, got {n_atoms.tolist()} and {n_ref.tolist()}')
+        for f, what in (('a_t', 'an atom type'), ('c_t', 'a charge'), ('e_t', 'a bond order')):
+            if not torch.equal(tok[f], ref[f]):
+                raise ValueError(f'stereo: a molecule differs from its reference in {what} token: the stereo state is compared between arrangements of ONE graph')
+        sizes = n_atoms.tolist()
+        a_m, c_m = torch.split(ref['a_t'], sizes), torch.split(ref['c_t'], sizes)
+        e_m = torch.split(ref['e_t'], [n * (n - 1) // 2 for n in sizes])
+        elem_set, rows = [], []
+        for m in range(len(sizes)):
+            if not (m and sizes[m] == sizes[m - 1] and torch.equal(a_m[m], a_m[m - 1]) and torch.equal(c_m[m], c_m[m - 1]) and torch.equal(e_m[m], e_m[m - 1])):
+                rows.append(stereo_elements(a_m[m], c_m[m], e_m[m], mask_token=self.cfg.n_bond_types,
+                                            fake_token=len(self.cfg.atom_type_map) if self.fake_atoms else None))
+            elem_set.append(len(rows) - 1)
+        eng = self.engine
+        eng.bind(n_atoms)
+        res = eng.stereo(x, ref['x_t'], (torch.tensor(elem_set, dtype=torch.int32), rows), flat_tol, fixed=mirror)
+        table, x_fixed = res if mirror else (res, None)
+        eng.synchronize()
+        table = table.cpu()
+        ok = table[:, 6] != 0
+        if mirror:
+            ok = ok | (table[:, 7] != 0)
+        return ok, table, x_fixed
+
+    @torch.no_grad()
+    def match_stereo(self, molecules, references, mirror=False, flat_tol=0.05):
+        """Do ``molecules`` have the stereo state of ``references``?  Molecule i is compared with reference i, an arrangement in space of the same graph
+        (``molecules_*`` as in ``resample``; ValueError when the two differ in size or in any token).  The stereo elements -- tetrahedral centres and
+        double bonds as ``stereo.stereo_elements`` defines them, which also says what that leaves out -- are perceived on the reference's tokens, once per
+        run of consecutive identical graphs, and compared in one bind and one launch on the device (``Engine.stereo``, whose ``flat_tol`` this is: an
+        element flatter than that in either arrangement is undefined, and a molecule with an undefined element does not match).
+        Returns ``(molecules_out, match, table)``: ``match`` (B,) bool, ``table`` (B,8) int32 on the CPU = {centres, defined in both, mismatches, double
+        bonds, defined in both, mismatches, match, mirror} per molecule, ``molecules_out`` the full list, unfiltered, in the form given.  With
+        ``mirror`` the molecules flagged as exact mirror images (every centre inverted, every double bond as in the reference) come back point-inverted:
+        their coordinates are exactly the negative of the input's, their tokens unchanged (new objects without trajectory frames; the others are the
+        objects given), and they count as matching.  ``mirror=False`` alters nothing."""
+        x1, n_atoms = self._given_molecules(molecules)
+        ref, n_ref = self._given_molecules(references)
+        ok, table, x_fixed = self._stereo_launch(x1['x_t'], x1, n_atoms, ref, n_ref, bool(mirror), flat_tol)
+        tensor_form = isinstance(molecules[0], dict)
+        if not mirror:
+            return (molecules if tensor_form else list(molecules)), ok, table
+        x_fixed = x_fixed.cpu()
+        if tensor_form:
+            return ({'x': x_fixed, **{k: x1[f'{k}_t'] for k in 'ace'}}, n_atoms), ok, table
+        out = list(molecules)
+        flipped = (table[:, 7] != 0).tolist()
+        xs = torch.split(x_fixed, n_atoms.tolist())
+        for i, m in enumerate(out):
+            if flipped[i]:
+                out[i] = self._package({'x': xs[i].clone(), 'a': m.a_1, 'c': m.c_1, 'e': m.e_1}, n_atoms[i:i + 1], None, False, False)[0]
+        return out, ok, table
 
     def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
         """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --

@@ -60,7 +60,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 14
+#define FM_ABI_VERSION 15
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -497,6 +497,32 @@ int fm_pair_rmsd(fm_ctx* ctx, void* stream, const float* x, int n_pairs, const i
                  const int32_t* perm_set, const int32_t* set_off, const int32_t* perms, int n_sets, float* out, int32_t* best_perm);
 int fm_prune_rmsd(fm_ctx* ctx, void* stream, int n_groups, const int32_t* group_off, const float* d, const int32_t* tri_off, float threshold, uint8_t* keep,
                   int32_t* rep);
+
+/* --- ABI 15: the stereo check -- do the conformers keep the handedness of the input's stereocentres and the cis/trans state of its double bonds?
+ *
+ * fm_stereo: x, x_ref (N,3) of the bound batch: the coordinates to check and the coordinates that define the stereo state.
+ *   the element table, or three NULLs and n_sets = 0 for no element at all: elem_set DEVICE (n_mols) int32, a set id per molecule or -1 (none); set_off DEVICE
+ *     (n_sets + 1) int32 ROW offsets into elems; elems DEVICE (rows,5) int32, a row = {kind, i0, i1, i2, i3} with local atom indices.  The layout mirrors
+ *     fm_pair_rmsd's permutation sets; conformers of one graph share a set.  PRECONDITION (device data, not checked here): kind is 0 or 1 (anything else is read
+ *     as 1) and the four indices lie inside every molecule that names the set (an index outside is read as 0: nothing is read out of the molecule).
+ *   value of an element in one coordinate set, float32, every operation separately rounded:
+ *     kind 0 (tetrahedral centre i0 with neighbours i1, i2, i3): (u1 x u2) . u3, u_k the unit vector from i0 to i_k
+ *     kind 1 (double bond i1 = i2 with substituents i0, i3): the cosine of the dihedral i0-i1-i2-i3
+ *     a vector or a normal of zero length gives the value +0, never a NaN
+ *   an element is DEFINED in a set when |value| >= flat_tol, and a MISMATCH when it is defined in both x and x_ref and the two signs differ
+ *   out DEVICE (n_mols,8) int32 = {kind-0 elements, of them defined in both, of them mismatches, kind-1 elements, defined in both, mismatches, match, mirror}:
+ *     match = 1 when every element is defined in both sets and none mismatches (a molecule without elements matches); mirror = 1 when there is a kind-0
+ *     element, every element is defined in both, every kind-0 element mismatches and no kind-1 element does -- what a point inversion of x_ref gives
+ *   values DEVICE float32 with val_off DEVICE (n_mols + 1) int32, both may be NULL: the values of x of molecule m at val_off[m] .., in row order (the caller
+ *     leaves room for the rows of the molecule's set)
+ *   x_out DEVICE (N,3), may be NULL: -x (an exact sign flip) for the atoms of a molecule with mirror = 1, x for the others
+ * One wave per molecule, lanes strided over its rows; the counts are integer sums: a molecule's outputs are a function of that molecule, its rows and
+ * flat_tol -- the same bits whatever else the batch holds; the order of the rows changes the order of values only.
+ * Does not synchronise, allocates nothing.  FM_ERR_INVALID (this call's status for every refusal), before anything is enqueued, for no bound batch, an output
+ * that aliases an input or another output, values without val_off, a partial element table, and a flat_tol that is negative or NaN. */
+int fm_stereo(fm_ctx* ctx, void* stream, const float* x, const float* x_ref, const int32_t* elem_set /* (n_mols), -1 = none */,
+              const int32_t* set_off /* (n_sets+1), in rows */, const int32_t* elems /* (rows,5) */, int n_sets, float flat_tol, int32_t* out /* (n_mols,8) */,
+              const int32_t* val_off /* (n_mols+1) or NULL */, float* values /* or NULL */, float* x_out /* (N,3) or NULL */);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
