@@ -11,11 +11,12 @@ import ctypes as C
 import os
 from pathlib import Path
 
-FM_ABI_VERSION = 15
+FM_ABI_VERSION = 16
 FM_DFM_CAMPBELL, FM_DFM_GAT = 0, 1
 FM_NOISE_TENSORS, FM_NOISE_PHILOX = 0, 1
 FM_PREC_F32, FM_PREC_BF16X3, FM_PREC_BF16X6, FM_PREC_F16X3 = 0, 1, 2, 3
 FM_MAX_CONVS = 16
+FM_OT_MAX_ATOMS = 256      # the largest molecule fm_ot_align takes
 FM_TAB_SLOTS = 32      # embedding tables per bound batch = the most time groups of a mixed-time call
 # fm_prior_kind, by the reference's prior names (flowmol/data_processing/priors.py)
 FM_PRIOR_KINDS = {'gaussian': 0, 'uniform-simplex': 1, 'barycenter': 2, 'biased-simplex': 3, 'marginal': 4, 'c-given-a': 5}
@@ -175,6 +176,10 @@ _EXPORTS = {
     # ABI 15: the stereo check of conformers against their input
     'fm_stereo': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p]),
+    # ABI 16: equivariant-OT coupling of the position prior, conditional path on a given prior
+    'fm_ot_align': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'fm_conditional_path_x0': (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(fm_state), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(fm_state),
+                                         C.POINTER(fm_cond_tape), C.c_void_p]),
     'fm_set_tap': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fm_clear_taps': (C.c_int, [C.c_void_p]),
     'fm_batch_query': (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),

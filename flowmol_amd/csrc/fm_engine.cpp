@@ -1243,31 +1243,44 @@ int fm_philox_tape(fm_ctx* c, void* stream, const fm_step_scalars* sc, const fm_
     return L.rc;
 }
 
-int fm_conditional_path(fm_ctx* c, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
-                        const fm_state* out, const fm_cond_tape* tape) {
-    if (const int rc = bound_check(c, "fm_conditional_path", x1 && alpha && out)) return rc;
-    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "fm_conditional_path: endpoint models (has_mask = 0) have no masked conditional path");
-    if (n_groups < 1) return fail(c, FM_ERR_INVALID, "fm_conditional_path: n_groups = %d, need at least 1", n_groups);
-    if (n_groups > 1 && !mol_group) return fail(c, FM_ERR_INVALID, "fm_conditional_path: mol_group is NULL with n_groups = %d", n_groups);
+// fm_conditional_path (x0_in = nullptr: the prior is drawn) and fm_conditional_path_x0 (the caller's prior): one kernel, one set of refusals
+static int conditional_path(fm_ctx* c, const char* fn, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                            const fm_state* out, const fm_cond_tape* tape, const float* x0_in) {
+    if (const int rc = bound_check(c, fn, x1 && alpha && out)) return rc;
+    if (!c->cfg.has_mask) return fail(c, FM_ERR_INVALID, "%s: endpoint models (has_mask = 0) have no masked conditional path", fn);
+    if (n_groups < 1) return fail(c, FM_ERR_INVALID, "%s: n_groups = %d, need at least 1", fn, n_groups);
+    if (n_groups > 1 && !mol_group) return fail(c, FM_ERR_INVALID, "%s: mol_group is NULL with n_groups = %d", fn, n_groups);
     const FmBatch& b = c->ws.b;
-    if (!x1->x_t || !out->x_t) return fail(c, FM_ERR_INVALID, "fm_conditional_path: null argument");
-    if (out->x_t == x1->x_t) return fail(c, FM_ERR_INVALID, "fm_conditional_path: out->x_t aliases x1->x_t (the call is not in-place)");
+    if (!x1->x_t || !out->x_t) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    if (out->x_t == x1->x_t) return fail(c, FM_ERR_INVALID, "%s: out->x_t aliases x1->x_t (the call is not in-place)", fn);
+    if (x0_in && (x0_in == out->x_t || (tape && x0_in == tape->x0))) return fail(c, FM_ERR_INVALID, "%s: x0_in aliases out->x_t or tape->x0", fn);
     FmCondArgs a{};
     static const char* const tag[3] = {"a_t", "c_t", "e_t"};
     for (int m = 0; m < 3; ++m) {
         const Modality md = modality(c, m);
         const int32_t* const t1 = pick3(m, x1->a_t, x1->c_t, x1->e_t);
         int32_t* const to = pick3(m, out->a_t, out->c_t, out->e_t);
-        if (md.rows > 0 && (!t1 || !to)) return fail(c, FM_ERR_INVALID, "fm_conditional_path: null argument");
-        if (to && to == t1) return fail(c, FM_ERR_INVALID, "fm_conditional_path: out->%s aliases x1->%s (the call is not in-place)", tag[m], tag[m]);
+        if (md.rows > 0 && (!t1 || !to)) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+        if (to && to == t1) return fail(c, FM_ERR_INVALID, "%s: out->%s aliases x1->%s (the call is not in-place)", fn, tag[m], tag[m]);
         a.mod[m] = {md.K, t1, to, tape ? pick3(m, tape->u_a, tape->u_c, tape->u_e) : nullptr, md.off};
     }
     a.x1 = x1->x_t; a.x_t = out->x_t; a.x0 = tape ? tape->x0 : nullptr; a.node_off = b.mol_node_off;
     a.mol_gid = c->ws.mol_gid; a.mol_group = n_groups > 1 ? mol_group : nullptr; a.alpha = alpha;
     a.seed_lo = (unsigned)(seed & 0xffffffffu); a.seed_hi = (unsigned)(seed >> 32);
+    a.x0_in = x0_in;
     Launch L{c, (hipStream_t)stream};
     L("conditional_path", fm_k_conditional_path, dim3(b.B, 4), dim3(256), 0, a);
     return L.rc;
+}
+
+int fm_conditional_path(fm_ctx* c, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                        const fm_state* out, const fm_cond_tape* tape) {
+    return conditional_path(c, "fm_conditional_path", stream, seed, x1, n_groups, mol_group, alpha, out, tape, nullptr);
+}
+
+int fm_conditional_path_x0(fm_ctx* c, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                           const fm_state* out, const fm_cond_tape* tape, const float* x0_in) {
+    return conditional_path(c, "fm_conditional_path_x0", stream, seed, x1, n_groups, mol_group, alpha, out, tape, x0_in);
 }
 
 int fm_forward(fm_ctx* c, void* stream, const fm_state* state, const float* temb, const fm_dst* prev, int bootstrap, int remove_com,
@@ -1584,6 +1597,33 @@ int fm_align_rmsd(fm_ctx* c, void* stream, const float* xa, const float* xb, con
     if (xa_aligned && (const void*)xa_aligned == (const void*)out) return fail(c, FM_ERR_INVALID, "%s: xa_aligned aliases out", fn);
     Launch L{c, (hipStream_t)stream};
     L("align_rmsd", fm_k_align_rmsd, dim3(c->ws.b.B), dim3(64), 0, xa, xb, (const unsigned char*)select, (const int*)c->ws.b.mol_node_off, out, xa_aligned);
+    return L.rc;
+}
+
+// Equivariant-OT coupling of a position prior to the given positions of the bound batch (fm_k_ot_align: one wave per molecule, assignment then rigid fit).  The
+// size cap is checked on the bind's host copy of the offsets: nothing is enqueued for a batch with a molecule above it.
+int fm_ot_align(fm_ctx* c, void* stream, const float* x0, const float* x1c, int allow_reflection, float* x0_aligned, int32_t* perm, float* out) {
+    const char* const fn = "fm_ot_align";
+    if (!c || !x0 || !x1c || !x0_aligned || !out) return fail(c, FM_ERR_INVALID, "%s: null argument", fn);
+    if (!c->bound) return fail(c, FM_ERR_INVALID, "%s: no batch bound", fn);
+    if (allow_reflection != 0 && allow_reflection != 1) return fail(c, FM_ERR_INVALID, "%s: allow_reflection = %d, need 0 or 1", fn, allow_reflection);
+    const void* const in[] = {x0, x1c};
+    const void* const outs[] = {x0_aligned, perm, out};
+    for (int a = 0; a < 3; ++a) {
+        if (!outs[a]) continue;
+        for (const void* p : in)
+            if (p == outs[a]) return fail(c, FM_ERR_INVALID, "%s: an output aliases an input", fn);
+        for (int b = a + 1; b < 3; ++b)
+            if (outs[b] == outs[a]) return fail(c, FM_ERR_INVALID, "%s: an output aliases another output", fn);
+    }
+    const std::vector<int32_t>& off = c->node_off_h;
+    for (int m = 0; m < c->ws.b.B; ++m)
+        if (off[m + 1] - off[m] > FM_OT_MAX_ATOMS)
+            return fail(c, FM_ERR_INVALID, "%s: molecule %d has %d atoms, more than the %d the assignment kernel takes", fn, m, off[m + 1] - off[m], FM_OT_MAX_ATOMS);
+    Launch L{c, (hipStream_t)stream};
+    FmOtArgs g{};
+    g.x0 = x0; g.x1c = x1c; g.node_off = c->ws.b.mol_node_off; g.x0_al = x0_aligned; g.perm = perm; g.out = out; g.allow_reflection = allow_reflection;
+    L("ot_align", fm_k_ot_align, dim3(c->ws.b.B), dim3(64), 0, g);
     return L.rc;
 }
 

@@ -2303,7 +2303,8 @@ static __global__ void __launch_bounds__(256) fm_k_prior_philox_dense(FmPriorDen
 // a_t / c_t / e_t over the molecule's rows (e: unordered pairs), job 3 = the positions.  Molecule m reads row mol_group[m] (row 0 without groups) of
 // alpha (n_groups, 4) = alpha_t of x, a, c, e: workgroup-uniform.
 //   job 3 (:112): x_t = (1 - alpha_x) x_0 + alpha_x (x_1 - per-molecule mean), x_0 = the position prior (fm_prior_x_molecule: fm_prior_philox's bits, staged
-//          through x_t), the mean with fm_k_remove_com's arithmetic, the three operations rounded separately as torch rounds them
+//          through x_t) or, with x0_in (fm_conditional_path_x0: one workgroup-uniform branch), the caller's rows, nothing drawn; the mean with
+//          fm_k_remove_com's arithmetic, the three operations rounded separately as torch rounds them
 //   jobs 0..2 (:122-134): tok_t = u < 1 - alpha ? mask : tok_1, u = fm_u01(word 0 of block 8) of counter (global molecule id, row, 0xFFFFFFFE - job, 8):
 //          blocks 0..7 of that c2 are the dense priors' (endpoint models), block 8 is this entry's
 // Optional tape: x0 (N,3) and the uniforms u (rows) the call consumed.  Reads x1 only; writes out and the tape only.
@@ -2314,6 +2315,7 @@ struct FmCondArgs {
     const float* x1; float* x_t; float* x0; const int* node_off;
     const int* mol_gid; const int* mol_group; const float* alpha;
     unsigned seed_lo, seed_hi;
+    const float* x0_in;      // fm_conditional_path_x0: the position prior to use, nothing is drawn for x; null = fm_prior_x_molecule's
 };
 
 static __global__ void __launch_bounds__(256) fm_k_conditional_path(FmCondArgs a) {
@@ -2325,7 +2327,7 @@ static __global__ void __launch_bounds__(256) fm_k_conditional_path(FmCondArgs a
         const float ax = al[0], bx = fm_sub_rn(1.0f, ax);
         __shared__ float com[3];
         if (tid < 64) {
-            fm_prior_x_molecule(a.x_t, n0, n1, gid, tid, a.seed_lo, a.seed_hi);      // x_0, read back behind the barrier
+            if (!a.x0_in) fm_prior_x_molecule(a.x_t, n0, n1, gid, tid, a.seed_lo, a.seed_hi);      // x_0, read back behind the barrier
             float sx = 0.f, sy = 0.f, sz = 0.f;          // the 64-lane strided sum + xor tree of fm_k_remove_com: identical rounding
             for (int n = n0 + tid; n < n1; n += 64) { sx += a.x1[n * 3]; sy += a.x1[n * 3 + 1]; sz += a.x1[n * 3 + 2]; }
 #pragma unroll
@@ -2334,8 +2336,9 @@ static __global__ void __launch_bounds__(256) fm_k_conditional_path(FmCondArgs a
             if (tid == 0) { com[0] = sx * inv; com[1] = sy * inv; com[2] = sz * inv; }
         }
         __syncthreads();
+        const float* const prior = a.x0_in ? a.x0_in : a.x_t;
         for (int i = n0 * 3 + tid; i < n1 * 3; i += 256) {
-            const float x0 = a.x_t[i], x1c = a.x1[i] - com[(i - n0 * 3) % 3];
+            const float x0 = prior[i], x1c = a.x1[i] - com[(i - n0 * 3) % 3];
             if (a.x0) a.x0[i] = x0;
             a.x_t[i] = fm_add_rn(fm_mul_rn(bx, x0), fm_mul_rn(ax, x1c));
         }
@@ -2467,8 +2470,10 @@ __device__ __forceinline__ float fm_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fm_add_rn(v, __shfl_xor(v, o));
     return v;
 }
-// the rotation of the unit quaternion that maximises q^T N(S) q, row-major in R
-__device__ __forceinline__ void fm_horn_rotation(const float (&S)[3][3], float (&R)[9]) {
+// the rotation of the unit quaternion that maximises q^T N(S) q, row-major in R.  allow_reflection != 0: the optimum over ALL orthogonal transforms instead
+// (what an SVD Kabsch without the determinant correction finds).  The eigenvalues of N(-S) are those of N(S) negated, so the one decomposition serves both:
+// when -lambda_min > lambda_max the best improper transform, -R(q_min), beats the best rotation and is returned; on a tie the rotation is.
+__device__ __forceinline__ void fm_horn_rotation(const float (&S)[3][3], float (&R)[9], int allow_reflection = 0) {
     float A[4][4], V[4][4];
     A[0][0] = fm_add_rn(fm_add_rn(S[0][0], S[1][1]), S[2][2]);
     A[1][1] = fm_sub_rn(fm_sub_rn(S[0][0], S[1][1]), S[2][2]);
@@ -2506,8 +2511,10 @@ __device__ __forceinline__ void fm_horn_rotation(const float (&S)[3][3], float (
             }
         }
     }
-    int best = 0;
-    for (int i = 1; i < 4; ++i) if (A[i][i] > A[best][best]) best = i;
+    int best = 0, worst = 0;
+    for (int i = 1; i < 4; ++i) { if (A[i][i] > A[best][best]) best = i; if (A[i][i] < A[worst][worst]) worst = i; }
+    const bool reflect = allow_reflection != 0 && -A[worst][worst] > A[best][best];
+    if (reflect) best = worst;
     float w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
     const float nrm = sqrtf(fm_add_rn(fm_add_rn(fm_mul_rn(w, w), fm_mul_rn(x, x)), fm_add_rn(fm_mul_rn(y, y), fm_mul_rn(z, z))));
     w = fm_div_rn(w, nrm); x = fm_div_rn(x, nrm); y = fm_div_rn(y, nrm); z = fm_div_rn(z, nrm);
@@ -2516,54 +2523,181 @@ __device__ __forceinline__ void fm_horn_rotation(const float (&S)[3][3], float (
     R[0] = fm_sub_rn(fm_add_rn(ww, xx), fm_add_rn(yy, zz)); R[1] = fm_mul_rn(2.f, fm_sub_rn(xy, wz)); R[2] = fm_mul_rn(2.f, fm_add_rn(xz, wy));
     R[3] = fm_mul_rn(2.f, fm_add_rn(xy, wz)); R[4] = fm_sub_rn(fm_add_rn(ww, yy), fm_add_rn(xx, zz)); R[5] = fm_mul_rn(2.f, fm_sub_rn(yz, wx));
     R[6] = fm_mul_rn(2.f, fm_sub_rn(xz, wy)); R[7] = fm_mul_rn(2.f, fm_add_rn(yz, wx)); R[8] = fm_sub_rn(fm_add_rn(ww, zz), fm_add_rn(xx, yy));
+    if (reflect) for (int k = 0; k < 9; ++k) R[k] = -R[k];
+}
+// The three rounds of one molecule, for the 64 lanes of its wave (fm_k_align_rmsd, fm_k_ot_align): xa, xb, sel (may be null) and xa_al (may be null) point at the
+// molecule's first atom, n = its atoms.  Returns false, xa_al = xa, when nothing is selected; otherwise cnt, d0 = sum |a - b|^2 of the centred coordinates and
+// d1 = sum |R a - b|^2, the same bits in every lane.  xa and xb may live in LDS; xa_al may not be xa.
+__device__ __forceinline__ bool fm_rigid_fit(const float* xa, const float* xb, const unsigned char* sel, int n, int lane, int allow_reflection, float* xa_al,
+                                             float& cnt_out, float& d0_out, float& d1_out) {
+    float oa[3] = {0.f, 0.f, 0.f}, ob[3] = {0.f, 0.f, 0.f};      // the molecule's first atom: the origin of every sum
+    if (n > 0) for (int k = 0; k < 3; ++k) { oa[k] = xa[k]; ob[k] = xb[k]; }
+    float cnt = 0.f, ma[3] = {0.f, 0.f, 0.f}, mb[3] = {0.f, 0.f, 0.f};
+    for (int i = lane; i < n; i += 64) {
+        if (sel && !sel[i]) continue;
+        cnt += 1.f;
+        for (int k = 0; k < 3; ++k) { ma[k] = fm_add_rn(ma[k], fm_sub_rn(xa[i * 3 + k], oa[k])); mb[k] = fm_add_rn(mb[k], fm_sub_rn(xb[i * 3 + k], ob[k])); }
+    }
+    cnt = fm_wave_sum(cnt);
+    if (cnt == 0.f) {      // wave-uniform: nothing selected
+        if (xa_al) for (int i = lane; i < n * 3; i += 64) xa_al[i] = xa[i];
+        return false;
+    }
+    for (int k = 0; k < 3; ++k) { ma[k] = fm_div_rn(fm_wave_sum(ma[k]), cnt); mb[k] = fm_div_rn(fm_wave_sum(mb[k]), cnt); }
+    float S[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, d0 = 0.f;
+    for (int i = lane; i < n; i += 64) {
+        if (sel && !sel[i]) continue;
+        float a[3], b[3];
+        for (int k = 0; k < 3; ++k) { a[k] = fm_sub_rn(fm_sub_rn(xa[i * 3 + k], oa[k]), ma[k]); b[k] = fm_sub_rn(fm_sub_rn(xb[i * 3 + k], ob[k]), mb[k]); }
+        for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) S[p][q] = fm_add_rn(S[p][q], fm_mul_rn(a[p], b[q]));
+        for (int k = 0; k < 3; ++k) { const float d = fm_sub_rn(a[k], b[k]); d0 = fm_add_rn(d0, fm_mul_rn(d, d)); }
+    }
+    for (int p = 0; p < 3; ++p) for (int q = 0; q < 3; ++q) S[p][q] = fm_wave_sum(S[p][q]);
+    d0 = fm_wave_sum(d0);
+    float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    if (lane == 0) fm_horn_rotation(S, R, allow_reflection);
+    for (int k = 0; k < 9; ++k) R[k] = __shfl(R[k], 0);
+    float d1 = 0.f;
+    for (int i = lane; i < n; i += 64) {
+        float a[3], r[3];
+        for (int k = 0; k < 3; ++k) a[k] = fm_sub_rn(fm_sub_rn(xa[i * 3 + k], oa[k]), ma[k]);
+        for (int k = 0; k < 3; ++k) r[k] = fm_add_rn(fm_add_rn(fm_mul_rn(R[k * 3], a[0]), fm_mul_rn(R[k * 3 + 1], a[1])), fm_mul_rn(R[k * 3 + 2], a[2]));
+        if (xa_al) for (int k = 0; k < 3; ++k) xa_al[i * 3 + k] = fm_add_rn(fm_add_rn(r[k], mb[k]), ob[k]);
+        if (sel && !sel[i]) continue;
+        for (int k = 0; k < 3; ++k) {
+            const float d = fm_sub_rn(r[k], fm_sub_rn(fm_sub_rn(xb[i * 3 + k], ob[k]), mb[k]));
+            d1 = fm_add_rn(d1, fm_mul_rn(d, d));
+        }
+    }
+    cnt_out = cnt; d0_out = d0; d1_out = fm_wave_sum(d1);
+    return true;
 }
 static __global__ void __launch_bounds__(64) fm_k_align_rmsd(const float* __restrict__ xa, const float* __restrict__ xb, const unsigned char* __restrict__ sel,
                                                              const int* __restrict__ node_off, float* __restrict__ out, float* __restrict__ xa_al) {
     const int mol = blockIdx.x, lane = threadIdx.x;
-    const int n0 = node_off[mol], n1 = node_off[mol + 1];
-    float oa[3] = {0.f, 0.f, 0.f}, ob[3] = {0.f, 0.f, 0.f};      // the molecule's first atom: the origin of every sum
-    if (n1 > n0) for (int k = 0; k < 3; ++k) { oa[k] = xa[n0 * 3 + k]; ob[k] = xb[n0 * 3 + k]; }
-    float cnt = 0.f, ma[3] = {0.f, 0.f, 0.f}, mb[3] = {0.f, 0.f, 0.f};
-    for (int n = n0 + lane; n < n1; n += 64) {
-        if (sel && !sel[n]) continue;
-        cnt += 1.f;
-        for (int k = 0; k < 3; ++k) { ma[k] = fm_add_rn(ma[k], fm_sub_rn(xa[n * 3 + k], oa[k])); mb[k] = fm_add_rn(mb[k], fm_sub_rn(xb[n * 3 + k], ob[k])); }
-    }
-    cnt = fm_wave_sum(cnt);
-    if (cnt == 0.f) {      // wave-uniform: nothing selected
+    const int n0 = node_off[mol], n = node_off[mol + 1] - n0;
+    float cnt, d0, d1;
+    if (!fm_rigid_fit(xa + (size_t)n0 * 3, xb + (size_t)n0 * 3, sel ? sel + n0 : nullptr, n, lane, 0, xa_al ? xa_al + (size_t)n0 * 3 : nullptr, cnt, d0, d1)) {
         if (lane < 4) out[mol * 4 + lane] = 0.f;
-        if (xa_al) for (int i = n0 * 3 + lane; i < n1 * 3; i += 64) xa_al[i] = xa[i];
         return;
     }
-    for (int k = 0; k < 3; ++k) { ma[k] = fm_div_rn(fm_wave_sum(ma[k]), cnt); mb[k] = fm_div_rn(fm_wave_sum(mb[k]), cnt); }
-    float S[3][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}}, d0 = 0.f;
-    for (int n = n0 + lane; n < n1; n += 64) {
-        if (sel && !sel[n]) continue;
-        float a[3], b[3];
-        for (int k = 0; k < 3; ++k) { a[k] = fm_sub_rn(fm_sub_rn(xa[n * 3 + k], oa[k]), ma[k]); b[k] = fm_sub_rn(fm_sub_rn(xb[n * 3 + k], ob[k]), mb[k]); }
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = fm_add_rn(S[i][j], fm_mul_rn(a[i], b[j]));
-        for (int k = 0; k < 3; ++k) { const float d = fm_sub_rn(a[k], b[k]); d0 = fm_add_rn(d0, fm_mul_rn(d, d)); }
-    }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[i][j] = fm_wave_sum(S[i][j]);
-    d0 = fm_wave_sum(d0);
-    float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
-    if (lane == 0) fm_horn_rotation(S, R);
-    for (int k = 0; k < 9; ++k) R[k] = __shfl(R[k], 0);
-    float d1 = 0.f;
-    for (int n = n0 + lane; n < n1; n += 64) {
-        float a[3], r[3];
-        for (int k = 0; k < 3; ++k) a[k] = fm_sub_rn(fm_sub_rn(xa[n * 3 + k], oa[k]), ma[k]);
-        for (int k = 0; k < 3; ++k) r[k] = fm_add_rn(fm_add_rn(fm_mul_rn(R[k * 3], a[0]), fm_mul_rn(R[k * 3 + 1], a[1])), fm_mul_rn(R[k * 3 + 2], a[2]));
-        if (xa_al) for (int k = 0; k < 3; ++k) xa_al[n * 3 + k] = fm_add_rn(fm_add_rn(r[k], mb[k]), ob[k]);
-        if (sel && !sel[n]) continue;
-        for (int k = 0; k < 3; ++k) {
-            const float d = fm_sub_rn(r[k], fm_sub_rn(fm_sub_rn(xb[n * 3 + k], ob[k]), mb[k]));
-            d1 = fm_add_rn(d1, fm_mul_rn(d, d));
-        }
-    }
-    d1 = fm_wave_sum(d1);
     if (lane == 0) {
         out[mol * 4] = cnt; out[mol * 4 + 1] = sqrtf(fm_div_rn(d0, cnt)); out[mol * 4 + 2] = sqrtf(fm_div_rn(d1, cnt)); out[mol * 4 + 3] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Equivariant-OT coupling of the position prior to given molecules (fm_ot_align; reference flowmol/data_processing/priors.py:109-169 align_prior with
+// permutation=True, rigid_body=True, as coupled_node_prior :267-303 calls it for every training and validation sample): molecule by molecule,
+//   A  perm = the linear assignment that minimises sum_i c(i, perm[i]),  c(i, j) = sqrtf(((dx dx) + (dy dy)) + (dz dz)), d = x1c[i] - x0[j], every operation float32
+//      and separately rounded (the reference's torch.cdist(x_1, x_0) up to its rounding); x0p[i] = x0[perm[i]]
+//   B  the rigid fit of x0p onto x1c: the rounds of fm_rigid_fit, with allow_reflection the optimum over all orthogonal transforms (the reference's
+//      rigid_alignment has no determinant correction), x0_al = R (x0p - mean0) + mean1
+// out[m] = {n, sum_i c(i, perm[i]) -- float64 in atom order, rounded once --, sqrt(mean |x0p - x1c|^2) (nothing centred), sqrt(mean |x0_al - x1c|^2)}.
+// One wave per molecule, n <= FM_OT_MAX_ATOMS (the entry point refuses more before the launch).  LDS is O(n): both coordinate sets and the solver's vectors; the
+// cost of a pair is recomputed from the coordinates whenever it is needed.
+// SOLVER: shortest augmenting paths (Jonker-Volgenant as Crouse states it, the algorithm of scipy's linear_sum_assignment).  Rows are inserted in order; a row's
+// search grows a tree of alternating paths: per iteration every unscanned column j = lane, lane + 64, ... relaxes its path cost
+// (min_val + c(i, j)) - u[i] - v[j] from the row i scanned last, and the column of the smallest path cost -- on equal values the LOWEST column index -- is scanned
+// next, found by the xor tree over (value, index), which leaves the same pair in every lane.  The search ends at the first unassigned column; the duals of the tree
+// are updated and lane 0 flips the path.  Duals, path costs and minima are float64: a molecule's float32 costs span far fewer than 2^29, so every sum and
+// difference of up to n of them is exact, the reduced costs carry no rounding at all and the assignment is exactly optimal for the float32 cost matrix.
+// A search that finds no finite path cost (a coordinate that is not a number) ends the solver: the permutation is then the identity.
+// ------------------------------------------------------------------------------------------------
+struct FmOtArgs {      // FM_OT_MAX_ATOMS: include/flowmol_hip.h
+    const float* x0; const float* x1c; const int* node_off;
+    float* x0_al; int* perm; float* out; int allow_reflection;
+};
+__device__ __forceinline__ double fm_shfl_xor_f64(double v, int o) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(b & 0xffffffffull), o), hi = (unsigned)__shfl_xor((int)(unsigned)(b >> 32), o);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ float fm_ot_cost(const float* a, const float* b) {
+    const float dx = fm_sub_rn(a[0], b[0]), dy = fm_sub_rn(a[1], b[1]), dz = fm_sub_rn(a[2], b[2]);
+    return sqrtf(fm_add_rn(fm_add_rn(fm_mul_rn(dx, dx), fm_mul_rn(dy, dy)), fm_mul_rn(dz, dz)));
+}
+static __global__ void __launch_bounds__(64) fm_k_ot_align(FmOtArgs g) {
+    const int mol = blockIdx.x, lane = threadIdx.x;
+    const int n0 = g.node_off[mol], n = g.node_off[mol + 1] - n0;
+    if (n <= 0 || n > FM_OT_MAX_ATOMS) {      // wave-uniform; above the cap nothing is launched (fm_ot_align), so nothing is written here either
+        if (n <= 0 && lane < 4) g.out[mol * 4 + lane] = 0.f;
+        return;
+    }
+    __shared__ float xr[FM_OT_MAX_ATOMS * 3], xc[FM_OT_MAX_ATOMS * 3], xp[FM_OT_MAX_ATOMS * 3];      // rows = atoms of x1c, columns = rows of x0, x0p
+    __shared__ double u[FM_OT_MAX_ATOMS], v[FM_OT_MAX_ATOMS], sp[FM_OT_MAX_ATOMS];                 // row duals, column duals, path cost of a column
+    __shared__ int path[FM_OT_MAX_ATOMS], row4col[FM_OT_MAX_ATOMS], col4row[FM_OT_MAX_ATOMS];
+    __shared__ unsigned char scanned[FM_OT_MAX_ATOMS];
+    for (int i = lane; i < n * 3; i += 64) { xr[i] = g.x1c[(size_t)n0 * 3 + i]; xc[i] = g.x0[(size_t)n0 * 3 + i]; }
+    for (int j = lane; j < n; j += 64) { u[j] = 0.0; v[j] = 0.0; row4col[j] = -1; col4row[j] = -1; }
+    __syncthreads();
+    const double inf = __builtin_huge_val();
+    bool solved = true;
+    for (int cur = 0; cur < n; ++cur) {
+        for (int j = lane; j < n; j += 64) { sp[j] = inf; scanned[j] = 0; }      // a lane's own columns: read back by that lane alone
+        double min_val = 0.0;
+        int i = cur, sink = -1;
+        while (sink < 0) {
+            const double ui = u[i];
+            double best = inf;
+            int bj = 0x7fffffff;
+            for (int j = lane; j < n; j += 64) {
+                if (scanned[j]) continue;
+                const double r = ((min_val + (double)fm_ot_cost(xr + i * 3, xc + j * 3)) - ui) - v[j];
+                double s = sp[j];
+                if (r < s) { s = r; sp[j] = r; path[j] = i; }
+                if (s < best) { best = s; bj = j; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = fm_shfl_xor_f64(best, o);
+                const int oj = __shfl_xor(bj, o);
+                if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+            }
+            if (bj == 0x7fffffff) { solved = false; break; }      // wave-uniform: no finite path cost
+            min_val = best;
+            if ((bj & 63) == lane) scanned[bj] = 1;
+            const int r4 = row4col[bj];
+            if (r4 < 0) sink = bj; else i = r4;
+        }
+        if (!solved) break;
+        for (int j = lane; j < n; j += 64) {      // the tree's duals; its columns but the sink are assigned, to distinct rows
+            if (!scanned[j] || j == sink) continue;
+            const double d = min_val - sp[j];
+            u[row4col[j]] += d; v[j] -= d;
+        }
+        if (lane == 0) u[cur] += min_val;
+        __syncthreads();
+        if (lane == 0) {
+            for (int j = sink;;) {
+                const int r = path[j], next = col4row[r];
+                row4col[j] = r; col4row[r] = j;
+                if (r == cur) break;
+                j = next;
+            }
+        }
+        __syncthreads();
+    }
+    if (!solved) {
+        __syncthreads();
+        for (int j = lane; j < n; j += 64) col4row[j] = j;
+    }
+    float dp = 0.f;
+    for (int i = lane; i < n; i += 64) {
+        const int p = col4row[i];
+        for (int k = 0; k < 3; ++k) xp[i * 3 + k] = xc[p * 3 + k];
+        if (g.perm) g.perm[n0 + i] = p;
+        sp[i] = (double)fm_ot_cost(xr + i * 3, xc + p * 3);
+        for (int k = 0; k < 3; ++k) { const float d = fm_sub_rn(xc[p * 3 + k], xr[i * 3 + k]); dp = fm_add_rn(dp, fm_mul_rn(d, d)); }
+    }
+    dp = fm_wave_sum(dp);
+    __syncthreads();
+    float cnt, d0, d1;
+    fm_rigid_fit(xp, xr, nullptr, n, lane, g.allow_reflection, g.x0_al + (size_t)n0 * 3, cnt, d0, d1);
+    if (lane == 0) {
+        double cost = 0.0;
+        for (int i = 0; i < n; ++i) cost += sp[i];
+        g.out[mol * 4] = cnt; g.out[mol * 4 + 1] = (float)cost; g.out[mol * 4 + 2] = sqrtf(fm_div_rn(dp, cnt)); g.out[mol * 4 + 3] = sqrtf(fm_div_rn(d1, cnt));
     }
 }
 

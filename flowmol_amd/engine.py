@@ -519,14 +519,52 @@ class Engine:
             self._check(self.lib.fm_philox_tape(self._ctx, self._stream(), C.byref(sc), C.byref(cs)), 'fm_philox_tape')
         return nz
 
-    def conditional_path(self, x1_state, alphas, mol_group=None, seed: int = None, tape: bool = False):
+    def _check_ot_sizes(self, what: str):
+        """ValueError when a bound molecule is above the cap of fm_ot_align (host-side sizes; nothing is enqueued)."""
+        if self.n_atoms is None:          # no batch bound: the library's refusal
+            return
+        big = (self.n_atoms > _lib.FM_OT_MAX_ATOMS).nonzero().reshape(-1)
+        if big.numel():
+            m = int(big[0])
+            raise ValueError(f"{what}: molecule {m} has {int(self.n_atoms[m])} atoms, the OT coupling takes at most {_lib.FM_OT_MAX_ATOMS}")
+
+    def ot_align(self, x0: torch.Tensor, x1c: torch.Tensor, reflect: bool = True, perm: bool = False):
+        """The equivariant-OT coupling of a position prior ``x0`` to the centred given positions ``x1c`` ((N,3) each, the bound batch's atoms, both used as
+        given), molecule by molecule on the device (fm_ot_align; the reference's ``align_prior(x_0, x_1, permutation=True, rigid_body=True)``,
+        priors.py:109-169): the optimal assignment of prior rows to atoms under the float32 distance, then the rigid fit of the permuted prior onto
+        ``x1c``.  ``reflect`` (default: the reference's behaviour) lets the fit be improper, False takes the optimal proper rotation.  Returns
+        (x0_aligned (N,3), out (B,4) = {n, assignment cost, rmsd after the permutation only, rmsd after the fit}) and, with ``perm``, the (N,) int32 local
+        index of the prior row each atom received.  ValueError, before the call, for a molecule above 256 atoms.  Does not synchronise."""
+        d = self.device
+        x0, x1c = (v.detach().to(d, torch.float32).contiguous() for v in (x0, x1c))
+        if tuple(x0.shape) != (self.N, 3) or tuple(x1c.shape) != (self.N, 3):
+            raise ValueError(f'x0 and x1c must be ({self.N}, 3): the atoms of the bound batch')
+        self._check_ot_sizes('ot_align')
+        moved, out = torch.empty(self.N, 3, device=d), torch.empty(self.B, 4, device=d)
+        pm = torch.empty(self.N, dtype=torch.int32, device=d) if perm else None
+        with self._dev():
+            rc = self.lib.fm_ot_align(self._ctx, self._stream(), _ptr(x0), _ptr(x1c), int(bool(reflect)), _ptr(moved), _ptr(pm), _ptr(out))
+        self._check(rc, 'fm_ot_align')
+        self._keep = [x0, x1c, moved, pm, out]
+        return (moved, out, pm) if perm else (moved, out)
+
+    def conditional_path(self, x1_state, alphas, mol_group=None, seed: int = None, tape: bool = False, coupling: str = 'independent', reflect: bool = True):
         """g_t ~ p(g_t | g_0, g_1) for the bound batch's molecules ``x1_state`` (a token state dict, real categories only; left untouched), the
         reference's CTMCVectorField.sample_conditional_path (ctmc_vector_field.py:97-143) in one launch (fm_conditional_path) with x_0 and the uniforms
         from the per-molecule Philox streams of ``seed``.  ``alphas``: (G, 4) -- or (4,) for one group -- rows of ``alpha_tables(t)[0]``, alpha_t of
         x, a, c, e at each time group's t; ``mol_group`` (B,): every molecule's group (None with one group).  Returns the new state dict; with
-        ``tape`` also {'x0', 'u_a', 'u_c', 'u_e'}: the draws the call consumed."""
+        ``tape`` also {'x0', 'u_a', 'u_c', 'u_e'}: the draws the call consumed.
+
+        ``coupling``: 'independent' pairs every molecule with its own Gaussian draw; 'ot' with the draw after the reference's equivariant-OT alignment
+        (``ot_align`` with ``reflect``; what a checkpoint trained with ``prior_config.x.align: True`` saw): fm_prior_philox, fm_ot_align and
+        fm_conditional_path_x0 back to back on the device.  The tape's 'x0' is then the coupled prior, and the tape also holds 'x0_raw' (the draws before the
+        coupling) and 'perm'.  Tokens and uniforms do not depend on ``coupling``."""
         if seed is None:
             raise ValueError('conditional_path draws from the Philox streams: seed is required')
+        if coupling not in ('independent', 'ot'):
+            raise ValueError(f"coupling must be 'independent' or 'ot', got {coupling!r}")
+        if coupling == 'ot':
+            self._check_ot_sizes('conditional_path')
         d = self.device
         al = torch.as_tensor(alphas).detach().to('cpu', torch.float32).reshape(-1, 4).contiguous()
         G = int(al.shape[0])
@@ -547,6 +585,18 @@ class Engine:
             cs = _lib.fm_cond_tape()
             cs.x0, cs.u_a, cs.u_c, cs.u_e = _ptr(tp['x0']), _ptr(tp['u_a']), _ptr(tp['u_c']), _ptr(tp['u_e'])
         s1, so = self._state_struct(x1_state), self._state_struct(out)
+        if coupling == 'ot':
+            x0_raw = self.prior_philox(seed)
+            x1c = self.remove_com(x1_state['x_t'].detach().to(d, torch.float32).contiguous().clone())
+            x0, _, pm = self.ot_align(x0_raw, x1c, reflect=reflect, perm=True)
+            with self._dev():
+                rc = self.lib.fm_conditional_path_x0(self._ctx, self._stream(), C.c_uint64(seed), C.byref(s1), G, _ptr(group), _ptr(al), C.byref(so),
+                                                     C.byref(cs) if cs is not None else None, _ptr(x0))
+            self._check(rc, 'fm_conditional_path_x0')
+            if tape:
+                tp.update(x0_raw=x0_raw, perm=pm)
+            self._keep = [x1_state, al, group, out, tp, x0_raw, x1c, x0, pm]
+            return (out, tp) if tape else out
         with self._dev():
             rc = self.lib.fm_conditional_path(self._ctx, self._stream(), C.c_uint64(seed), C.byref(s1), G, _ptr(group), _ptr(al), C.byref(so),
                                               C.byref(cs) if cs is not None else None)
@@ -779,16 +829,16 @@ class Engine:
         return dst[final.value]
 
     # ------------------------------------------------------------------ frozen atoms (replacement conditioning)
-    def inpaint_spec(self, x1_state, keep, seed: int) -> Dict[str, torch.Tensor]:
+    def inpaint_spec(self, x1_state, keep, seed: int, coupling: str = 'independent') -> Dict[str, torch.Tensor]:
         """The tensors of an ``fm_inpaint`` struct for the bound batch (and its molecule ids): ``keep`` (N,) marks the atoms of the given molecules
         ``x1_state`` that stay as given.  'x0' and 'u_a' / 'u_c' / 'u_e' are the tape of ``conditional_path(x1_state, ..., seed, tape=True)`` (they do not
         depend on alpha), 'x1c' the given positions after ``remove_com``, 'a1' / 'c1' / 'e1' copies of the given tokens, 'keep_pair' (U,) scratch that
-        every call fills.  ``x1_state`` is left untouched."""
+        every call fills.  ``x1_state`` is left untouched.  ``coupling`` as in ``conditional_path``: with 'ot' the frozen positions follow the coupled path."""
         d = self.device
         k = torch.as_tensor(keep).detach().reshape(-1)
         if k.shape[0] != self.N:
             raise ValueError(f'keep has {k.shape[0]} entries, the bound batch {self.N} atoms')
-        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True)
+        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True, coupling=coupling)
         return {'keep_atom': (k != 0).to(torch.uint8).to(d).contiguous(), 'keep_pair': torch.zeros(self.U, dtype=torch.uint8, device=d),
                 'x0': tape['x0'], 'x1c': self.remove_com(x1_state['x_t'].detach().to(d, torch.float32).contiguous().clone()),
                 'a1': x1_state['a_t'].detach().to(d, torch.int32).contiguous().clone(), 'c1': x1_state['c_t'].detach().to(d, torch.int32).contiguous().clone(),
@@ -801,11 +851,12 @@ class Engine:
             setattr(s, name, _ptr(spec[name]) if spec[name].numel() else None)      # a batch without pairs: empty pair tensors travel as NULL
         return s
 
-    def freeze_spec(self, x1_state, keep: Dict[str, torch.Tensor], seed: int) -> Dict[str, Optional[torch.Tensor]]:
+    def freeze_spec(self, x1_state, keep: Dict[str, torch.Tensor], seed: int, coupling: str = 'independent') -> Dict[str, Optional[torch.Tensor]]:
         """The tensors of an ``fm_freeze`` struct for the bound batch (and its molecule ids): frozen rows per modality.  ``keep``: a dict with any of the
         keys 'x', 'a', 'c' ((N,) bool: positions, atom types, charges) and 'e' ((U,) bool, the pair order of ``e_t``); a missing key -- or None -- leaves
         that modality free: its keep array and its path inputs stay None and travel as NULL.  The other members are those of ``inpaint_spec``, of which
-        this is the general form: 'x': k, 'a': k, 'c': k, 'e': both atoms in k gives the bits of ``inpaint_spec(x1_state, k, seed)``."""
+        this is the general form: 'x': k, 'a': k, 'c': k, 'e': both atoms in k gives the bits of ``inpaint_spec(x1_state, k, seed)``.  ``coupling`` as in
+        ``conditional_path``: it changes 'x0' alone, so it matters only with an 'x' part."""
         unknown = set(keep) - set('xace')
         if unknown:
             raise ValueError(f"keep has unknown keys {sorted(unknown)}: 'x', 'a', 'c' (atoms) and 'e' (pairs) are the modalities")
@@ -819,7 +870,7 @@ class Engine:
             if k.shape[0] != rows:
                 raise ValueError(f"keep['{f}'] has {k.shape[0]} entries, the bound batch {rows} {'pairs' if f == 'e' else 'atoms'}")
             flags[f] = (k != 0).to(torch.uint8).to(d).contiguous()
-        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True)
+        _, tape = self.conditional_path(x1_state, [1.0, 1.0, 1.0, 1.0], seed=seed, tape=True, coupling=coupling)
         spec = {name: None for name, _ in _lib.fm_freeze._fields_}
         if 'x' in flags:
             spec.update(keep_x=flags['x'], x0=tape['x0'], x1c=self.remove_com(x1_state['x_t'].detach().to(d, torch.float32).contiguous().clone()))

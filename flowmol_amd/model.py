@@ -155,6 +155,8 @@ class FlowMol:
         # what FlowMol.forward reads besides the network (flowmol.py:29-55, the reference's defaults for missing keys): the defaults of denoising_loss
         defaults = {'time_scaled_loss': True, 'weight_ae': False, 'target_blur': 0.0, 'distort_p': 0.0, 'distort_t': 0.5, 'total_loss_weights': None}
         model.loss_hparams = {k: hp.get(k, v) for k, v in defaults.items()}
+        # the dataset pairs x_1 with an OT-aligned prior when prior_config.x.align is set (priors.py:267-303): the default coupling of denoising_loss
+        model.loss_hparams['prior_align_x'] = bool(((hp.get('prior_config') or {}).get('x') or {}).get('align', False))
         return model
 
     # nn.Module-ish conveniences of the documented usage (readme.md:44-49)
@@ -334,7 +336,7 @@ class FlowMol:
     # ------------------------------------------------------------------ resampling given molecules
     @torch.no_grad()
     def resample(self, molecules, start_step, n_timesteps=None, seed=None, mol_ids=None, stochasticity=None, high_confidence_threshold=None,
-                 return_tensors=False, xt_traj=False, ep_traj=False, keep=None, **kwargs):
+                 return_tensors=False, xt_traj=False, ep_traj=False, keep=None, coupling='independent', **kwargs):
         """Variations of given molecules (no reference entry point; its parts are the reference's): molecule *i* is noised back to time point
         ``k = start_step[i]`` of its ``T = n_timesteps[i]``-point schedule, ``t = linspace(0, 1, T)[k]``, with the model's own corruption process
         (CTMCVectorField.sample_conditional_path, ctmc_vector_field.py:97-143: the distribution the network was trained on), and then takes steps
@@ -361,7 +363,13 @@ class FlowMol:
         (bonds: a bool tensor over the concatenated unordered pairs, or one sequence of n (n - 1) / 2 entries per molecule in upper-triangle order, the
         order of ``e``).  The four are independent -- every type, charge and bond frozen with the positions free gives conformers of the given graph
         (``conformers``), 'x' alone fixes a pose and lets the chemistry run, a bond may be frozen between two free atoms -- and a missing key leaves
-        that modality free.  {'x': k, 'a': k, 'c': k, 'e': both atoms in k} is ``keep=k`` bit for bit; an all-False dict is the call without ``keep``."""
+        that modality free.  {'x': k, 'a': k, 'c': k, 'e': both atoms in k} is ``keep=k`` bit for bit; an all-False dict is the call without ``keep``.
+
+        ``coupling``: 'independent' (default) corrupts with the molecule's own Gaussian draw, and ``resample(mols, 0, T)`` is ``sample`` as stated above.
+        'ot' pairs the draw with the molecule the way the reference's datasets do for every shipped config (``prior_config.x.align: True``: optimal
+        assignment, then a rigid fit that may reflect; ``Engine.ot_align``, priors.py:109-169), which is the path a checkpoint trained that way saw: the
+        start state and, under a ``keep`` that freezes positions, the frozen path use the coupled prior.  Per molecule, so the bit-for-bit single-molecule
+        statement holds.  ValueError, before the bind, for any other value and, with 'ot', a molecule above 256 atoms; not sharded, no command line."""
         cfg = self.cfg
         # ---- arguments: every refusal before the bind and before anything is enqueued; no generator is touched
         if cfg.parameterization == 'endpoint':
@@ -380,6 +388,7 @@ class FlowMol:
         if dfm_type == 'gat' and (ks is not None or Ts is not None):
             raise NotImplementedError("resample with per-molecule start_step / n_timesteps: dfm_type 'gat' is not supported")
         x1, n_atoms = self._given_molecules(molecules)
+        _check_coupling(coupling, n_atoms, 'resample')
         B = int(n_atoms.numel())
         keep = _keep_rows(keep, n_atoms)
         ks = [int(start_step)] * B if ks is None else ks
@@ -420,12 +429,12 @@ class FlowMol:
             st1 = eng.make_state(st1['x_t'], st1['a_t'], st1['c_t'], st1['e_t'])
             keys = sorted({(Ts[i], ks[i]) for i in part})
             group = [keys.index((Ts[i], ks[i])) for i in part]
-            state = eng.conditional_path(st1, torch.stack([alphas[key] for key in keys]), group if len(keys) > 1 else None, seed=int(seed))
+            state = eng.conditional_path(st1, torch.stack([alphas[key] for key in keys]), group if len(keys) > 1 else None, seed=int(seed), coupling=coupling)
             spec = None
             if isinstance(kept, dict):
-                spec = eng.freeze_spec(st1, {f: torch.cat([blocks[i] for i in part]) for f, blocks in kept.items()}, int(seed))
+                spec = eng.freeze_spec(st1, {f: torch.cat([blocks[i] for i in part]) for f, blocks in kept.items()}, int(seed), coupling=coupling)
             elif kept is not None:
-                spec = eng.inpaint_spec(st1, torch.cat([kept[i] for i in part]), int(seed))
+                spec = eng.inpaint_spec(st1, torch.cat([kept[i] for i in part]), int(seed), coupling=coupling)
             t0 = time.perf_counter()
             if len(keys) == 1:
                 (T, k), traj, init = keys[0], None, None
@@ -451,7 +460,8 @@ class FlowMol:
         return self._finish(final, n_atoms, frames if not return_tensors else None, return_tensors, False, xt_traj, ep_traj, t_integrate)
 
     def inpaint(self, molecules, keep, n_timesteps=None, seed=None, mol_ids=None, **kwargs):
-        """Generate the free atoms of ``molecules`` from the prior around the kept ones: ``resample(molecules, 0, n_timesteps, keep=keep, ...)``."""
+        """Generate the free atoms of ``molecules`` from the prior around the kept ones: ``resample(molecules, 0, n_timesteps, keep=keep, ...)``;
+        ``coupling='ot'`` (a keyword of ``resample``) lets the kept positions follow the coupled path."""
         return self.resample(molecules, 0, n_timesteps, seed=seed, mol_ids=mol_ids, keep=keep, **kwargs)
 
     def conformers(self, molecules, n_conformers=1, n_timesteps=None, seed=None, mol_ids=None, start_step=0, **kwargs):
@@ -459,7 +469,8 @@ class FlowMol:
         every pair's bond order are frozen and the positions are left free -- ``resample(repeated molecules, start_step, n_timesteps, seed=seed,
         mol_ids=mol_ids, keep={'a': all, 'c': all, 'e': all})``, whose other arguments and refusals it takes.  ``mol_ids`` (B * n_conformers entries,
         default 0 .. B * n_conformers - 1) name the Philox streams: two conformers of a molecule differ because their streams do.  Returns the flat list of
-        B * n_conformers molecules (``return_tensors`` as in ``resample``); on models with alpha(1) = 1 the tokens of every result are the input's."""
+        B * n_conformers molecules (``return_tensors`` as in ``resample``); on models with alpha(1) = 1 the tokens of every result are the input's.
+        ``coupling`` (a keyword of ``resample``, default 'independent'): with ``start_step > 0`` and 'ot' the conformers start from the coupled path."""
         if self.cfg.parameterization == 'endpoint':          # resample's refusal, before the molecules are read as tokens of a CTMC model
             raise NotImplementedError('conformers: endpoint models are not supported (they have no masked conditional path)')
         K = int(n_conformers)
@@ -602,6 +613,7 @@ class FlowMol:
         gives) and then drops what still mismatches.  The lists then have between 0 and ``n_conformers`` members; nothing is sampled again to fill them
         up.  None is the call without the argument.  ``stereo`` together with ``return_tensors`` or trajectories, any other value, and a conformer
         whose tokens are not the input's (a model with alpha(1) < 1) are a ValueError.
+        ``coupling`` goes to ``conformers`` with the other keywords; the coordinates stay on the device with either value.
         Not covered: sharding across ranks, the command line."""
         K = int(n_conformers)
         if stereo not in (None, 'match', 'mirror'):
@@ -705,7 +717,7 @@ class FlowMol:
                 out[i] = self._package({'x': xs[i].clone(), 'a': m.a_1, 'c': m.c_1, 'e': m.e_1}, n_atoms[i:i + 1], None, False, False)[0]
         return out, ok, table
 
-    def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None):
+    def denoising_loss(self, molecules, t, seed=None, mol_ids=None, distort=None, time_scaled=None, total_loss_weights=None, coupling=None):
         """The denoising losses of given molecules: the reference's ``FlowMol.forward(g)`` (flowmol.py:297-415, what its ``validation_step`` logs) --
         corrupt every molecule to its time ``t``, evaluate the network once, and compare its logits and positions with the molecule.  The standard check
         of a ported checkpoint: compare ``losses`` on a few hundred dataset molecules with what training logged.
@@ -716,6 +728,11 @@ class FlowMol:
         hparams (``self.loss_hparams``; presets: off).  Per call: centre, ``Engine.conditional_path``, optional ``Engine.distort``,
         ``Engine.denoising_loss``; more than 32 distinct ``t`` are served by sorting on ``t`` and binding several batches, which canonical arithmetic makes
         invisible: molecule *i* of any call is, bit for bit, ``denoising_loss([mol_i], t[i], seed=s, mol_ids=[id_i])``.
+
+        ``coupling`` ('independent' | 'ot' | None): how x_0 is paired with x_1.  The reference's loaders hand ``forward`` an x_0 that was OT-aligned to the
+        molecule whenever ``prior_config.x.align`` is set (priors.py:267-303; every shipped config), so the logged position loss is that of 'ot'.  None
+        follows the checkpoint (``loss_hparams['prior_align_x']``); presets and an empty ``loss_hparams`` give 'independent'.  Per molecule, so the
+        bit-for-bit statement above holds for both.  ValueError for another value and, with 'ot', a molecule above 256 atoms.
 
         Returns ``per_molecule`` (B,8) = {se_x, 3 n_atoms, nll_a, cnt_a, nll_c, cnt_c, nll_e, cnt_e} and ``rows`` {'x', 'a', 'c' (N), 'e' (U)} (CPU), and
         ``losses`` {'x', 'a', 'c', 'e'}: the reference's four batch values, formed from the table on the host as its code forms them (:388-413).
@@ -736,6 +753,9 @@ class FlowMol:
         if seed is None:
             raise ValueError('denoising_loss draws from the per-molecule Philox streams: seed is required')
         x1, n_atoms = self._given_molecules(molecules)
+        if coupling is None:
+            coupling = 'ot' if hp.get('prior_align_x', False) else 'independent'
+        _check_coupling(coupling, n_atoms, 'denoising_loss')
         B = int(n_atoms.numel())
         tv = torch.as_tensor(t).detach().to('cpu', torch.float32).reshape(-1)
         tv = tv.expand(B).clone() if tv.numel() == 1 else tv
@@ -767,7 +787,7 @@ class FlowMol:
             tp = tv[part]
             tvals, group = torch.unique(tp, return_inverse=True)
             alphas = alpha_tables(tvals.clone(), cfg.schedule_type, cfg.cosine_params)[0]
-            state = eng.conditional_path(raw, alphas, group if tvals.numel() > 1 else None, seed=int(seed))
+            state = eng.conditional_path(raw, alphas, group if tvals.numel() > 1 else None, seed=int(seed), coupling=coupling)
             if distort is not None:
                 eng.distort(state['x_t'], distort[0], tp > distort[1], seed=int(seed))
             res = eng.denoising_loss(state, target, tp)
@@ -997,6 +1017,15 @@ ALLOWED_KWARGS = {
 
 
 RESAMPLE_KWARGS = {'dfm_type', 'tspan', 'cat_temp_func', 'forward_weight_func', 'inv_temp_func'}       # resample(): Philox only, so no rng and no noise hooks
+
+
+def _check_coupling(coupling, n_atoms: torch.Tensor, who: str) -> None:
+    """The refusals of a ``coupling`` argument, before any bind: an unknown value; with 'ot', a molecule above the cap of fm_ot_align."""
+    if coupling not in ('independent', 'ot'):
+        raise ValueError(f"{who}: coupling must be 'independent' or 'ot', got {coupling!r}")
+    if coupling == 'ot' and n_atoms.numel() and int(n_atoms.max()) > _lib.FM_OT_MAX_ATOMS:
+        m = int(n_atoms.argmax())
+        raise ValueError(f"{who}: coupling='ot' takes molecules of at most {_lib.FM_OT_MAX_ATOMS} atoms, molecule {m} has {int(n_atoms[m])}")
 
 
 def _keep_flat(keep, sizes, name: str, what: str) -> torch.Tensor:

@@ -14,17 +14,18 @@ import torch
 
 from . import _lib
 from .engine import IntegrationRun, alpha_tables, make_step_plan
-from .model import _keep_rows, _pairs_of_atoms
+from .model import _check_coupling, _keep_rows, _pairs_of_atoms
 
 
 class _Request:
-    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev', 'given', 'keep', 'spec')
+    __slots__ = ('ticket', 'n', 'T', 'mol_id', 'pos', 'state', 'prev', 'given', 'keep', 'spec', 'coupling')
 
-    def __init__(self, ticket, n, T, mol_id, start=0, given=None, keep=None):
+    def __init__(self, ticket, n, T, mol_id, start=0, given=None, keep=None, coupling='independent'):
         self.ticket, self.n, self.T, self.mol_id = ticket, n, T, mol_id
         self.pos = start      # the step it takes next: steps taken, or where a given molecule (submit_from) enters its schedule
         self.given = given    # submit_from: the molecule to corrupt {'x_t', 'a_t', 'c_t', 'e_t'} (CPU); None: start from the prior
         self.keep = keep      # submit_from(keep=...): (n,) bool, the atoms that stay as given, or {modality: its rows' bools}; None: nothing frozen
+        self.coupling = coupling      # submit_from(coupling=...): how the position prior is paired with the given molecule (Engine.conditional_path)
         self.spec = None      # its rows of Engine.inpaint_spec / freeze_spec, on the device, from admission on
         self.state = None     # {'x_t', 'a_t', 'c_t', 'e_t'}: this molecule's rows, on the device
         self.prev = None      # {'x', 'a', 'c', 'e'}: its previous endpoint prediction
@@ -64,14 +65,17 @@ class SamplingQueue:
             tickets.append(t)
         return tickets
 
-    def submit_from(self, molecules, start_step, n_timesteps=None, mol_ids=None, keep=None) -> List[int]:
+    def submit_from(self, molecules, start_step, n_timesteps=None, mol_ids=None, keep=None, coupling='independent') -> List[int]:
         """Queue given molecules for resampling (``FlowMol.resample``): molecule *i* is corrupted to time point ``start_step[i]`` of its
         ``n_timesteps[i]``-point schedule at admission and joins the running batch from there; ``start_step >= n_timesteps - 1`` retires at once with the
         corrupted state.  ``molecules`` / ``start_step`` / ``n_timesteps`` / ``mol_ids`` as in ``resample`` (ids default to the ticket numbers).  Every
         molecule is, bit for bit, ``model.resample([mol], start_step, n_timesteps, seed, mol_ids=[id])``.  ``keep``: the atoms that stay as given, as in
         ``resample`` -- such molecules are admitted into the running batch like any other and are, bit for bit, their ``resample(..., keep=...)`` run alone.
-        Both forms of ``keep`` are taken; a batch that holds requests of both is served in the per-modality form, of which the whole-atom form is a case."""
+        Both forms of ``keep`` are taken; a batch that holds requests of both is served in the per-modality form, of which the whole-atom form is a case.
+        ``coupling`` ('independent' | 'ot') as in ``resample``: requests of either kind share the running batch, a coupling only decides the prior a
+        molecule's path starts from."""
         x1, n_atoms = self.model._given_molecules(molecules)
+        _check_coupling(coupling, n_atoms, 'submit_from')
         sizes = n_atoms.tolist()
         B = len(sizes)
         n_pairs = [n * (n - 1) // 2 for n in sizes]
@@ -95,7 +99,7 @@ class SamplingQueue:
         for i in range(B):
             t = self._next_ticket
             self._next_ticket += 1
-            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1}, kept[i]))
+            self._pending.append(_Request(t, sizes[i], Ts[i], t if ids is None else ids[i], ks[i], {f: cols[f][i] for f in x1}, kept[i], coupling))
             tickets.append(t)
         return tickets
 
@@ -175,9 +179,9 @@ class SamplingQueue:
                 continue
             if joins:
                 groups.add((r.T, r.pos + 1))
-            by_key.setdefault((r.T, r.pos, r.given is not None), []).append(r)
+            by_key.setdefault((r.T, r.pos, r.given is not None, r.coupling), []).append(r)
         self._pending = keep
-        for (T, k, given), reqs in by_key.items():
+        for (T, k, given, coupling), reqs in by_key.items():
             sizes, spec = [r.n for r in reqs], None
             eng.bind(torch.tensor(sizes))
             eng.set_molecule_ids(torch.tensor([r.mol_id for r in reqs]))
@@ -185,14 +189,14 @@ class SamplingQueue:
                 x1 = {f: torch.cat([r.given[f] for r in reqs]) for f in ('x_t', 'a_t', 'c_t', 'e_t')}
                 alpha = alpha_tables(torch.linspace(0, 1, T), cfg.schedule_type, cfg.cosine_params)[0][k]
                 st1 = eng.make_state(x1['x_t'], x1['a_t'], x1['c_t'], x1['e_t'])
-                state = eng.conditional_path(st1, alpha, seed=self.seed)
+                state = eng.conditional_path(st1, alpha, seed=self.seed, coupling=coupling)
                 if any(isinstance(r.keep, dict) for r in reqs):          # one per-modality request: the group's first step runs in that form
                     none = lambda r, f: torch.zeros(r.n * (r.n - 1) // 2 if f == 'e' else r.n, dtype=torch.bool)
                     modal = [self._modal(r.keep) if r.keep is not None else {} for r in reqs]
                     live = [f for f in 'xace' if any(f in m for m in modal)]
-                    spec = eng.freeze_spec(st1, {f: torch.cat([m[f] if f in m else none(r, f) for r, m in zip(reqs, modal)]) for f in live}, self.seed)
+                    spec = eng.freeze_spec(st1, {f: torch.cat([m[f] if f in m else none(r, f) for r, m in zip(reqs, modal)]) for f in live}, self.seed, coupling=coupling)
                 elif any(r.keep is not None for r in reqs):
-                    spec = eng.inpaint_spec(st1, torch.cat([r.keep if r.keep is not None else torch.zeros(r.n, dtype=torch.bool) for r in reqs]), self.seed)
+                    spec = eng.inpaint_spec(st1, torch.cat([r.keep if r.keep is not None else torch.zeros(r.n, dtype=torch.bool) for r in reqs]), self.seed, coupling=coupling)
             else:
                 state = eng.prior_state(eng.prior_philox(self.seed))
             prev = None

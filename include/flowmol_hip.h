@@ -28,6 +28,11 @@
  *   fm_distort_philox   the geometry distortion of FlowMol.forward, flowmol.py:333-337, from the per-molecule counter-based streams
  *   fm_ctmc_step_inpaint, fm_integrate_inpaint   fm_ctmc_step / fm_integrate / fm_integrate_mixed with frozen atoms (replacement conditioning; no reference entry
  *                       point): after every step the kept rows are put back onto sample_conditional_path (ctmc_vector_field.py:97-143) of the given molecule
+ *   fm_ot_align         the coupling of the position prior to a data sample that every shipped training config switches on (prior_config.x.align: True):
+ *                       flowmol/data_processing/priors.py:109-169 align_prior(permutation=True, rigid_body=True) -- scipy's linear_sum_assignment on
+ *                       torch.cdist(x_1, x_0), then rigid_alignment, Kabsch without a determinant correction -- as coupled_node_prior :267-303 calls it
+ *                       for every sample of the training and validation loaders
+ *   fm_conditional_path_x0   fm_conditional_path on a caller-supplied position prior (the coupled one): flowmol.py:316-324 interpolates from the dataset's x_0
  *
  * Conventions
  *   - every function returns 0 on success or a negative fm_status; the message is available from
@@ -60,7 +65,7 @@
 extern "C" {
 #endif
 
-#define FM_ABI_VERSION 15
+#define FM_ABI_VERSION 16
 #define FM_MAX_CONVS 16
 
 typedef enum fm_status {
@@ -523,6 +528,42 @@ int fm_prune_rmsd(fm_ctx* ctx, void* stream, int n_groups, const int32_t* group_
 int fm_stereo(fm_ctx* ctx, void* stream, const float* x, const float* x_ref, const int32_t* elem_set /* (n_mols), -1 = none */,
               const int32_t* set_off /* (n_sets+1), in rows */, const int32_t* elems /* (rows,5) */, int n_sets, float flat_tol, int32_t* out /* (n_mols,8) */,
               const int32_t* val_off /* (n_mols+1) or NULL */, float* values /* or NULL */, float* x_out /* (N,3) or NULL */);
+
+/* --- ABI 16: the equivariant-OT coupling of the position prior -- the conditional path the network was TRAINED on starts from a prior that was assigned and
+ * rigidly fitted to the molecule, not from an independent Gaussian.
+ *
+ * fm_ot_align: x0 (N,3) the prior (fm_prior_philox's output), x1c (N,3) the given positions after fm_remove_com, both of the bound batch and both used AS GIVEN
+ * (nothing is re-centred for the cost: the reference's cost is between the dataset's COM-free x_1 and the prior).  Molecule by molecule, on the device:
+ *   A  the assignment: perm minimises sum_i c(i, perm[i]) with c(i, j) = sqrtf(((dx dx) + (dy dy)) + (dz dz)), d = x1c[i] - x0[j], every operation float32 and
+ *      separately rounded -- torch.cdist(x_1, x_0) (priors.py:113) up to rounding.  perm[i] is the LOCAL index of the prior row given to atom i (the reference's
+ *      prior_idx, :114-115), x0p[i] = x0[perm[i]].  Solver: shortest augmenting paths (Jonker-Volgenant, the algorithm behind linear_sum_assignment), rows inserted
+ *      in order, the next column the arg-min of the path costs with ties to the LOWEST column index.  Duals, path costs and minima are float64; a molecule's
+ *      float32 costs span far fewer than 2^29, so sums and differences of up to n of them are exact: perm is exactly optimal for the float32 cost matrix
+ *      above, and unique whenever that matrix has a unique optimum.  The matrix is never stored: LDS use is O(n).  Coordinates that are not numbers give the
+ *      identity permutation (and NaN results), in bounded work.
+ *   B  the rigid fit of x0p onto x1c (:128-169): means relative to the molecule's first atom, the 3x3 cross-covariance, Horn's 4x4 by fm_align_rmsd's fixed
+ *      Jacobi sweeps -- fm_align_rmsd's rounds and summation order.  allow_reflection = 1 is the REFERENCE'S behaviour, the optimum over all orthogonal
+ *      transforms (R = V U^T, no determinant correction): with lambda the eigenvalues of Horn's matrix, -lambda_min > lambda_max takes R = -R(q_min), otherwise
+ *      (ties included) R(q_max).  allow_reflection = 0 is the optimal PROPER rotation, fm_align_rmsd's.  x0_aligned = R (x0p - mean0) + mean1.
+ *   x0_aligned DEVICE (N,3); perm DEVICE (N) int32, may be NULL
+ *   out DEVICE (n_mols,4) float32 = {n, sum_i c(i, perm[i]) added in float64 in atom order and rounded once, sqrt(mean |x0p - x1c|^2) (after the permutation
+ *     only, nothing centred), sqrt(mean |x0_aligned - x1c|^2) from the explicit residuals}
+ * n = 0 gives {0, 0, 0, 0}; n = 1 gives perm = {0} and x0_aligned = x1c's row.  One wave per molecule, every sum in a fixed per-molecule order: a molecule's
+ * outputs are the same bits whatever else the batch holds.  Work is O(n^3 / 64) wave steps per molecule; FM_OT_MAX_ATOMS bounds it (GEOM-drugs' largest
+ * molecule, 181 atoms, with the 54 fake atoms of fake_atom_p = 0.3 is 235 rows).  Does not synchronise, allocates nothing.
+ * FM_ERR_INVALID (this call's status for every refusal), with a message and before anything is enqueued, for no bound batch, a bound molecule above
+ * FM_OT_MAX_ATOMS (read from the bind's host-side sizes; the message names it), allow_reflection outside {0, 1}, and an output that aliases an input or another
+ * output -- x0_aligned == x0 included, the kernel gathers from x0.
+ *
+ * fm_conditional_path_x0: fm_conditional_path's arguments and x0_in DEVICE (N,3): the position job reads x0_in[row] instead of drawing (one uniform branch).
+ * x0_in = NULL is fm_conditional_path bit for bit, and so is x0_in = fm_prior_philox(seed)'s output; the tokens and the tape's uniforms never depend on x0_in.
+ * tape->x0 receives the prior actually used, so the frozen-row structs (fm_inpaint / fm_freeze) carry a coupled path unchanged.  fm_conditional_path's
+ * refusals, and FM_ERR_INVALID for x0_in equal to out->x_t or tape->x0. */
+#define FM_OT_MAX_ATOMS 256
+int fm_ot_align(fm_ctx* ctx, void* stream, const float* x0, const float* x1c, int allow_reflection, float* x0_aligned /* (N,3) */,
+                int32_t* perm /* (N) or NULL */, float* out /* (n_mols,4) */);
+int fm_conditional_path_x0(fm_ctx* ctx, void* stream, uint64_t seed, const fm_state* x1, int n_groups, const int32_t* mol_group, const float* alpha,
+                           const fm_state* out, const fm_cond_tape* tape, const float* x0_in /* (N,3) or NULL */);
 
 /* debugging / parity taps: copy an internal buffer to `dst` (device) after the next fm_forward stages.
  * name: "embed.s", "sc.s", "sc.ef", "conv<i>.s", "conv<i>.v", "conv<i>.agg.s", "conv<i>.agg.v",
